@@ -5,28 +5,33 @@
 
 A "step" is one whole product C = A*B on device-resident, synthetic (splitmix64, density 1/2) operands, everything through
 libm4ri_amd.so's C ABI.  Inputs are in HBM before the timed region starts.
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--size 65536] [--workload mul|leaf16384|rect131072]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--size 65536] [--workload mul|leaf16384|rect131072] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the result line (`value`, `ms_per_step`, the configuration), nothing else.
+`--full` adds everything measured or checked beside the number: the fields listed at the end of this docstring and, at N > 1, the link
+probe, the one-GPU run, the second rung of the ladder and the stream of products.  `--dump-outputs DIR` writes the C of the last timed
+step as .npy files (dump_outputs) so that two builds can be compared output for output on the same seeded inputs.
 
 N = 1: Strassen-Winograd levels over batched M4RM leaves on one GPU (m4ri_amd_mul_dev).
 N > 1: the command that receives `--gpus N` is a CONTROLLER (under `torch.distributed.run` launcher rank 0 takes the role, the other
-launcher ranks step aside).  It measures, each in processes of its own: the links (every ordered pair of GPUs, `config.links`), the
-SAME product on ONE GPU (`speedup_vs_n1`), the product on N GPUs through a ladder of two transports, and the reference's multi-core
-path on this host (`cpu_baseline`; the reference switches to its multi-core path inside the same command,
+launcher ranks step aside).  It measures, each in processes of its own, the product on N GPUs through a ladder of two transports and,
+with --full, also the links (every ordered pair of GPUs, `config.links`), the SAME product on ONE GPU (`speedup_vs_n1`) and the
+reference's multi-core path on this host (`cpu_baseline`; the reference switches to its multi-core path inside the same command,
 bench/bench_multiplication.c:94-103) -- and always ends with exactly one JSON line (`config.controller_wall_s`).
   transports  `peer` = ONE process driving all GPUs through libm4ri_amd.so's distributed matrices (m4ri_amd_dmat_mul,
               m4ri_amd/csrc/multi.hip: the schedules behind the C boundary -- what mzd_mul_mp runs -- pieces pulled by
               hipMemcpyPeerAsync on per-link copy streams, one host thread per GPU); `rccl` = one process per GPU, torch.distributed
               (backend nccl == RCCL) send/recv + all-gather.  `--transport auto`: the FIRST rung that completes is the line (peer,
-              then rccl; with the development backend gloo: rccl, then peer) -- never the better of two; the other rung is measured
-              briefly beside it (`config.transports_measured`) and in full only when its first 3 steps are within 1.3x.
+              then rccl; with the development backend gloo: rccl, then peer) -- never the better of two; with --full the other rung is
+              measured briefly beside it (`config.transports_measured`) and in full only when its first 3 steps are within 1.3x.
   schedules   row slabs up to 4 ranks and for products a Strassen level cannot help (configs[4]); above, the sub-products of the top
               Strassen-Winograd level(s) over the ranks, slab-cyclic layout (m4ri_amd/sharding.py).
   numbers     `value` / `ms_per_step` = ONE product at a time (the metric is the wall clock of one mzd_mul); `pipelined_value` /
               `pipelined_ms_per_step` = a stream of independent products, two in flight (the transport of one under the
-              multiplications of the other): a second, separately named measurement, never the headline.
+              multiplications of the other): a second, separately named measurement (--full or --inflight 2), never the headline.
 
-Besides the contract fields the line carries "roofline" (the M4RM leaf launch against the HBM roofline: HIP events around every launch of
-the timed steps; "traffic" from rocprofv3 PMC passes at N = 1), "roofline_schedule" (bytes of the declared, unfused
+With --full, besides the contract fields the line carries "roofline" (the M4RM leaf launch against the HBM roofline: HIP events around
+every launch of the timed steps; "traffic" from rocprofv3 PMC passes at N = 1), "roofline_schedule" (bytes of the declared, unfused
 schedule over the step time against 8 TB/s), "cpu_baseline" (the real reference M4RI, oracle/_ref, on this host's cores) and "verified"
 (SHA-256 of the C the timed steps produced against the reference's, tests/golden).
 """
@@ -144,6 +149,51 @@ def sha_of_device_rows(t, chunk_rows=8192):
     return h.hexdigest()
 
 
+DUMP_SEED = 20261015        # the row / column sample of --dump-outputs: fixed, the same for every build and run
+DUMP_ROWS = 128             # rows of C dumped bit by bit
+DUMP_SAMPLE_BITS = 1 << 23  # at most this many bits of C in the bit-by-bit sample (32 MB as float32)
+DUMP_MAX_COLS = 1 << 20     # a column sample holds at most this many columns (their indices: 8 MB as float64)
+DUMP_MAX_GROUPS = 1 << 19   # per-row figures for at most this many rows, else for groups of consecutive rows (12 MB as float64)
+
+
+def dump_outputs(out_dir, rows_of, m, n):
+    """--dump-outputs: the C (m x n bits) of the last timed step as float .npy files under out_dir, at most 52 MB in all.
+    rows_of(r0, r1) returns rows r0..r1-1 of C on the host as words ([r1 - r0, ceil(n / 64)], column j = bit j % 64 of word j // 64).
+      C_rows_sample.npy         float32 [R, K]: the bits of a fixed, seeded sample of R rows (all n columns, or K sampled columns when
+                                R * n exceeds DUMP_SAMPLE_BITS); C_rows_sample_index.npy / C_cols_sample_index.npy: which (float64)
+      C_row_popcount.npy        float64 [G]: set bits per row of C -- every row, or every group of ceil(m / DUMP_MAX_GROUPS) rows
+      C_row_xor_fold.npy        float64 [G, 2]: XOR of the row's (group's) words, high and low 32 bits
+    The bits beyond column n in the last word of a row are not part of C and are cleared first."""
+    os.makedirs(out_dir, exist_ok=True)
+    w = (n + 63) // 64
+    tail = np.uint64((1 << (n % 64)) - 1) if n % 64 else np.uint64(0xFFFFFFFFFFFFFFFF)
+    rng = np.random.default_rng(DUMP_SEED)
+    rows = np.sort(rng.choice(m, min(m, DUMP_ROWS), replace=False))
+    cols = None if len(rows) * n <= DUMP_SAMPLE_BITS else np.sort(rng.choice(n, min(DUMP_MAX_COLS, DUMP_SAMPLE_BITS // len(rows)), replace=False))
+    sample = np.zeros((len(rows), n if cols is None else len(cols)), dtype=np.float32)
+    group = -(-m // DUMP_MAX_GROUPS)
+    pop = np.zeros(-(-m // group), dtype=np.int64)
+    fold = np.zeros(len(pop), dtype=np.uint64)
+    chunk = max(1, (64 << 20) // (8 * max(1, w)))   # rows per host chunk: 64 MiB of words
+    for r0 in range(0, m, chunk):
+        r1 = min(m, r0 + chunk)
+        c = np.array(rows_of(r0, r1), dtype=np.uint64).reshape(r1 - r0, w)   # a copy: the mask below must not touch C
+        if w:
+            c[:, -1] &= tail
+        g = np.arange(r0, r1) // group
+        np.add.at(pop, g, np.bitwise_count(c).sum(axis=1, dtype=np.int64))
+        np.bitwise_xor.at(fold, g, np.bitwise_xor.reduce(c, axis=1) if w else np.zeros(r1 - r0, np.uint64))
+        for i in np.nonzero((rows >= r0) & (rows < r1))[0]:
+            bits = np.unpackbits(c[rows[i] - r0].view(np.uint8), bitorder="little")[:n]
+            sample[i] = bits if cols is None else bits[cols]
+    np.save(os.path.join(out_dir, "C_rows_sample.npy"), sample)
+    np.save(os.path.join(out_dir, "C_rows_sample_index.npy"), rows.astype(np.float64))
+    if cols is not None:
+        np.save(os.path.join(out_dir, "C_cols_sample_index.npy"), cols.astype(np.float64))
+    np.save(os.path.join(out_dir, "C_row_popcount.npy"), pop.astype(np.float64))
+    np.save(os.path.join(out_dir, "C_row_xor_fold.npy"), np.stack([fold >> np.uint64(32), fold & np.uint64(0xFFFFFFFF)], axis=1).astype(np.float64))
+
+
 # ---------------------------------------------------------------------------------------------------
 # the controller of an N > 1 run
 # ---------------------------------------------------------------------------------------------------
@@ -219,26 +269,28 @@ def run_rung(transport: str, n_ranks: int, argv: list, watchdog_s: float, extra=
 
 
 def controller(args) -> int:
-    """`bench.py --gpus N` as a command: measure the links and the one-GPU time of the same product, start the ranks, watch them, fall
-    down the ladder, time the reference's multi-core path, and end with exactly one JSON line either way."""
+    """`bench.py --gpus N` as a command: start the ranks, watch them, fall down the ladder, and end with exactly one JSON line either way.
+    With --full also: measure the links and the one-GPU time of the same product first, the other rung beside the line, and the
+    reference's multi-core path last."""
     t_start = time.perf_counter()
     real = args.backend == "nccl"
     ladder = {"auto": ["peer", "rccl"] if real else ["rccl", "peer"], "rccl": ["rccl"], "peer": ["peer"]}[args.transport]
     me = os.path.abspath(__file__)
     # (a) what the links give, before anything is scheduled over them: one process, every ordered pair of ranks
     links = None
-    if not args.no_links:
+    if args.full and not args.no_links:
         line, why, _ = run_child([sys.executable, me, "--gpus", str(args.gpus), "--inner", "--links-probe"] + (["--virtual-ranks"] if args.virtual_ranks else []),
                                  min(args.watchdog, 180.0), key='"links"')
         links = json.loads(line)["links"] if line else {"error": why}
     # (b) the same product of the same binary on ONE GPU, in the same invocation: the denominator of the speed-up
     n1 = None
-    if not args.no_n1:
+    if args.full and not args.no_n1:
         line, why, _ = run_child([sys.executable, me, *own_args(sys.argv[1:], {"--gpus": 1, "--backend": 1, "--variant": 1, "--inflight": 1, "--overlap": 1,
-                                                                            "--shard-levels": 1, "--check": 0, "--virtual-ranks": 0, "--slab-overlap": 1}),
+                                                                            "--shard-levels": 1, "--check": 0, "--virtual-ranks": 0, "--slab-overlap": 1,
+                                                                            "--dump-outputs": 1}),
                                   "--gpus", "1", "--no-cpu-baseline", "--no-api", "--no-traffic"], args.watchdog)
         n1 = json.loads(line) if line else {"error": why}
-    # (c) the ladder: the first rung that completes is the line; the other is measured beside it, briefly unless it is close
+    # (c) the ladder: the first rung that completes is the line; with --full the other is measured beside it, briefly unless it is close
     failed, done, primary = [], {}, None
     for transport in ladder:
         extra = ["--compare-ms", f"{done[primary]['ms_per_step']:.4f}"] if primary else []
@@ -248,7 +300,7 @@ def controller(args) -> int:
         if line is not None:
             done[transport] = json.loads(line)
             primary = primary or transport
-            if not (args.transport == "auto" and real):
+            if not (args.transport == "auto" and real and args.full):
                 break
         else:
             failed.append({"transport": transport, "reason": why})
@@ -278,7 +330,7 @@ def controller(args) -> int:
         else:
             out["speedup_vs_n1"] = n1
     # (d) the reference's multi-core path on this host's cores, once, outside the ranks (they are gone by now)
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline_or_note(cfg["m"] if cfg.get("m") and cfg.get("m") == cfg.get("n") == cfg.get("l") else args.size)
     cfg["controller_wall_s"] = time.perf_counter() - t_start
     print(json.dumps(out), flush=True)
@@ -314,6 +366,11 @@ def main():
                     help="N > 1: what is handed out to the ranks (auto: slabs up to 4 ranks and for thin products, strassen above)")
     ap.add_argument("--shard-levels", type=int, default=0, help="strassen variant: sharded levels (1, 2; 0 = automatic)")
     ap.add_argument("--max-fuse", type=int, default=0, help="Strassen levels per fused pass (1..4; 0 = engine default: 4)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what is reported beside the number: the reference's CPU baseline, roofline and traffic, host-API "
+                         "timing, the SHA-256 of C against the reference's; at N > 1 the links, the one-GPU run, the other rung and the stream of products")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write the C of the last one as DIR/<name>.npy (float32 / float64, a fixed seeded sample, <= 52 MB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-api", action="store_true", help="skip the host-API (PCIe-inclusive) timing")
     ap.add_argument("--no-traffic", action="store_true", help="skip the rocprofv3 PMC passes (roofline.traffic = null)")
@@ -334,7 +391,7 @@ def main():
                     help="--gpus 1 only: initialise the process group anyway and run the N > 1 code path (its collectives, "
                          "batches and fences) at world size 1 -- how a one-GPU box puts the RCCL path through its paces")
     ap.add_argument("--inflight", type=int, default=0, choices=[0, 1, 2],
-                    help="N > 1: 2 (the default there) = after the timed loop (always one product at a time: `value`) also time a stream of products, "
+                    help="N > 1: 2 (the default there with --full) = after the timed loop (always one product at a time: `value`) also time a stream of products, "
                          "two in flight -- reported as pipelined_value / pipelined_ms_per_step; 1 = skip that")
     ap.add_argument("--transport", default="auto", choices=["auto", "rccl", "peer"],
                     help="N > 1: peer = one process, all GPUs, m4ri_amd_dmat_mul (peer copies); rccl = one process per GPU over torch.distributed; "
@@ -350,6 +407,8 @@ def main():
                     help="strassen variant: R or RxC -- row (x column) chunks per sub-product whose transport overlaps the products "
                          "(1 = none; default: 2 when a rank owns one large sub-product, else 1)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.links_probe:
         raise SystemExit(links_probe(args))
@@ -445,7 +504,7 @@ def main():
     phase_steps = None            # per buffer slot: an object with start() / multiply() / finish() (sharding.run_products)
     pipelined_step = None         # peer transport: product k of a stream, issued on lane k & 1
     last = {"slot": 0}            # the slot that holds the C of the last product
-    inflight = (args.inflight or 2) if multi else 1
+    inflight = (args.inflight or (2 if args.full else 1)) if multi else 1   # two in flight: the pipelined measurement
 
     # ---------------------------------------------------------------- N == 1 -----------------------
     if not multi:
@@ -689,7 +748,8 @@ def main():
         if 1e3 * quick / 3 > 1.3 * args.compare_ms:
             stopped_early = {"after_steps": 3, "ms_per_step": 1e3 * quick / 3, "compare_ms": args.compare_ms, "rule": "> 1.3 x the rung that is the line"}
             steps = 3
-    m4ri_amd.set_profiling(2)  # leaf launches bracketed by HIP events on their stream, accumulated over all steps
+    if args.full:
+        m4ri_amd.set_profiling(2)  # leaf launches bracketed by HIP events on their stream, accumulated over all steps (roofline)
     marks = [torch.cuda.Event(enable_timing=True) for _ in range(steps + 1)]
     elapsed, posted = timed(steps, marks=marks)
     step_ms = sorted(marks[k].elapsed_time(marks[k + 1]) for k in range(steps)) if not peer else None
@@ -714,17 +774,19 @@ def main():
     if peer:
         dC = dCs[last["slot"]]
 
-    # ---------------------------------------------------------------- correctness of what was timed --
+    # ---------------------------------------------------------------- correctness of what was timed, and the outputs --
     verified, Chost = None, None
-    want = golden_sha("mul", M, L, N, seeds) if (not args.no_verify and args.workload != "leaf16384") else None
-    if want is not None:
+    want = golden_sha("mul", M, L, N, seeds) if (args.full and not args.no_verify and args.workload != "leaf16384") else None
+    if want is not None or args.dump_outputs:
         what = "C of the last timed step vs the real reference's product of the same inputs (tests/golden/sha256.json)"
         got = None
         if not multi:
-            got = sha_of_device_rows(Cfull)
+            if want is not None:
+                got = sha_of_device_rows(Cfull)
         elif peer:
             Chost = dC.download()   # every device its own rows, outside the timed region
-            got = hashlib.sha256(Chost.masked().tobytes()).hexdigest()
+            if want is not None:
+                got = hashlib.sha256(Chost.masked().tobytes()).hexdigest()
             what = f"C of the last product, downloaded from the {world} ranks, vs the real reference's product of the same inputs (tests/golden/sha256.json)"
         else:
             # gather the ranks' rows of C on rank 0 (outside the timed region, over the same transport)
@@ -751,13 +813,19 @@ def main():
             exchange(sends, recvs)
             if rank == 0:
                 torch.cuda.synchronize()
-                got = sha_of_device_rows(Cfull)
+                if want is not None:
+                    got = sha_of_device_rows(Cfull)
                 what = f"C of the last product, gathered from the {world} ranks, vs the real reference's product of the same inputs (tests/golden/sha256.json)"
         if got is not None:
             verified = {"sha256": got, "matches_reference": got == want, "what": what}
             if got != want:
                 print(json.dumps({"error": "C differs from the reference", "sha256": got, "expected": want}), flush=True)
                 raise SystemExit(4)
+        if args.dump_outputs and rank == 0:
+            if peer:
+                dump_outputs(args.dump_outputs, lambda r0, r1: Chost.valid_words()[r0:r1], M, N)
+            else:
+                dump_outputs(args.dump_outputs, lambda r0, r1: Cfull[r0:r1].cpu().numpy().view(np.uint64), M, N)
     if args.check and multi:
         fullA = torch.empty((M, wl), dtype=torch.int64, device="cuda")
         fullB = torch.empty((L, w), dtype=torch.int64, device="cuda")
@@ -801,7 +869,7 @@ def main():
         leaf_ops = float(stats.leaf_m) * stats.leaf_l * stats.leaf_n * stats.leaf_products
         leaf_ms_per_product = leaf_launch_ms * max(1, int(stats.leaf_launches))
         traffic, traffic_detail = None, "not measured for this configuration"
-        if not multi and args.workload == "mul" and not args.no_traffic:
+        if args.full and not multi and args.workload == "mul" and not args.no_traffic:
             traffic, traffic_detail = measure_leaf_traffic(n, args.cutoff)
         workload = (f"mzd_mul_m4rm {n}^3 leaf only (BASELINE.json configs[1])" if args.workload == "leaf16384" else
                     f"mzd_mul {M}x{L}x{N} (BASELINE.json configs[4])" if args.workload == "rect131072" else
@@ -825,7 +893,9 @@ def main():
                 "workspace_GiB": stats.workspace_bytes / 2 ** 30,
                 **config_extra,
             },
-            "roofline": {
+        }
+        if args.full:
+            out["roofline"] = {
                 # the resource that binds the kernel is the LDS array (`lds` below); achieved / peak / frac are the HBM figures SURVEY.md 8(d) asks for
                 "bound": "lds",
                 "kernel": LEAF_KERNELS.get(int(stats.leaf_gen), "?") + " (the M4RM leaf; HIP events around every launch on its stream, mean over all timed steps)",
@@ -839,18 +909,17 @@ def main():
                                  int(stats.leaf_products) // max(1, int(stats.leaf_launches)), leaf_launch_ms),
                 "note": "the leaf is LDS-bound by design (table gathers at 256 B/clk/CU), not HBM-bound: its algorithmic HBM bytes are ~1e-3 of its "
                         "LDS traffic, so frac is small; the `lds` object prices the launch against the LDS-array cycles it needs (DESIGN.md 3.1)",
-            },
-        }
-        lds = out["roofline"]["lds"]
-        if lds and isinstance(traffic_detail, dict) and traffic_detail.get("gui_active_cycles"):
-            # in cycles the clock drops out: LDS-array cycles the launch needs / cycles it took (same launch, profiled pass)
-            need = lds["bound_ms"] * 1e-3 * PEAK_CLOCK_HZ
-            lds["frac_in_cycles"] = need / traffic_detail["gui_active_cycles"]
-            lds["effective_clock_hz"] = traffic_detail["effective_clock_hz"]
-            lds["note"] = ("frac prices the launch at the 2.4 GHz peak clock, frac_in_cycles at the clock it really ran at (GRBM_GUI_ACTIVE / duration): "
-                           "the kernel sits on the chip's power limit (measured: 1338 W of a 1400 W socket cap, the firmware's package-power limiter active 82 % of "
-                           "the launch's time, no thermal limiter -- profiles/r04_leaf_power/).  Of the cycles with the LDS idle ~10 % are bubbles of the gather "
-                           "pipeline itself (gathers alone: 90 % busy) and ~4.5 % the stage barrier (profiles/r03_leaf_decomposition/README.md)")
+            }
+            lds = out["roofline"]["lds"]
+            if lds and isinstance(traffic_detail, dict) and traffic_detail.get("gui_active_cycles"):
+                # in cycles the clock drops out: LDS-array cycles the launch needs / cycles it took (same launch, profiled pass)
+                need = lds["bound_ms"] * 1e-3 * PEAK_CLOCK_HZ
+                lds["frac_in_cycles"] = need / traffic_detail["gui_active_cycles"]
+                lds["effective_clock_hz"] = traffic_detail["effective_clock_hz"]
+                lds["note"] = ("frac prices the launch at the 2.4 GHz peak clock, frac_in_cycles at the clock it really ran at (GRBM_GUI_ACTIVE / duration): "
+                               "the kernel sits on the chip's power limit (measured: 1338 W of a 1400 W socket cap, the firmware's package-power limiter active 82 % of "
+                               "the launch's time, no thermal limiter -- profiles/r04_leaf_power/).  Of the cycles with the LDS idle ~10 % are bubbles of the gather "
+                               "pipeline itself (gathers alone: 90 % busy) and ~4.5 % the stage barrier (profiles/r03_leaf_decomposition/README.md)")
         if step_ms:
             out["step_ms_min"], out["step_ms_median"] = step_ms[0], step_ms[len(step_ms) // 2]
         out["host_issue_ms_per_step"] = host_issue_ms
@@ -874,7 +943,7 @@ def main():
                                                          if ms.variant == m4ri_amd.VARIANT_STRASSEN else "slabs: gather done; first product done; all done")})
         if verified is not None:
             out["verified"] = verified
-        if args.workload != "leaf16384":
+        if args.full and args.workload != "leaf16384":
             # the whole product against the HBM roofline in SURVEY.md 8(d)'s terms (schedule bytes of this rank's products / step time)
             pm, pl, pn = per_rank_product
             nprod_rank = 1 if (not multi or args.variant != "strassen") else len(sharding.owned_products(plan, 0))
@@ -899,13 +968,13 @@ def main():
                         "one-write kernel (median of 5), the practical ceiling of the passes; our fused multi-level passes move far fewer bytes than the "
                         "unfused schedule (no fraction is quoted against a per-box ceiling: it would move with the box)",
             }
-        if not multi and args.workload != "leaf16384" and not args.no_api:
+        if args.full and not multi and args.workload != "leaf16384" and not args.no_api:
             try:
                 out["api"] = host_api_timing(A, B, M, L, N, args.cutoff)
                 out["api_ms"] = out["api"]["c_given_ms_min"]
             except Exception as e:  # noqa: BLE001 -- reported beside the number, never required for it
                 out["api"] = {"error": repr(e)}
-        if not multi and not args.no_cpu_baseline:
+        if args.full and not multi and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline_or_note(n)
         print(json.dumps(out), flush=True)
     if dist is not None:

@@ -10,5 +10,5 @@ for n in 32768 65536; do echo "== LD_PRELOAD=libm4ri_amd.so, n=$n"; M4RI_AMD_STA
 (cd /tmp && export TMPDIR=/tmp && rm -rf /tmp/prof_ple && rocprofv3 --kernel-trace --stats -d /tmp/prof_ple -o t -- python $R/tools/ple_profile_driver.py 65536 > /tmp/prof_ple.log 2>&1; f=$(find /tmp/prof_ple -name "*results.db" | head -1); python $R/tools/rocpd_summary.py $f > $O/r02_ple_65536_trace.summary.txt 2>&1)
 bash tools/prof_bench.sh r02_ > $O/prof_bench.log 2>&1
 bash tools/prof_transpose.sh r02 > $O/prof_transpose.log 2>&1
-python bench.py --steps 20 --warmup 5 > $O/r02_bench_final.json 2> $O/r02_bench_final.err
+python bench.py --steps 20 --warmup 5 --full > $O/r02_bench_final.json 2> $O/r02_bench_final.err
 cat $O/r02_pytest_final.log; cat $O/r02_l4_device_timing.log | grep 65536; tail -4 $O/r02_l4_timing_final.log; tail -c 300 $O/r02_bench_final.json

@@ -48,9 +48,11 @@ def run(bench, capsys, monkeypatch, outcomes, **kw):
     monkeypatch.setattr(bench, "run_rung", fake_rung)
     monkeypatch.setattr(bench, "run_child", fake_child)
     monkeypatch.setattr(bench, "cpu_baseline_or_note", lambda n: {"value": 1.8e13, "unit": "bit-op/s", "cores": 256, "kind": "reference", "sample": f"stand-in {n}"})
-    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "8", "--steps", "5"])
+    full = kw.get("full", True)   # everything beside the number is measured with --full only (a plain run: the first rung, nothing else)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "8", "--steps", "5"] + (["--full"] if full else []) + kw.get("argv_extra", []))
     args = argparse.Namespace(gpus=8, size=65536, transport=kw.get("transport", "auto"), variant="auto", backend=kw.get("backend", "nccl"), watchdog=5.0,
-                              no_links=kw.get("no_links", False), no_n1=kw.get("no_n1", False), no_cpu_baseline=kw.get("no_cpu_baseline", False), virtual_ranks=False)
+                              no_links=kw.get("no_links", False), no_n1=kw.get("no_n1", False), no_cpu_baseline=kw.get("no_cpu_baseline", False), virtual_ranks=False,
+                              full=full)
     rc = bench.controller(args)
     out = capsys.readouterr().out.splitlines()
     return rc, [json.loads(ln) for ln in out if ln.startswith("{")], tried, out, children
@@ -110,6 +112,26 @@ def test_a_failed_probe_or_one_gpu_run_is_noted_not_fatal(bench, capsys, monkeyp
     rc, lines, _, _, children = run(bench, capsys, monkeypatch, {"peer": (line(5.2, "peer"), None), "rccl": (line(5.5, "rccl"), None)},
                                     no_links=True, no_n1=True, no_cpu_baseline=True)
     assert rc == 0 and children == [] and "links" not in lines[0]["config"] and "speedup_vs_n1" not in lines[0] and "cpu_baseline" not in lines[0]
+
+
+def test_a_plain_run_is_the_first_rung_that_completes_and_nothing_else(bench, capsys, monkeypatch):
+    """Without --full the command measures its headline only: no link probe, no one-GPU run, no second rung, no CPU baseline."""
+    rc, lines, tried, _, children = run(bench, capsys, monkeypatch, {"peer": (line(5.2, "peer"), None), "rccl": (line(4.9, "rccl"), None)}, full=False)
+    assert rc == 0 and [t for t, _ in tried] == ["peer"] and children == [] and len(lines) == 1
+    o, cfg = lines[0], lines[0]["config"]
+    assert cfg["transport"] == "peer" and o["ms_per_step"] == 5.2 and o["value"] > 0 and cfg["controller_wall_s"] >= 0
+    assert not {"cpu_baseline", "speedup_vs_n1"} & set(o) and not {"links", "transports_measured"} & set(cfg)
+    rc, lines, tried, _, children = run(bench, capsys, monkeypatch, {"peer": (None, "exit code 2"), "rccl": (line(4.9, "rccl"), None)}, full=False)
+    assert rc == 0 and [t for t, _ in tried] == ["peer", "rccl"] and children == [] and lines[0]["config"]["transport_fallback"][0]["transport"] == "peer"
+
+
+def test_the_one_gpu_run_does_not_dump_outputs(bench, capsys, monkeypatch):
+    """--dump-outputs goes to the rungs (the product the line is about), never to the one-GPU run beside it."""
+    rc, _, _, _, children = run(bench, capsys, monkeypatch, {"peer": (line(5.2, "peer"), None), "rccl": (line(4.9, "rccl"), None)},
+                                    argv_extra=["--dump-outputs", "out_dir"])
+    n1_cmd = [c for c in children if "--links-probe" not in c][0]
+    assert rc == 0 and "--dump-outputs" not in n1_cmd and "out_dir" not in n1_cmd and "--full" in n1_cmd
+    assert bench.own_args(["--gpus", "8", "--dump-outputs", "out_dir", "--full"]) == ["--gpus", "8", "--dump-outputs", "out_dir", "--full"]
 
 
 def test_a_rung_gets_the_commands_arguments_minus_the_controllers(bench, monkeypatch):

@@ -99,7 +99,7 @@ def test_bench_ranks_on_one_gpu(world, variant):
     # rank 0 becomes the controller of the run, starts the ranks that do the work and prints their line; the other launcher ranks step aside
     cmd = [sys.executable, "-m", "torch.distributed.run", "--standalone", "--local-addr", "127.0.0.1", "--nnodes=1", f"--nproc-per-node={world}",
            os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "1", "--warmup", "1",
-           "--size", "8192", "--backend", "gloo", "--check", "--variant", variant, "--no-cpu-baseline", "--no-links", "--no-n1", "--transport", "rccl"]
+           "--size", "8192", "--backend", "gloo", "--check", "--variant", variant, "--no-cpu-baseline", "--no-links", "--no-n1", "--transport", "rccl", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     assert r.stdout.count("-> OK") == world and r.stdout.count('"metric"') == 1, r.stdout[-3000:]
@@ -128,9 +128,10 @@ def test_baseline_sizes_through_the_sharded_path_vs_reference_sha256(m, l, n, se
 
 # ---- bench.py as the driver runs it: the command itself starts the ranks ---------------------------------------------
 def _bench(args, timeout=900, lean=True):
-    """`python bench.py ...` exactly as typed (no launcher around it); returns rank 0's JSON line and the whole stdout.  lean: without the
+    """`python bench.py --full ...` (no launcher around it); returns rank 0's JSON line and the whole stdout.  lean: without the
     controller's link probe and one-GPU run (two more processes per call; the tests that are about them pass lean=False)."""
     import json
+    args = list(args) + ["--full"]   # the measurements and checks beside the number (SHA-256 vs the reference, the stream of products, ...)
     if lean:
         args = list(args) + [f for f in ("--no-links", "--no-n1") if f not in args]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
@@ -312,7 +313,7 @@ def test_bench_falls_back_down_the_ladder_and_still_prints_one_line(inject):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
     base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--size", "8192", "--backend", "gloo", "--steps", "1", "--warmup", "1",
-            "--no-cpu-baseline", "--watchdog", "90" if inject == "crash" else "45"]
+            "--no-cpu-baseline", "--watchdog", "90" if inject == "crash" else "45", "--full"]
     r = subprocess.run(base + ["--virtual-ranks", "--check"], capture_output=True, text=True, env=env, timeout=900, cwd=ROOT)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert r.returncode == 0 and len(lines) == 1, r.stdout[-3000:] + r.stderr[-3000:]
