@@ -302,6 +302,21 @@ int m4ri_amd_transpose_dev(word *D, int64_t d_stride, const word *A, int64_t a_s
 int m4ri_amd_trtri_upper_dev(word *U, int64_t stride, int64_t n, void *stream);
 /* Device twins of mzd_echelonize* and mzd_apply_p_right{,_trans} (echelon.hip).  P: HOST array.  Blocking. */
 int m4ri_amd_echelonize_dev(word *A, int64_t stride, int64_t nrows, int64_t ncols, int full, int32_t *rank_out, void *stream);
+/* `batch` independent (reduced) row echelon forms in place (echelon_batch.hip).  Member b is the nrows x ncols matrix at
+ * A + b * a_bs (words), rows `stride` words apart; each comes out bit-identical to m4ri_amd_echelonize_dev (mzd_echelonize) with
+ * the same `full`.  rank[b] (DEVICE int32 array, batch entries) = its rank; pivots (DEVICE int32, batch * min(nrows, ncols) entries,
+ * member b at b * min(nrows, ncols), or NULL): the pivot column of each of the first rank[b] rows, -1 after them.  Bits at columns
+ * >= ncols of a row's last word, the words from the width to `stride` of a row and the words between members are never written.
+ * hipErrorInvalidValue, before any HIP call, for negative sizes, stride < width, overlapping members (batch > 1 and
+ * a_bs < (nrows - 1) * stride + width) or rank == NULL with batch > 0.  Asynchronous on `stream` (one launch, no allocation, no
+ * copy: capturable) on paths 0-2 of m4ri_amd_plan_echelonize_batch; path 3 allocates and BLOCKS. */
+int m4ri_amd_echelonize_batch_dev(word *A, int64_t stride, int64_t a_bs, int64_t nrows, int64_t ncols, int64_t batch, int full, int32_t *rank,
+                                  int32_t *pivots, void *stream);
+/* which path m4ri_amd_echelonize_batch_dev takes for members of this shape (pure host arithmetic; -1 for negative sizes):
+ * 0 one wave per member, rows in registers (nrows, ncols <= 64); 1 one workgroup per member, member in LDS (rows padded to an odd
+ * number of words, plus a row index and flags, within 160 KiB); 2 one workgroup per member, in place in global memory (valid words
+ * up to 512 KiB); 3 members one by one through m4ri_amd_echelonize_dev (blocking) */
+int m4ri_amd_plan_echelonize_batch(int64_t nrows, int64_t ncols);
 int m4ri_amd_apply_p_right_dev(word *A, int64_t stride, int64_t nrows, int64_t ncols, const int32_t *P, int64_t length, int trans, void *stream);
 /* Row r <- its columns under the transpositions (i, Q[i]), i = r+1 .. ncols-1 ascending (mzd_apply_p_right_trans_tri,
  * m4ri/mzp.c:279-293).  Q: HOST array, ncols entries, Q[i] >= i.  Blocking. */

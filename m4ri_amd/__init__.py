@@ -173,6 +173,8 @@ SYMBOLS = {
     "m4ri_amd_model_seconds_batch": (ctypes.c_double, [_I64, _I64, _I64, _I, _I64]),
     "m4ri_amd_trtri_upper_dev": (_I, [_P, _I64, _I64, _P]),
     "m4ri_amd_echelonize_dev": (_I, [_P, _I64, _I64, _I64, _I, _P, _P]),
+    "m4ri_amd_echelonize_batch_dev": (_I, [_P, _I64, _I64, _I64, _I64, _I64, _I, _P, _P, _P]),
+    "m4ri_amd_plan_echelonize_batch": (_I, [_I64, _I64]),
     "m4ri_amd_apply_p_right_dev": (_I, [_P, _I64, _I64, _I64, _P, _I64, _I, _P]),
     "m4ri_amd_mzd_init": (MzdPtr, [_I, _I]),
     "m4ri_amd_mzd_free": (None, [MzdPtr]),
@@ -465,6 +467,19 @@ def mul_batch_dev(C: int, c_stride: int, c_bs: int, A: int, a_stride: int, a_bs:
 def model_seconds_batch(m: int, l: int, n: int, levels: int = -1, batch: int = 1) -> float:
     """The engine's time model for `batch` products scheduled as one (levels < 0: at the depth the model picks). Host arithmetic."""
     return float(lib().m4ri_amd_model_seconds_batch(m, l, n, levels, batch))
+
+
+def echelonize_batch_dev(A: int, stride: int, a_bs: int, nrows: int, ncols: int, batch: int, full: int, rank: int, pivots: int = 0,
+                         stream: int = 0) -> None:
+    """`batch` (reduced) row echelon forms in place, member b at A + b * a_bs words; rank / pivots: DEVICE int32 arrays (pivots 0 =
+    not wanted).  Asynchronous on paths 0-2 of plan_echelonize_batch, blocking on path 3."""
+    _check(lib().m4ri_amd_echelonize_batch_dev(A, stride, a_bs, nrows, ncols, batch, int(full), rank, pivots or None, stream),
+           "m4ri_amd_echelonize_batch_dev")
+
+
+def plan_echelonize_batch(nrows: int, ncols: int) -> int:
+    """The path echelonize_batch_dev takes for members of this shape (0 wave, 1 LDS, 2 global, 3 one by one). Host arithmetic."""
+    return int(lib().m4ri_amd_plan_echelonize_batch(nrows, ncols))
 
 
 def m4rm_dev(C: int, c_stride: int, A: int, a_stride: int, B: int, b_stride: int, m: int, l: int, n: int,
