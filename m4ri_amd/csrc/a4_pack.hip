@@ -6,7 +6,7 @@
 // entries, 2048 x 1024 tiles -- retired in round 2 when generation 4 turned out to be at least as fast on every shape,
 // short tiles included: DESIGN.md 3.1.)
 #include <hip/hip_runtime.h>
-#include "gf2_common.h"
+#include "gf2_internal.h"
 
 namespace {
 

@@ -1,7 +1,7 @@
 // aux_kernels.hip -- the HBM-bound helpers around the M4RM leaf: the fused Strassen-Winograd passes
-// (one, two or three levels per pass; the A side optionally written straight into the leaf's packed
-// form), strided XOR / copy / masked copy, the fold of split leaf launches, tail masking and the
-// deterministic fill.
+// (one to four levels per pass, chosen by gf2_launch_pass_* at the end of this file; the A side
+// optionally written straight into the leaf's packed form), strided XOR / copy / masked copy, the
+// fold of split leaf launches, tail masking and the deterministic fill.
 //
 // The passes replace the reference's 15 separate quadrant additions per recursion node
 // (_mzd_add, /root/reference m4ri/mzd.c:1471-1583, called from m4ri/strassen.c:111-150) by one
@@ -13,7 +13,7 @@
 // contiguous -- bounded by HBM bandwidth; only the packed-output passes tile (an LDS transpose).
 #include <hip/hip_runtime.h>
 #include <cstdlib>
-#include "gf2_common.h"
+#include "gf2_internal.h"
 
 namespace {
 
@@ -325,9 +325,9 @@ inline bool vec_ok(const void *p, int64_t stride, int64_t bs, int64_t cw, int64_
 
 typedef unsigned long long __attribute__((ext_vector_type(2))) word2;
 
-extern "C" hipError_t gf2_launch_winograd_down(hipStream_t s, int bside, const word *parent,
-                                               int64_t p_stride, int64_t p_bs, word *child,
-                                               int64_t nparents, int64_t crows, int64_t cw) {
+static hipError_t gf2_launch_winograd_down(hipStream_t s, int bside, const word *parent,
+                                           int64_t p_stride, int64_t p_bs, word *child,
+                                           int64_t nparents, int64_t crows, int64_t cw) {
   // child matrices: crows x cw words, contiguous (stride cw), batch stride crows*cw
   const int64_t c_bs = crows * cw;
   if (nparents * c_bs == 0) return hipSuccess;
@@ -353,9 +353,9 @@ extern "C" hipError_t gf2_launch_winograd_down(hipStream_t s, int bside, const w
   return hipGetLastError();
 }
 
-extern "C" hipError_t gf2_launch_winograd_up(hipStream_t s, int acc, const word *prod, word *parent,
-                                             int64_t o_stride, int64_t o_bs, int64_t nparents,
-                                             int64_t crows, int64_t cw) {
+static hipError_t gf2_launch_winograd_up(hipStream_t s, int acc, const word *prod, word *parent,
+                                         int64_t o_stride, int64_t o_bs, int64_t nparents,
+                                         int64_t crows, int64_t cw) {
   const int64_t p_bs = crows * cw;
   if (nparents * p_bs == 0) return hipSuccess;
   if (vec_ok(prod, cw, p_bs, cw, cw) && vec_ok(parent, o_stride, o_bs, cw, cw)) {
@@ -518,14 +518,14 @@ __global__ __launch_bounds__(AUX_THREADS) void winograd_down2_pack_kernel(
 // Grandchild i of the pass lands at a4 + i * (crows * cw * 2) dwords, laid out exactly as
 // gf2_launch_a4_pack(_rot) would have packed the row-major grandchild.  Returns
 // hipErrorInvalidValue when the shape does not tile (caller falls back to down2 + pack).
-extern "C" int gf2_winograd_down2_pack_ok(const word *gparent, int64_t p_stride, int64_t p_bs, const word *a4,
-                                          int64_t crows, int64_t cw) {
+static int gf2_winograd_down2_pack_ok(const word *gparent, int64_t p_stride, int64_t p_bs, const word *a4,
+                                      int64_t crows, int64_t cw) {
   return vec_ok(gparent, p_stride, p_bs, cw, cw) && crows > 0 && cw > 0 && crows % DP_ROWS == 0 && cw % (2 * DP_V) == 0 &&
          (reinterpret_cast<uintptr_t>(a4) & 15) == 0;
 }
 
-extern "C" hipError_t gf2_launch_winograd_down2_pack(hipStream_t s, const word *gparent, int64_t p_stride, int64_t p_bs,
-                                                     word *a4, int64_t nparents, int64_t crows, int64_t cw, int rot) {
+static hipError_t gf2_launch_winograd_down2_pack(hipStream_t s, const word *gparent, int64_t p_stride, int64_t p_bs,
+                                                 word *a4, int64_t nparents, int64_t crows, int64_t cw, int rot) {
   if (nparents * crows * cw == 0) return hipSuccess;
   if (!gf2_winograd_down2_pack_ok(gparent, p_stride, p_bs, a4, crows, cw)) return hipErrorInvalidValue;
   const int64_t tiles_r = crows / DP_ROWS, tiles_w = (cw / 2) / DP_V;
@@ -761,8 +761,8 @@ __global__ __launch_bounds__(DP3_THREADS) void winograd_down3_pack_kernel(
 }
 }  // namespace
 
-extern "C" hipError_t gf2_launch_winograd_down3(hipStream_t s, int bside, const word *anc, int64_t p_stride, int64_t p_bs,
-                                                word *gchild, int64_t nparents, int64_t crows, int64_t cw) {
+static hipError_t gf2_launch_winograd_down3(hipStream_t s, int bside, const word *anc, int64_t p_stride, int64_t p_bs,
+                                            word *gchild, int64_t nparents, int64_t crows, int64_t cw) {
   const int64_t c_bs = crows * cw;
   if (nparents * c_bs == 0) return hipSuccess;
   const int64_t total = nparents * c_bs;
@@ -775,8 +775,8 @@ extern "C" hipError_t gf2_launch_winograd_down3(hipStream_t s, int bside, const 
   return hipGetLastError();
 }
 
-extern "C" hipError_t gf2_launch_winograd_up3(hipStream_t s, int acc, const word *prod, word *anc, int64_t o_stride,
-                                              int64_t o_bs, int64_t nparents, int64_t crows, int64_t cw) {
+static hipError_t gf2_launch_winograd_up3(hipStream_t s, int acc, const word *prod, word *anc, int64_t o_stride,
+                                          int64_t o_bs, int64_t nparents, int64_t crows, int64_t cw) {
   const int64_t p_bs = crows * cw;
   if (nparents * p_bs == 0) return hipSuccess;
   const int64_t total = nparents * p_bs;
@@ -789,14 +789,14 @@ extern "C" hipError_t gf2_launch_winograd_up3(hipStream_t s, int acc, const word
   return hipGetLastError();
 }
 
-extern "C" int gf2_winograd_down3_pack_ok(const word *a4, int64_t crows, int64_t cw) {
+static int gf2_winograd_down3_pack_ok(const word *a4, int64_t crows, int64_t cw) {
   return crows > 0 && cw > 0 && crows % DP3_ROWS == 0 && cw % DP3_W == 0 && (reinterpret_cast<uintptr_t>(a4) & 7) == 0;
 }
 
 // Great-grandchild i of the pass lands at a4 + i * (crows * cw * 2) dwords, laid out exactly as
 // gf2_launch_a4_pack(_rot) would have packed the row-major great-grandchild.
-extern "C" hipError_t gf2_launch_winograd_down3_pack(hipStream_t s, const word *anc, int64_t p_stride, int64_t p_bs,
-                                                     word *a4, int64_t nparents, int64_t crows, int64_t cw, int rot) {
+static hipError_t gf2_launch_winograd_down3_pack(hipStream_t s, const word *anc, int64_t p_stride, int64_t p_bs,
+                                                 word *a4, int64_t nparents, int64_t crows, int64_t cw, int rot) {
   if (nparents * crows * cw == 0) return hipSuccess;
   if (!gf2_winograd_down3_pack_ok(a4, crows, cw)) return hipErrorInvalidValue;
   const int64_t tiles_r = crows / DP3_ROWS, tiles_w = cw / DP3_W;
@@ -1272,8 +1272,8 @@ __global__ __launch_bounds__(DP3_THREADS) void winograd_down4_pack_kernel(
 
 // Descendant 343 * j0 + 49 * j1 + 7 * j2 + j3 of ancestor i is stored at index 2401 * i + that; descendants are crows x cw words,
 // contiguous; an ancestor is 16 * crows rows x 16 * cw words with row stride p_stride.
-extern "C" hipError_t gf2_launch_winograd_down4(hipStream_t s, int bside, const word *anc, int64_t p_stride, int64_t p_bs,
-                                                word *gchild, int64_t nparents, int64_t crows, int64_t cw) {
+static hipError_t gf2_launch_winograd_down4(hipStream_t s, int bside, const word *anc, int64_t p_stride, int64_t p_bs,
+                                            word *gchild, int64_t nparents, int64_t crows, int64_t cw) {
   const int64_t c_bs = crows * cw;
   if (nparents * c_bs == 0) return hipSuccess;
   // the form that reads the ancestor once through LDS needs the 32 positions of a workgroup inside one descendant row: 0.92 ms against
@@ -1300,8 +1300,8 @@ extern "C" hipError_t gf2_launch_winograd_down4(hipStream_t s, int bside, const 
 
 // anc (+)= the recombination of the 2401 products per ancestor.  acc == 0: the ancestor's 16 crows x 16 cw words are zeroed first (the
 // seven top-level products of a word meet in it by atomic XOR); acc != 0: they are added onto what is there.
-extern "C" hipError_t gf2_launch_winograd_up4(hipStream_t s, int acc, const word *prod, word *anc, int64_t o_stride, int64_t o_bs,
-                                              int64_t nparents, int64_t crows, int64_t cw) {
+static hipError_t gf2_launch_winograd_up4(hipStream_t s, int acc, const word *prod, word *anc, int64_t o_stride, int64_t o_bs,
+                                          int64_t nparents, int64_t crows, int64_t cw) {
   const int64_t p_bs = crows * cw;
   if (nparents * p_bs == 0) return hipSuccess;
   // the form that combines the seven top-level products in LDS needs the 32 positions of a workgroup inside one row
@@ -1331,8 +1331,8 @@ extern "C" hipError_t gf2_launch_winograd_up4(hipStream_t s, int acc, const word
   return hipGetLastError();
 }
 
-extern "C" hipError_t gf2_launch_winograd_down4_pack(hipStream_t s, const word *anc, int64_t p_stride, int64_t p_bs, word *a4,
-                                                     int64_t nparents, int64_t crows, int64_t cw, int rot) {
+static hipError_t gf2_launch_winograd_down4_pack(hipStream_t s, const word *anc, int64_t p_stride, int64_t p_bs, word *a4,
+                                                 int64_t nparents, int64_t crows, int64_t cw, int rot) {
   if (nparents * crows * cw == 0) return hipSuccess;
   if (!gf2_winograd_down3_pack_ok(a4, crows, cw)) return hipErrorInvalidValue;
   // the form without the transpose (one word column x 32 rows per workgroup, the grid through LDS) wherever the shape allows it:
@@ -1364,8 +1364,8 @@ extern "C" hipError_t gf2_launch_winograd_down4_pack(hipStream_t s, const word *
 // Two levels per pass.  Grandchildren are crows x cw words, contiguous; a grandparent is 4*crows rows
 // x 4*cw words with row stride p_stride; grandchild 7*j1 + j2 of grandparent i is stored at index
 // 49*i + 7*j1 + j2.
-extern "C" hipError_t gf2_launch_winograd_down2(hipStream_t s, int bside, const word *gparent, int64_t p_stride,
-                                                int64_t p_bs, word *gchild, int64_t nparents, int64_t crows, int64_t cw) {
+static hipError_t gf2_launch_winograd_down2(hipStream_t s, int bside, const word *gparent, int64_t p_stride,
+                                            int64_t p_bs, word *gchild, int64_t nparents, int64_t crows, int64_t cw) {
   const int64_t c_bs = crows * cw;
   if (nparents * c_bs == 0) return hipSuccess;
   if (vec_ok(gparent, p_stride, p_bs, cw, cw) && vec_ok(gchild, cw, c_bs, cw, cw)) {
@@ -1390,8 +1390,8 @@ extern "C" hipError_t gf2_launch_winograd_down2(hipStream_t s, int bside, const 
   return hipGetLastError();
 }
 
-extern "C" hipError_t gf2_launch_winograd_up2(hipStream_t s, int acc, const word *prod, word *gparent, int64_t o_stride,
-                                              int64_t o_bs, int64_t nparents, int64_t crows, int64_t cw) {
+static hipError_t gf2_launch_winograd_up2(hipStream_t s, int acc, const word *prod, word *gparent, int64_t o_stride,
+                                          int64_t o_bs, int64_t nparents, int64_t crows, int64_t cw) {
   const int64_t p_bs = crows * cw;
   if (nparents * p_bs == 0) return hipSuccess;
   if (vec_ok(prod, cw, p_bs, cw, cw) && vec_ok(gparent, o_stride, o_bs, cw, cw)) {
@@ -1414,4 +1414,45 @@ extern "C" hipError_t gf2_launch_winograd_up2(hipStream_t s, int acc, const word
                          gparent, o_stride, o_bs, nparents, crows, cw);
   }
   return hipGetLastError();
+}
+
+// ---- the pass of `levels` fused levels (gf2_internal.h): the Winograd form of that depth, or the rank-R scheme's ---------------
+extern "C" hipError_t gf2_launch_pass_down(hipStream_t s, int levels, int scheme, int bside, const word *src, int64_t stride, int64_t bs,
+                                           word *dst, int64_t nparents, int64_t crows, int64_t cw) {
+  if (scheme) return gf2_launch_scheme_down(s, levels, bside, src, stride, bs, dst, nparents, crows, cw);
+  switch (levels) {
+    case 4: return gf2_launch_winograd_down4(s, bside, src, stride, bs, dst, nparents, crows, cw);
+    case 3: return gf2_launch_winograd_down3(s, bside, src, stride, bs, dst, nparents, crows, cw);
+    case 2: return gf2_launch_winograd_down2(s, bside, src, stride, bs, dst, nparents, crows, cw);
+    case 1: return gf2_launch_winograd_down(s, bside, src, stride, bs, dst, nparents, crows, cw);
+    default: return hipErrorInvalidValue;
+  }
+}
+
+extern "C" int gf2_pass_down_pack_ok(int levels, const word *src, int64_t stride, int64_t bs, const word *a4, int64_t crows, int64_t cw) {
+  if (levels >= 3) return gf2_winograd_down3_pack_ok(a4, crows, cw);  // (the four-level pass tiles like the three-level one)
+  return levels == 2 && gf2_winograd_down2_pack_ok(src, stride, bs, a4, crows, cw);
+}
+
+extern "C" hipError_t gf2_launch_pass_down_pack(hipStream_t s, int levels, int scheme, const word *src, int64_t stride, int64_t bs,
+                                                word *a4, int64_t nparents, int64_t crows, int64_t cw, int rot) {
+  if (scheme) return gf2_launch_scheme_down_pack(s, levels, src, stride, bs, a4, nparents, crows, cw);
+  switch (levels) {
+    case 4: return gf2_launch_winograd_down4_pack(s, src, stride, bs, a4, nparents, crows, cw, rot);
+    case 3: return gf2_launch_winograd_down3_pack(s, src, stride, bs, a4, nparents, crows, cw, rot);
+    case 2: return gf2_launch_winograd_down2_pack(s, src, stride, bs, a4, nparents, crows, cw, rot);
+    default: return hipErrorInvalidValue;
+  }
+}
+
+extern "C" hipError_t gf2_launch_pass_up(hipStream_t s, int levels, int scheme, int acc, const word *prod, word *dst, int64_t stride,
+                                         int64_t bs, int64_t nparents, int64_t crows, int64_t cw) {
+  if (scheme) return gf2_launch_scheme_up(s, levels, acc, prod, dst, stride, bs, nparents, crows, cw);
+  switch (levels) {
+    case 4: return gf2_launch_winograd_up4(s, acc, prod, dst, stride, bs, nparents, crows, cw);
+    case 3: return gf2_launch_winograd_up3(s, acc, prod, dst, stride, bs, nparents, crows, cw);
+    case 2: return gf2_launch_winograd_up2(s, acc, prod, dst, stride, bs, nparents, crows, cw);
+    case 1: return gf2_launch_winograd_up(s, acc, prod, dst, stride, bs, nparents, crows, cw);
+    default: return hipErrorInvalidValue;
+  }
 }

@@ -18,16 +18,10 @@
 // on the columns of U that share that word it produces U^-1 U = identity, which is what :105 writes anyway.
 #include <hip/hip_runtime.h>
 #include <vector>
-#include "gf2_common.h"
+#include "gf2_internal.h"
 #include "../../include/m4ri_amd.h"
 
 namespace {
-
-#define HIPTRY(expr)                                  \
-  do {                                                \
-    hipError_t e_ = (hipError_t)(expr);               \
-    if (e_ != hipSuccess) return (int)e_;             \
-  } while (0)
 
 constexpr int EC_THREADS = 256;
 

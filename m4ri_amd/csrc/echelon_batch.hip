@@ -15,16 +15,10 @@
 #include <hip/hip_runtime.h>
 #include <mutex>
 #include <vector>
-#include "gf2_common.h"
+#include "gf2_internal.h"
 #include "../../include/m4ri_amd.h"
 
 namespace {
-
-#define HIPTRY(expr)                                  \
-  do {                                                \
-    hipError_t e_ = (hipError_t)(expr);               \
-    if (e_ != hipSuccess) return (int)e_;             \
-  } while (0)
 
 constexpr int EB_WAVE_THREADS   = 256;                 // path 0: four members per workgroup
 constexpr int EB_MAX_THREADS    = 1024;                // paths 1, 2

@@ -23,65 +23,8 @@
 #include <cstring>
 #include <mutex>
 #include <vector>
-#include "gf2_common.h"
+#include "gf2_internal.h"
 #include "../../include/m4ri_amd.h"
-
-extern "C" {
-hipError_t gf2_launch_m4rm_leaf(hipStream_t stream, LeafArgs a, int rg);
-hipError_t gf2_launch_m4rm_small(hipStream_t stream, LeafArgs a);
-int gf2_m4rm_small_ksplit(int64_t tiles, int64_t wl, int cus, int64_t c_words);
-hipError_t gf2_launch_a4_pack_rot(hipStream_t stream, LeafArgs a, word *a4_ws, int rot);
-int gf2_winograd_down2_pack_ok(const word *gparent, int64_t p_stride, int64_t p_bs, const word *a4, int64_t crows, int64_t cw);
-hipError_t gf2_launch_winograd_down3(hipStream_t s, int bside, const word *anc, int64_t p_stride, int64_t p_bs, word *gchild,
-                                     int64_t nparents, int64_t crows, int64_t cw);
-hipError_t gf2_launch_winograd_up3(hipStream_t s, int acc, const word *prod, word *anc, int64_t o_stride, int64_t o_bs,
-                                   int64_t nparents, int64_t crows, int64_t cw);
-int gf2_winograd_down3_pack_ok(const word *a4, int64_t crows, int64_t cw);
-hipError_t gf2_launch_winograd_down3_pack(hipStream_t s, const word *anc, int64_t p_stride, int64_t p_bs, word *a4,
-                                          int64_t nparents, int64_t crows, int64_t cw, int rot);
-hipError_t gf2_launch_winograd_down2_pack(hipStream_t s, const word *gparent, int64_t p_stride, int64_t p_bs, word *a4,
-                                          int64_t nparents, int64_t crows, int64_t cw, int rot);
-hipError_t gf2_launch_winograd_down4(hipStream_t s, int bside, const word *anc, int64_t p_stride, int64_t p_bs, word *gchild,
-                                     int64_t nparents, int64_t crows, int64_t cw);
-hipError_t gf2_launch_winograd_up4(hipStream_t s, int acc, const word *prod, word *anc, int64_t o_stride, int64_t o_bs,
-                                   int64_t nparents, int64_t crows, int64_t cw);
-hipError_t gf2_launch_winograd_down4_pack(hipStream_t s, const word *anc, int64_t p_stride, int64_t p_bs, word *a4,
-                                          int64_t nparents, int64_t crows, int64_t cw, int rot);
-hipError_t gf2_launch_m4rm8q(hipStream_t stream, LeafArgs a, word *a4_ws);
-// scheme_passes.hip: 2, 3 or 4 fused levels whose last two are one application of a rank-R scheme for the 4 x 4 x 4 block product
-// (R < 49: R, 7 R or R^2 leaves per ancestor instead of 49, 343, 2401)
-int gf2_scheme444_rank(void);
-int64_t gf2_scheme444_leaves(int levels);
-int gf2_scheme444_ok(int levels, int64_t a_rows, int64_t a_cw, int64_t b_rows, int64_t b_cw);
-hipError_t gf2_launch_scheme_down(hipStream_t s, int levels, int bside, const word *anc, int64_t p_stride, int64_t p_bs, word *child, int64_t nparents,
-                                  int64_t crows, int64_t cw);
-hipError_t gf2_launch_scheme_down_pack(hipStream_t s, int levels, const word *anc, int64_t p_stride, int64_t p_bs, word *a4, int64_t nparents,
-                                       int64_t crows, int64_t cw);
-hipError_t gf2_launch_scheme_up(hipStream_t s, int levels, int acc, const word *prod, word *anc, int64_t o_stride, int64_t o_bs, int64_t nparents,
-                                int64_t crows, int64_t cw);
-int gf2_m4rm8q_effective_ksplit(int64_t l, int ksplit);
-int64_t gf2_m4rm8_a4_words(int64_t m, int64_t l, int64_t batch);
-hipError_t gf2_launch_winograd_down(hipStream_t s, int bside, const word *parent, int64_t p_stride,
-                                    int64_t p_bs, word *child, int64_t nparents, int64_t crows, int64_t cw);
-hipError_t gf2_launch_winograd_up(hipStream_t s, int acc, const word *prod, word *parent, int64_t o_stride,
-                                  int64_t o_bs, int64_t nparents, int64_t crows, int64_t cw);
-hipError_t gf2_launch_winograd_down2(hipStream_t s, int bside, const word *gparent, int64_t p_stride, int64_t p_bs,
-                                     word *gchild, int64_t nparents, int64_t crows, int64_t cw);
-hipError_t gf2_launch_winograd_up2(hipStream_t s, int acc, const word *prod, word *gparent, int64_t o_stride,
-                                   int64_t o_bs, int64_t nparents, int64_t crows, int64_t cw);
-hipError_t gf2_launch_reduce_partials(hipStream_t s, int acc, word *C, int64_t cs, int64_t cbs, int64_t m, int64_t wn, int64_t tile_rows,
-                                      int64_t tw, int64_t tiles_m, int64_t tiles_n, int64_t tile_base, int64_t ntiles, int ks,
-                                      const word *Cpart);
-hipError_t gf2_launch_zero_tiles(hipStream_t s, word *C, int64_t cs, int64_t cbs, int64_t m, int64_t wn, int64_t tile_rows, int64_t tw,
-                                 int64_t tiles_m, int64_t tiles_n, int64_t tile_base, int64_t ntiles);
-hipError_t gf2_launch_rowwise(hipStream_t s, int op, word *C, int64_t cs, const word *A, int64_t as,
-                              const word *B, int64_t bs, int64_t rows, int64_t w);
-hipError_t gf2_launch_xor_masked(hipStream_t s, word *C, int64_t cs, const word *A, int64_t as, const word *B, int64_t bs,
-                                 int64_t rows, int64_t ncols);
-hipError_t gf2_launch_mask_tail(hipStream_t s, word *M, int64_t stride, int64_t rows, int64_t ncols);
-hipError_t gf2_launch_fill_splitmix(hipStream_t s, word *M, int64_t stride, int64_t rows, int64_t ncols, uint64_t seed);
-hipError_t gf2_launch_fill_splitmix_rows(hipStream_t s, word *M, int64_t stride, int64_t row0, int64_t rows, int64_t ncols, uint64_t seed);
-}
 
 namespace {
 
@@ -105,12 +48,6 @@ constexpr int DEFAULT_CUTOFF  = 4096;  // engine default: split while l/2 >= thi
 constexpr int DEFAULT_CUTOFF_M = 4096; // ... and m/2 >= this (one generation-4 tile row)
 constexpr int DEFAULT_CUTOFF_N = 4096; // ... and n/2 >= this (8 column tiles)
 constexpr int NUM_DEVICES_MAX = 16;
-
-#define HIPTRY(expr)                                                  \
-  do {                                                                \
-    hipError_t e_ = (expr);                                           \
-    if (e_ != hipSuccess) return (int)e_;                             \
-  } while (0)
 
 struct Engine {
   int device            = -1;
@@ -136,10 +73,6 @@ struct Engine {
   hipEvent_t last_done    = nullptr;  // on ANOTHER stream first waits for this event (recorded after every product)
   bool have_last          = false;
   std::mutex mu;                      // one host thread at a time plans on this device's workspace; other devices do not wait
-#ifdef M4RI_AMD_DEV_EXPERIMENTS
-  hipStream_t aux_stream = nullptr;   // second stream of the overlap experiment (developer builds; lives as long as the process)
-  hipEvent_t aux_ev[2]   = {nullptr, nullptr};
-#endif
 };
 
 std::mutex g_cfg_mu;  // the process-wide knobs (workspace budget, fuse depth)
@@ -266,6 +199,37 @@ bool packed_a_fits(const Engine *e, const LeafKind &kind, int64_t m, int64_t l, 
   return e->apk != nullptr && need <= e->apk_words && (uint64_t)need * 8 / (uint64_t)batch < (1ull << 32);
 }
 
+// C = 0 over the batch: one memset when the batch is one contiguous block, else a clearing pass per member
+int zero_c(hipStream_t st, word *C, int64_t cs, int64_t cbs, int64_t m, int64_t wn, int64_t batch) {
+  if (cs == wn && (batch == 1 || cbs == m * wn)) HIPTRY(hipMemsetAsync(C, 0, (size_t)batch * m * wn * 8, st));
+  else
+    for (int64_t b = 0; b < batch; ++b) HIPTRY(gf2_launch_rowwise(st, 2, C + b * cbs, cs, nullptr, 0, nullptr, 0, m, wn));
+  return 0;
+}
+
+// the leaf kernel(s) of one launch_leaf_one, bracketed by profiling events, then the call's leaf statistics
+template <typename Launch>
+int timed_leaf(Engine *e, hipStream_t st, int gen, int64_t m, int64_t l, int64_t n, int64_t batch, bool add, Launch &&launch) {
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (e->profiling) {  // the events bracket the leaf kernel alone
+    e0 = take_event(e); e1 = take_event(e);
+    if (e0 && e1) HIPTRY(hipEventRecord(e0, st));
+  }
+  if (int rc = launch()) return rc;
+  if (e->profiling && e0 && e1) {
+    HIPTRY(hipEventRecord(e1, st));
+    e->pending.push_back({e0, e1, e->call_seq});
+    e->pending_stream = st;
+  }
+  const int64_t wn = words_of(n);
+  e->stats.leaf_launches += 1;
+  e->stats.leaf_products += batch;
+  e->stats.leaf_m = (int32_t)m; e->stats.leaf_l = (int32_t)l; e->stats.leaf_n = (int32_t)n;
+  e->stats.leaf_gen = gen;
+  e->stats.leaf_bytes += 8.0 * (double)batch * ((double)m * words_of(l) + (double)l * wn + (double)m * wn * (add ? 2 : 1));
+  return 0;
+}
+
 // a_prepacked: the engine's packed-A scratch already holds A in the form the picked kernel reads
 // (written by the fused down pass); A itself is then not touched.
 int launch_leaf_one(Engine *e, hipStream_t st, word *C, int64_t cs, int64_t cbs, const word *A, int64_t as, int64_t abs_,
@@ -277,40 +241,21 @@ int launch_leaf_one(Engine *e, hipStream_t st, word *C, int64_t cs, int64_t cbs,
   if ((uint64_t)m * (uint64_t)as * 8 >= (1ull << 32) || (uint64_t)l * (uint64_t)bs * 8 >= (1ull << 32))
     return (int)hipErrorInvalidValue;
   const int64_t wn   = words_of(n);
+  LeafArgs a{};
+  a.A = A; a.B = B; a.C = C;
+  a.a_stride = as; a.b_stride = bs; a.c_stride = cs;
+  a.a_bs = abs_; a.b_bs = bbs; a.c_bs = cbs;
+  a.m = (int32_t)m; a.l = (int32_t)l; a.n = (int32_t)n;
+  a.batch = (int32_t)batch;
   if (!a_prepacked && ksplit_req <= 0 && l > 0 && small_leaf_wanted(m, l, n, batch)) {
     // a small product: ONE launch of the light kernel (m4rm_small.hip) instead of pack + split leaf + reduce
     const int64_t tiles = ((m + 255) / 256) * ((wn + 7) / 8) * batch;
     static const int ks_env = getenv("M4RI_AMD_SMALL_KS") ? atoi(getenv("M4RI_AMD_SMALL_KS")) : 0;  // developer: force the inner split of the small leaf
     const int ks        = ks_env > 0 ? (ks_env < words_of(l) ? ks_env : (int)words_of(l)) : gf2_m4rm_small_ksplit(tiles, words_of(l), e->cus, batch * m * wn);
-    if (ks > 1 && !add) {  // the splits meet by atomic XOR: they start from zero
-      if (cs == wn && (batch == 1 || cbs == m * wn)) HIPTRY(hipMemsetAsync(C, 0, (size_t)batch * m * wn * 8, st));
-      else
-        for (int64_t b = 0; b < batch; ++b) HIPTRY(gf2_launch_rowwise(st, 2, C + b * cbs, cs, nullptr, 0, nullptr, 0, m, wn));
-    }
-    LeafArgs a{};
-    a.A = A; a.B = B; a.C = C;
-    a.a_stride = as; a.b_stride = bs; a.c_stride = cs;
-    a.a_bs = abs_; a.b_bs = bbs; a.c_bs = cbs;
-    a.m = (int32_t)m; a.l = (int32_t)l; a.n = (int32_t)n;
-    a.batch = (int32_t)batch; a.ksplit = ks;
-    a.mode  = (add || ks > 1) ? 1 : 0;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (e->profiling) {
-      e0 = take_event(e); e1 = take_event(e);
-      if (e0 && e1) HIPTRY(hipEventRecord(e0, st));
-    }
-    HIPTRY(gf2_launch_m4rm_small(st, a));
-    if (e->profiling && e0 && e1) {
-      HIPTRY(hipEventRecord(e1, st));
-      e->pending.push_back({e0, e1, e->call_seq});
-      e->pending_stream = st;
-    }
-    e->stats.leaf_launches += 1;
-    e->stats.leaf_products += batch;
-    e->stats.leaf_m = (int32_t)m; e->stats.leaf_l = (int32_t)l; e->stats.leaf_n = (int32_t)n;
-    e->stats.leaf_gen = 5;
-    e->stats.leaf_bytes += 8.0 * (double)batch * ((double)m * words_of(l) + (double)l * wn + (double)m * wn * (add ? 2 : 1));
-    return 0;
+    if (ks > 1 && !add) HIPTRY(zero_c(st, C, cs, cbs, m, wn, batch));  // the splits meet by atomic XOR: they start from zero
+    a.ksplit = ks;
+    a.mode   = (add || ks > 1) ? 1 : 0;
+    return timed_leaf(e, st, 5, m, l, n, batch, add, [&]() -> int { HIPTRY(gf2_launch_m4rm_small(st, a)); return 0; });
   }
   LeafKind kind      = pick_leaf(m, l, n);
   const int64_t tw   = kind.gen == 4 ? 8 : LEAF_TW;  // tile width in words
@@ -377,22 +322,11 @@ int launch_leaf_one(Engine *e, hipStream_t st, word *C, int64_t cs, int64_t cbs,
   const bool slabs = kind.gen == 4 && e->part != nullptr && packed_a_fits(e, kind, m, l, batch) &&
                      (tail_tiles > 0 ? tail_tiles * tail_ksplit : (ksplit > 1 ? tiles * ksplit : PART_SLABS + 1)) <= PART_SLABS;
   if (l == 0 || (ksplit > 1 && !add && !slabs)) {  // empty inner dimension, or atomics need a zeroed C
-    if (!add) {
-      if (cs == wn && (batch == 1 || cbs == m * wn))  // one contiguous block
-        HIPTRY(hipMemsetAsync(C, 0, (size_t)batch * m * wn * 8, st));
-      else
-        for (int64_t b = 0; b < batch; ++b)
-          HIPTRY(gf2_launch_rowwise(st, 2, C + b * cbs, cs, nullptr, 0, nullptr, 0, m, wn));
-    }
+    if (!add) HIPTRY(zero_c(st, C, cs, cbs, m, wn, batch));
     if (l == 0) return 0;
   }
-  LeafArgs a{};
-  a.A = A; a.B = B; a.C = C;
-  a.a_stride = as; a.b_stride = bs; a.c_stride = cs;
-  a.a_bs = abs_; a.b_bs = bbs; a.c_bs = cbs;
-  a.m = (int32_t)m; a.l = (int32_t)l; a.n = (int32_t)n;
-  a.batch = (int32_t)batch; a.ksplit = ksplit;
-  a.mode  = (ksplit > 1 && slabs) ? 2 : (add || ksplit > 1) ? 1 : 0;
+  a.ksplit = ksplit;
+  a.mode   = (ksplit > 1 && slabs) ? 2 : (add || ksplit > 1) ? 1 : 0;
   a.Cpart = e->part;
   // generation 4 consumes A in a packed, chunk-major form (one streaming pass into the call's
   // scratch first); it needs that scratch and 32-bit offsets inside one packed operand
@@ -406,51 +340,27 @@ int launch_leaf_one(Engine *e, hipStream_t st, word *C, int64_t cs, int64_t cbs,
       e->stats.aux_bytes += 8.0 * (double)batch * (double)m * words_of(l) + 8.0 * (double)need;
     }
   }
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (e->profiling) {  // the events bracket the leaf kernel alone
-    e0 = take_event(e); e1 = take_event(e);
-    if (e0 && e1) HIPTRY(hipEventRecord(e0, st));
-  }
-#ifdef M4RI_AMD_DEV_EXPERIMENTS  // developer builds only (profiles/r05_overlap_power/): the batch in this many launches
-  static const int exp_groups = getenv("M4RI_AMD_LEAF_GROUPS") ? atoi(getenv("M4RI_AMD_LEAF_GROUPS")) : 0;
-#else
-  constexpr int exp_groups = 0;
-#endif
-  if (kind.gen == 4 && exp_groups > 1 && batch % exp_groups == 0 && ksplit == 1) {
-    for (int g = 0; g < exp_groups; ++g) {
-      LeafArgs part = a;
-      part.tile_base = (tiles / exp_groups) * g; part.tile_count = tiles / exp_groups;
-      HIPTRY(gf2_launch_m4rm8q(st, part, e->apk));
+  return timed_leaf(e, st, kind.gen, m, l, n, batch, add, [&]() -> int {
+    if (kind.gen == 4 && tail_tiles > 0) {
+      LeafArgs head = a, tail = a;
+      head.tile_base = 0; head.tile_count = tiles - tail_tiles;
+      tail.tile_base = tiles - tail_tiles; tail.tile_count = tail_tiles;
+      tail.ksplit = tail_ksplit; tail.mode = slabs ? 2 : 1;
+      const int64_t tm = (m + kind.rows - 1) / kind.rows, tn = (wn + tw - 1) / tw;
+      if (!add && !slabs)  // the split tiles are combined by atomic XOR: they start from zero
+        HIPTRY(gf2_launch_zero_tiles(st, C, cs, cbs, m, wn, kind.rows, tw, tm, tn, tail.tile_base, tail_tiles));
+      HIPTRY(gf2_launch_m4rm8q(st, head, e->apk));
+      HIPTRY(gf2_launch_m4rm8q(st, tail, e->apk));
+      if (slabs) HIPTRY(gf2_launch_reduce_partials(st, add ? 1 : 0, C, cs, cbs, m, wn, kind.rows, tw, tm, tn, tail.tile_base, tail_tiles, tail_ksplit, e->part));
+    } else if (kind.gen == 4) {
+      HIPTRY(gf2_launch_m4rm8q(st, a, e->apk));
+      if (a.mode == 2)
+        HIPTRY(gf2_launch_reduce_partials(st, add ? 1 : 0, C, cs, cbs, m, wn, kind.rows, tw, (m + kind.rows - 1) / kind.rows, (wn + tw - 1) / tw,
+                                          0, tiles, ksplit, e->part));
     }
-  } else if (kind.gen == 4 && tail_tiles > 0) {
-    LeafArgs head = a, tail = a;
-    head.tile_base = 0; head.tile_count = tiles - tail_tiles;
-    tail.tile_base = tiles - tail_tiles; tail.tile_count = tail_tiles;
-    tail.ksplit = tail_ksplit; tail.mode = slabs ? 2 : 1;
-    const int64_t tm = (m + kind.rows - 1) / kind.rows, tn = (wn + tw - 1) / tw;
-    if (!add && !slabs)  // the split tiles are combined by atomic XOR: they start from zero
-      HIPTRY(gf2_launch_zero_tiles(st, C, cs, cbs, m, wn, kind.rows, tw, tm, tn, tail.tile_base, tail_tiles));
-    HIPTRY(gf2_launch_m4rm8q(st, head, e->apk));
-    HIPTRY(gf2_launch_m4rm8q(st, tail, e->apk));
-    if (slabs) HIPTRY(gf2_launch_reduce_partials(st, add ? 1 : 0, C, cs, cbs, m, wn, kind.rows, tw, tm, tn, tail.tile_base, tail_tiles, tail_ksplit, e->part));
-  } else if (kind.gen == 4) {
-    HIPTRY(gf2_launch_m4rm8q(st, a, e->apk));
-    if (a.mode == 2)
-      HIPTRY(gf2_launch_reduce_partials(st, add ? 1 : 0, C, cs, cbs, m, wn, kind.rows, tw, (m + kind.rows - 1) / kind.rows, (wn + tw - 1) / tw,
-                                        0, tiles, ksplit, e->part));
-  }
-  else HIPTRY(gf2_launch_m4rm_leaf(st, a, kind.rg));
-  if (e->profiling && e0 && e1) {
-    HIPTRY(hipEventRecord(e1, st));
-    e->pending.push_back({e0, e1, e->call_seq});
-    e->pending_stream = st;
-  }
-  e->stats.leaf_launches += 1;
-  e->stats.leaf_products += batch;
-  e->stats.leaf_m = (int32_t)m; e->stats.leaf_l = (int32_t)l; e->stats.leaf_n = (int32_t)n;
-  e->stats.leaf_gen = kind.gen;
-  e->stats.leaf_bytes += 8.0 * (double)batch * ((double)m * words_of(l) + (double)l * wn + (double)m * wn * (add ? 2 : 1));
-  return 0;
+    else HIPTRY(gf2_launch_m4rm_leaf(st, a, kind.rg));
+    return 0;
+  });
 }
 
 // The kernels address one operand of one product through a raw buffer descriptor: 32-bit byte
@@ -498,6 +408,19 @@ int reserve_apk(Engine *e, size_t words) {
 // ---- level planning ----------------------------------------------------------------------------
 int64_t ipow7(int d) { int64_t r = 1; while (d-- > 0) r *= 7; return r; }
 bool closer(int64_t a, int64_t cutoff) { return 3 * a < 4 * cutoff; }  // strassen.c:39
+int fuse_of(int L) { return L < g_max_fuse ? L : g_max_fuse; }  // levels covered by the fused bottom pass each way
+// the levels of an L-level schedule whose operands and products are materialised: those above the fused bottom pass, and the leaves
+bool materialised(int d, int L) { return d <= L - fuse_of(L) || d == L; }
+// every level halves l and n on word boundaries and m on rows: at most L levels that leave a non-empty even block
+int clamp_levels(int64_t m, int64_t l, int64_t n, int L) {
+  while (L > 0 && ((m >> L) == 0 || (l / (64ll << L)) == 0 || (n / (64ll << L)) == 0)) --L;
+  return L;
+}
+// words a pass of `step` fused levels moves per word of one leaf: the 4^step blocks of the parent read (acc: read and written) and
+// every leaf operand written -- or, up, every product read (stats.aux_bytes)
+double pass_words(int step, bool scheme, bool acc) {
+  return (double)(scheme ? gf2_scheme444_leaves(step) : ipow7(step)) + (acc ? 2.0 : 1.0) * (double)(1 << (2 * step));
+}
 
 // ---- the engine's own depth: a time model -------------------------------------------------------------------------------
 // Rounds 1 - 4a split "while every half keeps 4096 rows, inner bits and columns".  That rule is right for cubes and wrong by up to
@@ -535,15 +458,14 @@ double depth_model_seconds(int64_t m, int64_t l, int64_t n, int L, double batch 
   double p7 = batch;
   for (int d = 0; d < L; ++d) p7 *= 7;
   // the fused bottom levels run through the rank-R 4 x 4 x 4 scheme where the leaves allow it: R, 7 R or R^2 products instead of 7^2, 7^3, 7^4
-  const int mfuse = L < g_max_fuse ? L : g_max_fuse;
-  const bool scheme = scheme_applies(mfuse, mm, ll, nn);
-  const double srat = scheme ? (double)gf2_scheme444_leaves(mfuse) / (double)ipow7(mfuse) : 1.0;
+  const int fuse = fuse_of(L);
+  const bool scheme = scheme_applies(fuse, mm, ll, nn);
+  const double srat = scheme ? (double)gf2_scheme444_leaves(fuse) / (double)ipow7(fuse) : 1.0;
   p7 *= srat;
   double t = leaf(mm, ll, nn, p7);
   // passes over the even block
   const int64_t me = mm << L, le = ll << L, ne = nn << L;
   const double sa = 8.0 * (double)me * (double)words_of(le), sb = 8.0 * (double)le * (double)words_of(ne), sc = 8.0 * (double)me * (double)words_of(ne);
-  const int fuse = L < g_max_fuse ? L : (g_max_fuse > 0 ? g_max_fuse : 1);
   auto r = [](int d) { double x = 1; while (d-- > 0) x *= 1.75; return x; };
   double factor = 0;
   for (int d = 0; d < L - fuse; ++d) factor += r(d) + r(d + 1);
@@ -626,9 +548,7 @@ int plan_levels(int64_t m, int64_t l, int64_t n, int cutoff) {
     const int want = atoi(f);
     if (want >= 0 && want <= MAX_LEVELS) L = want;
   }
-  // every level halves l and n on word boundaries and m on rows: need a non-empty even block
-  while (L > 0 && ((m >> L) == 0 || (l / (64ll << L)) == 0 || (n / (64ll << L)) == 0)) --L;
-  return L;
+  return clamp_levels(m, l, n, L);
 }
 
 
@@ -642,8 +562,7 @@ int bfs_product(Engine *e, hipStream_t st, DMat C, DMat A, DMat B, bool add, int
   // The deepest levels are done by ONE fused pass each way: up to four of them (g_max_fuse), whose
   // intermediate levels are never materialised -- that saves their buffers and a write + a read of
   // the 7/4-times-larger operands per skipped level.  Levels above go one at a time.
-  const int fuse = L < g_max_fuse ? L : g_max_fuse;            // levels covered by the bottom pass
-  auto materialised = [&](int d) { return d <= L - fuse || d == L; };
+  const int fuse = fuse_of(L);  // levels covered by the bottom pass
   // With a fused last pass and a leaf that reads packed A, the pass writes the packed form itself:
   // the row-major A operands of the leaves are never materialised and the pack pass disappears.
   const LeafKind leaf_kind = pick_leaf(m >> L, (l / (64ll << L)) * 64, (n / (64ll << L)) * 64);  // (the dimensions launch_leaf_one will see)
@@ -655,23 +574,26 @@ int bfs_product(Engine *e, hipStream_t st, DMat C, DMat A, DMat B, bool add, int
   const int64_t leaves1 = scheme ? ipow7(L - fuse) * gf2_scheme444_leaves(fuse) : ipow7(L);  // leaf products of ONE product
   const int64_t leaves  = batch * leaves1;                                                      // products of the leaf launch
   bool prepack = scheme;
-  if (!scheme && fuse >= 2 && leaf_kind.gen == 4) {
+  if (!scheme && leaf_kind.gen == 4) {
     static const word aligned16[2] __attribute__((aligned(16))) = {0, 0};
     const int d0      = L - fuse;
     const word *pa    = d0 == 0 ? A.p : aligned16;  // deeper levels live in the 256-byte aligned workspace
     const int64_t pas = d0 == 0 ? A.stride : (l >> d0) / 64;
     const uint64_t a4_bytes = (uint64_t)gf2_m4rm8_a4_words(m >> L, l >> L, 1) * 8;  // one packed operand: 32-bit offsets
     prepack = a4_bytes < (1ull << 32) &&
-              (fuse >= 3 ? gf2_winograd_down3_pack_ok(aligned16, m >> L, (l >> L) / 64) != 0
-                         : gf2_winograd_down2_pack_ok(pa, pas, d0 == 0 ? a_bs : (m >> d0) * pas, aligned16, m >> L, (l >> L) / 64) != 0);
+              gf2_pass_down_pack_ok(fuse, pa, pas, d0 == 0 ? a_bs : (m >> d0) * pas, aligned16, m >> L, (l >> L) / 64) != 0;
   }
-  // workspace plan
+  // workspace plan: the A and B operands and the products of every materialised level, in words (none for the level that is not,
+  // nor for the leaves' A operands when the pass writes them packed) -- summed for the reservation, then carved
+  struct LevelWords { size_t a, b, p; };
+  std::vector<LevelWords> lw(L + 1, LevelWords{0, 0, 0});
   size_t need = 0;
   auto pad = [](size_t w) { return (w + 31) & ~(size_t)31; };
   for (int d = 1; d <= L; ++d) {
-    if (!materialised(d)) continue;
+    if (!materialised(d, L)) continue;
     const int64_t md = m >> d, wl = (l >> d) / 64, wnn = (n >> d) / 64, cnt = d == L ? leaves : batch * ipow7(d);
-    need += (prepack && d == L ? 0 : pad((size_t)cnt * md * wl)) + pad((size_t)cnt * (l >> d) * wnn) + pad((size_t)cnt * md * wnn);
+    lw[d] = {prepack && d == L ? 0 : (size_t)cnt * md * wl, (size_t)cnt * (l >> d) * wnn, (size_t)cnt * md * wnn};
+    need += pad(lw[d].a) + pad(lw[d].b) + pad(lw[d].p);
   }
   // C += A*B through a three-level up pass: the pass writes a temporary and one XOR pass folds it into
   // C (the accumulating three-level kernel needs > 256 registers per lane and runs at a quarter of the rate)
@@ -687,20 +609,17 @@ int bfs_product(Engine *e, hipStream_t st, DMat C, DMat A, DMat B, bool add, int
   e->apk = ws_take(e, a7_extra);
   e->apk_words = a7_extra;
   e->part = ws_take(e, (size_t)PART_SLABS * LEAF_PART_WORDS);
-  std::vector<word *> Al(L + 1, nullptr), Bl(L + 1, nullptr), Pl(L + 1, nullptr);
   if (prepack && !packed_a_fits(e, leaf_kind, m >> L, l >> L, leaves)) return (int)hipErrorInvalidValue;  // cannot happen: a7_extra covers it
-  for (int d = 1; d <= L; ++d) {
-    if (!materialised(d)) continue;
-    const int64_t md = m >> d, wl = (l >> d) / 64, wnn = (n >> d) / 64, cnt = d == L ? leaves : batch * ipow7(d);
-    if (!(prepack && d == L)) Al[d] = ws_take(e, (size_t)cnt * md * wl);
-    Bl[d] = ws_take(e, (size_t)cnt * (l >> d) * wnn);
-    Pl[d] = ws_take(e, (size_t)cnt * md * wnn);
-  }
+  std::vector<word *> Al(L + 1, nullptr), Bl(L + 1, nullptr), Pl(L + 1, nullptr);
+  auto take = [&](size_t w) { return w ? ws_take(e, w) : nullptr; };
+  for (int d = 1; d <= L; ++d) { Al[d] = take(lw[d].a); Bl[d] = take(lw[d].b); Pl[d] = take(lw[d].p); }
   word *acc_tmp = acc_via_tmp ? ws_take(e, (size_t)m * (n / 64)) : nullptr;
   e->stats.workspace_bytes = (double)e->ws_cap * 8.0;
-  // down passes: level d -> d+1, and d -> L for the fused pass at the bottom
+  // down passes: level d -> d+1, and d -> L for the fused pass at the bottom (through the scheme when it applies; with A written
+  // packed when the leaf takes that)
   for (int d = 0; d < L;) {
     const int step    = d == L - fuse ? fuse : 1;
+    const bool sch    = scheme && step == fuse;
     const int64_t cnt = batch * ipow7(d);
     const int64_t cm = m >> (d + step), cl = l >> (d + step), cn = n >> (d + step);
     const word *pa = d == 0 ? A.p : Al[d];
@@ -708,51 +627,12 @@ int bfs_product(Engine *e, hipStream_t st, DMat C, DMat A, DMat B, bool add, int
     const word *pb = d == 0 ? B.p : Bl[d];
     const int64_t pbs = d == 0 ? B.stride : (n >> d) / 64, pbbs = d == 0 ? b_bs : (l >> d) * pbs;
     const int rot = leaf_kind.gen == 4 ? 1 : 0;  // the leaf's pre-rotated index bytes (pack mode)
-    if (scheme && step == fuse && step >= 2) {  // the fused bottom levels through the 4 x 4 x 4 scheme, one pass each way (scheme_passes.hip)
-      const double rr = (double)gf2_scheme444_leaves(step), blocks = (double)(1 << (2 * step));
-      HIPTRY(gf2_launch_scheme_down_pack(st, step, pa, pas, pabs, e->apk, cnt, cm, cl / 64));
-      HIPTRY(gf2_launch_scheme_down(st, step, 1, pb, pbs, pbbs, Bl[d + step], cnt, cl, cn / 64));
-      e->stats.aux_bytes += 8.0 * cnt * (blocks + rr) * ((double)cm * (cl / 64) + (double)cl * (cn / 64));
-    } else if (step == 4) {  // four levels in one pass each way: the top one formed on the fly (aux_kernels.hip)
-      if (prepack) HIPTRY(gf2_launch_winograd_down4_pack(st, pa, pas, pabs, e->apk, cnt, cm, cl / 64, rot));
-      else HIPTRY(gf2_launch_winograd_down4(st, 0, pa, pas, pabs, Al[d + 4], cnt, cm, cl / 64));
-      HIPTRY(gf2_launch_winograd_down4(st, 1, pb, pbs, pbbs, Bl[d + 4], cnt, cl, cn / 64));
-      e->stats.aux_bytes += 8.0 * cnt * 2657.0 * ((double)cm * (cl / 64) + (double)cl * (cn / 64));  // 256 in + 2401 out
-    } else if (step == 3) {
-      if (prepack) HIPTRY(gf2_launch_winograd_down3_pack(st, pa, pas, pabs, e->apk, cnt, cm, cl / 64, rot));
-      else HIPTRY(gf2_launch_winograd_down3(st, 0, pa, pas, pabs, Al[d + 3], cnt, cm, cl / 64));
-      HIPTRY(gf2_launch_winograd_down3(st, 1, pb, pbs, pbbs, Bl[d + 3], cnt, cl, cn / 64));
-      e->stats.aux_bytes += 8.0 * cnt * 407.0 * ((double)cm * (cl / 64) + (double)cl * (cn / 64));  // 64 in + 343 out
-    } else if (step == 2) {
-      if (prepack) HIPTRY(gf2_launch_winograd_down2_pack(st, pa, pas, pabs, e->apk, cnt, cm, cl / 64, rot));
-      else HIPTRY(gf2_launch_winograd_down2(st, 0, pa, pas, pabs, Al[d + 2], cnt, cm, cl / 64));
-      HIPTRY(gf2_launch_winograd_down2(st, 1, pb, pbs, pbbs, Bl[d + 2], cnt, cl, cn / 64));
-      e->stats.aux_bytes += 8.0 * cnt * 65.0 * ((double)cm * (cl / 64) + (double)cl * (cn / 64));  // 16 in + 49 out
-    } else {
-      HIPTRY(gf2_launch_winograd_down(st, 0, pa, pas, pabs, Al[d + 1], cnt, cm, cl / 64));
-      HIPTRY(gf2_launch_winograd_down(st, 1, pb, pbs, pbbs, Bl[d + 1], cnt, cl, cn / 64));
-      e->stats.aux_bytes += 8.0 * cnt * 11.0 * ((double)cm * (cl / 64) + (double)cl * (cn / 64));  // 4 in + 7 out
-    }
+    if (prepack && step == fuse) HIPTRY(gf2_launch_pass_down_pack(st, step, sch, pa, pas, pabs, e->apk, cnt, cm, cl / 64, rot));
+    else HIPTRY(gf2_launch_pass_down(st, step, sch, 0, pa, pas, pabs, Al[d + step], cnt, cm, cl / 64));
+    HIPTRY(gf2_launch_pass_down(st, step, sch, 1, pb, pbs, pbbs, Bl[d + step], cnt, cl, cn / 64));
+    e->stats.aux_bytes += 8.0 * cnt * pass_words(step, sch, false) * ((double)cm * (cl / 64) + (double)cl * (cn / 64));
     d += step;
   }
-#ifdef M4RI_AMD_DEV_EXPERIMENTS
-  // developer experiment, NOT in the product build (profiles/r05_overlap_power/; build with -DM4RI_AMD_DEV_EXPERIMENTS): the three
-  // four-level passes once more on a second stream UNDER the leaf launch (same sources, same destinations, same values; the up pass
-  // reads half-written products and its output is overwritten by the real one -- unsafe by construction, correct only because the
-  // real up pass waits for it) -- what the leaf loses to HBM-bound work beside it bounds what a pipelined schedule could win
-  static const int exp_overlap = getenv("M4RI_AMD_OVERLAP_EXP") ? atoi(getenv("M4RI_AMD_OVERLAP_EXP")) : 0;
-  const bool overlap_now = exp_overlap && L == 4 && fuse == 4 && prepack && !scheme;
-  if (overlap_now) {
-    if (!e->aux_stream) { HIPTRY(hipStreamCreateWithFlags(&e->aux_stream, hipStreamNonBlocking)); HIPTRY(hipEventCreateWithFlags(&e->aux_ev[0], hipEventDisableTiming)); HIPTRY(hipEventCreateWithFlags(&e->aux_ev[1], hipEventDisableTiming)); }
-    HIPTRY(hipEventRecord(e->aux_ev[0], st));
-    HIPTRY(hipStreamWaitEvent(e->aux_stream, e->aux_ev[0], 0));
-    const int64_t cm = m >> 4, cl = l >> 4, cn = n >> 4;
-    if (exp_overlap & 1) HIPTRY(gf2_launch_winograd_down4_pack(e->aux_stream, A.p, A.stride, 0, e->apk, 1, cm, cl / 64, 1));
-    if (exp_overlap & 2) HIPTRY(gf2_launch_winograd_down4(e->aux_stream, 1, B.p, B.stride, 0, Bl[4], 1, cl, cn / 64));
-    if (exp_overlap & 4) HIPTRY(gf2_launch_winograd_up4(e->aux_stream, 0, Pl[4], C.p, C.stride, 0, 1, cm, cn / 64));
-    HIPTRY(hipEventRecord(e->aux_ev[1], e->aux_stream));
-  }
-#endif
   // all 7^L leaf products in one launch
   {
     const int64_t lm = m >> L, ll = l >> L, ln = n >> L, cnt = leaves;
@@ -760,12 +640,10 @@ int bfs_product(Engine *e, hipStream_t st, DMat C, DMat A, DMat B, bool add, int
                              ll * (ln / 64), lm, ll, ln, cnt, false, 0, prepack))
       return rc;
   }
-#ifdef M4RI_AMD_DEV_EXPERIMENTS
-  if (overlap_now) HIPTRY(hipStreamWaitEvent(st, e->aux_ev[1], 0));
-#endif
   // up passes: the fused pass at the bottom first (L -> L - fuse), then level d+1 -> d
   for (int d = L; d > 0;) {
     const int step    = d == L ? fuse : 1;
+    const bool sch    = scheme && step == fuse;
     const int dst     = d - step;
     const int64_t cnt = batch * ipow7(dst);
     const int64_t cm = m >> d, cn = n >> d;
@@ -773,26 +651,15 @@ int bfs_product(Engine *e, hipStream_t st, DMat C, DMat A, DMat B, bool add, int
     const int64_t ostr = dst == 0 ? C.stride : (n >> dst) / 64;
     const int64_t obs  = dst == 0 ? c_bs : (m >> dst) * ostr;
     const int acc      = (dst == 0 && add) ? 1 : 0;
-    if (scheme && step == fuse && step >= 2) {
-      const double rr = (double)gf2_scheme444_leaves(step), blocks = (double)(1 << (2 * step));
-      HIPTRY(gf2_launch_scheme_up(st, step, acc, Pl[d], out, ostr, obs, cnt, cm, cn / 64));
-      e->stats.aux_bytes += 8.0 * cnt * (double)cm * (cn / 64) * (rr + (acc ? 2.0 : 1.0) * blocks);
-    } else if (step == 4) {
-      HIPTRY(gf2_launch_winograd_up4(st, acc, Pl[d], out, ostr, obs, cnt, cm, cn / 64));
-      e->stats.aux_bytes += 8.0 * cnt * (double)cm * (cn / 64) * (2401.0 + 512.0 + (acc ? 0.0 : 256.0));  // products in, every word read + written once, the clear
-    } else if (step == 3 && acc && acc_tmp) {
-      HIPTRY(gf2_launch_winograd_up3(st, 0, Pl[d], acc_tmp, n / 64, 0, cnt, cm, cn / 64));
+    if (step == 3 && acc && acc_tmp) {
+      HIPTRY(gf2_launch_pass_up(st, 3, 0, 0, Pl[d], acc_tmp, n / 64, 0, cnt, cm, cn / 64));
       HIPTRY(gf2_launch_rowwise(st, 0, C.p, C.stride, C.p, C.stride, acc_tmp, n / 64, m, n / 64));
-      e->stats.aux_bytes += 8.0 * cnt * (double)cm * (cn / 64) * 407.0 + 8.0 * 3.0 * (double)m * (n / 64);
-    } else if (step == 3) {
-      HIPTRY(gf2_launch_winograd_up3(st, acc, Pl[d], out, ostr, obs, cnt, cm, cn / 64));
-      e->stats.aux_bytes += 8.0 * cnt * (double)cm * (cn / 64) * (acc ? 471.0 : 407.0);
-    } else if (step == 2) {
-      HIPTRY(gf2_launch_winograd_up2(st, acc, Pl[d], out, ostr, obs, cnt, cm, cn / 64));
-      e->stats.aux_bytes += 8.0 * cnt * (double)cm * (cn / 64) * (acc ? 81.0 : 65.0);
+      e->stats.aux_bytes += 8.0 * cnt * (double)cm * (cn / 64) * pass_words(3, false, false) + 8.0 * 3.0 * (double)m * (n / 64);
     } else {
-      HIPTRY(gf2_launch_winograd_up(st, acc, Pl[d], out, ostr, obs, cnt, cm, cn / 64));
-      e->stats.aux_bytes += 8.0 * cnt * (double)cm * (cn / 64) * (acc ? 15.0 : 11.0);
+      HIPTRY(gf2_launch_pass_up(st, step, sch, acc, Pl[d], out, ostr, obs, cnt, cm, cn / 64));
+      const double words = step == 4 && !sch ? 2401.0 + 512.0 + (acc ? 0.0 : 256.0)  // products in, every word read + written once, the clear
+                                             : pass_words(step, sch, acc);
+      e->stats.aux_bytes += 8.0 * cnt * (double)cm * (cn / 64) * words;
     }
     d = dst;
   }
@@ -802,10 +669,9 @@ int bfs_product(Engine *e, hipStream_t st, DMat C, DMat A, DMat B, bool add, int
 // upper bound of the words bfs_product reserves for an L-level schedule (level-L operands and products,
 // packed A, the materialised upper levels, slabs, the accumulate temporary)
 size_t bfs_words_bound(int64_t m, int64_t l, int64_t n, int L) {
-  const int fuse = L < g_max_fuse ? L : g_max_fuse;
   size_t w = 0;
   for (int d = 1; d <= L; ++d) {
-    if (!(d <= L - fuse || d == L)) continue;
+    if (!materialised(d, L)) continue;
     const size_t md = (size_t)(m >> d), wl = (size_t)((l >> d) / 64), ld = (size_t)(l >> d), wn = (size_t)((n >> d) / 64);
     w += (size_t)ipow7(d) * (md * wl + ld * wn + md * wn) + 96;
   }
@@ -932,8 +798,7 @@ int engine_mul(Engine *e, hipStream_t st, DMat C, DMat A, DMat B, bool add, int 
   std::vector<RowBlock> blocks;
   if (cutoff == 0 && !getenv("M4RI_AMD_LEVELS")) plan_row_blocks(m, l, n, blocks);
   if (blocks.empty()) blocks.push_back(RowBlock{m, plan_levels(m, l, n, cutoff)});
-  for (RowBlock &b : blocks)  // every level halves l and n on word boundaries and m on rows: need a non-empty even block
-    while (b.levels > 0 && ((b.rows >> b.levels) == 0 || (l / (64ll << b.levels)) == 0 || (n / (64ll << b.levels)) == 0)) --b.levels;
+  for (RowBlock &b : blocks) b.levels = clamp_levels(b.rows, l, n, b.levels);
   const int L = blocks[0].levels;
   e->stats.levels = L;
   // depth-first levels (workspace larger than the device has left) take their temporaries from a grow-only stack
@@ -982,10 +847,10 @@ int engine_mul_batch(Engine *e, hipStream_t st, DMat C, int64_t c_bs, DMat A, in
   } else {
     L = plan_levels(m, l, n, cutoff);
   }
-  while (L > 0 && ((m >> L) == 0 || (l / (64ll << L)) == 0 || (n / (64ll << L)) == 0)) --L;
+  L = clamp_levels(m, l, n, L);
   if (L > 0 && (m % (1ll << L) != 0 || l % (64ll << L) != 0 || n % (64ll << L) != 0)) return one_by_one();  // strips
   if (L > 0 && (double)bfs_words_bound(m, l, n, L) * 8.0 * (double)batch > workspace_budget(e)) return one_by_one();
-  const int fuse = L < g_max_fuse ? L : g_max_fuse;
+  const int fuse = fuse_of(L);
   if (add && fuse == 3 && L == 3 && !scheme_applies(fuse, m >> L, l >> L, n >> L)) return one_by_one();  // (the accumulate temporary is one product's)
   e->stats.levels = L;
   e->df_used = 0;
@@ -1194,9 +1059,6 @@ int m4ri_amd_get_stats(m4ri_amd_stats *out) {
   *out = e->stats;
   return 0;
 }
-
-void gf2_release_staging(void);  // mzd_api.hip: the host entry points' staging arena
-void gf2_release_multi(void);    // multi.hip: the per-rank arenas of the multi-device path
 
 void m4ri_amd_release_workspace(void) {
   gf2_release_staging();

@@ -1,0 +1,82 @@
+// gf2_internal.h -- the functions the library's translation units call across files, declared once.
+//
+// Every file that defines one of them includes this header, so the compiler checks each definition against the one
+// declaration here.  C linkage: tools/leaf_check.cpp links the leaf sources directly.  None of these names leaves the
+// shared library (build.py's export map lists only include/m4ri_amd.h).
+#pragma once
+#include <hip/hip_runtime.h>
+#include "gf2_common.h"
+
+// return the HIP error of `expr` (a hipError_t or an int status) from the enclosing int-returning function
+#define HIPTRY(expr)                                  \
+  do {                                                \
+    hipError_t e_ = (hipError_t)(expr);               \
+    if (e_ != hipSuccess) return (int)e_;             \
+  } while (0)
+
+extern "C" {
+
+// ---- the M4RM leaves --------------------------------------------------------------------------------------------------------
+// m4rm_leaf.hip: generation 1 (plain A, rg row groups; the variant takes the developer's unroll / pipeline bits)
+hipError_t gf2_launch_m4rm_leaf(hipStream_t stream, LeafArgs a, int rg);
+hipError_t gf2_launch_m4rm_leaf_variant(hipStream_t stream, LeafArgs a, int rg, int ug, int pipe);
+// m4rm_small.hip: the one-launch kernel of small products ("generation 5") and its inner split
+hipError_t gf2_launch_m4rm_small(hipStream_t stream, LeafArgs a);
+int gf2_m4rm_small_ksplit(int64_t tiles, int64_t wl, int cus, int64_t c_words);
+// a4_pack.hip: the packed, chunk-major A of generation 4 (words of scratch it needs; the pack pass)
+int64_t gf2_m4rm8_a4_words(int64_t m, int64_t l, int64_t batch);
+hipError_t gf2_launch_a4_pack_rot(hipStream_t stream, LeafArgs a, word *a4_ws, int rot);
+// m4rm8q_leaf.hip: generation 4 (the split the kernel will really use; the launch)
+int gf2_m4rm8q_effective_ksplit(int64_t l, int ksplit);
+hipError_t gf2_launch_m4rm8q(hipStream_t stream, LeafArgs a, word *a4_ws);
+
+// ---- the fused passes of `levels` Strassen-Winograd levels (aux_kernels.hip) ------------------------------------------------
+// levels 1 ... 4 through the Winograd passes, or (scheme != 0, levels 2 ... 4) through the rank-R scheme of the 4 x 4 x 4 block
+// product (scheme_passes.hip).  Down: nparents parents of 2^levels crows rows x 2^levels cw words (row stride `stride`, `bs` words
+// apart) -> their descendants, crows x cw words each, back to back; bside selects the B side's operand sums.  Down_pack: the A side
+// written straight into generation 4's packed form at a4 (rot: the Winograd passes' index-byte rotation).  Up: the products back
+// into the parents (acc != 0: added onto them).
+hipError_t gf2_launch_pass_down(hipStream_t s, int levels, int scheme, int bside, const word *src, int64_t stride, int64_t bs, word *dst,
+                                int64_t nparents, int64_t crows, int64_t cw);
+hipError_t gf2_launch_pass_down_pack(hipStream_t s, int levels, int scheme, const word *src, int64_t stride, int64_t bs, word *a4,
+                                     int64_t nparents, int64_t crows, int64_t cw, int rot);
+hipError_t gf2_launch_pass_up(hipStream_t s, int levels, int scheme, int acc, const word *prod, word *dst, int64_t stride, int64_t bs,
+                              int64_t nparents, int64_t crows, int64_t cw);
+// can the Winograd down_pack pass of `levels` levels take this parent and packed output (descendants of crows x cw words)?
+int gf2_pass_down_pack_ok(int levels, const word *src, int64_t stride, int64_t bs, const word *a4, int64_t crows, int64_t cw);
+
+// scheme_passes.hip: the scheme's rank, leaves per ancestor of a `levels`-level pass, whether its passes take these leaf shapes
+int gf2_scheme444_rank(void);
+int64_t gf2_scheme444_leaves(int levels);
+int gf2_scheme444_ok(int levels, int64_t a_rows, int64_t a_cw, int64_t b_rows, int64_t b_cw);
+hipError_t gf2_launch_scheme_down(hipStream_t s, int levels, int bside, const word *anc, int64_t p_stride, int64_t p_bs, word *child,
+                                  int64_t nparents, int64_t crows, int64_t cw);
+hipError_t gf2_launch_scheme_down_pack(hipStream_t s, int levels, const word *anc, int64_t p_stride, int64_t p_bs, word *a4,
+                                       int64_t nparents, int64_t crows, int64_t cw);
+hipError_t gf2_launch_scheme_up(hipStream_t s, int levels, int acc, const word *prod, word *anc, int64_t o_stride, int64_t o_bs,
+                                int64_t nparents, int64_t crows, int64_t cw);
+
+// ---- streaming helpers (aux_kernels.hip) ------------------------------------------------------------------------------------
+// op 0: C = A ^ B, 1: C = A, 2: C = 0 (whole words of `w` words per row)
+hipError_t gf2_launch_rowwise(hipStream_t s, int op, word *C, int64_t cs, const word *A, int64_t as, const word *B, int64_t bs,
+                              int64_t rows, int64_t w);
+hipError_t gf2_launch_xor_masked(hipStream_t s, word *C, int64_t cs, const word *A, int64_t as, const word *B, int64_t bs,
+                                 int64_t rows, int64_t ncols);
+hipError_t gf2_launch_copy_masked(hipStream_t s, word *C, int64_t cs, const word *A, int64_t as, int64_t rows, int64_t ncols);
+hipError_t gf2_launch_reduce_partials(hipStream_t s, int acc, word *C, int64_t cs, int64_t cbs, int64_t m, int64_t wn, int64_t tile_rows,
+                                      int64_t tw, int64_t tiles_m, int64_t tiles_n, int64_t tile_base, int64_t ntiles, int ks,
+                                      const word *Cpart);
+hipError_t gf2_launch_zero_tiles(hipStream_t s, word *C, int64_t cs, int64_t cbs, int64_t m, int64_t wn, int64_t tile_rows, int64_t tw,
+                                 int64_t tiles_m, int64_t tiles_n, int64_t tile_base, int64_t ntiles);
+hipError_t gf2_launch_mask_tail(hipStream_t s, word *M, int64_t stride, int64_t rows, int64_t ncols);
+hipError_t gf2_launch_fill_splitmix(hipStream_t s, word *M, int64_t stride, int64_t rows, int64_t ncols, uint64_t seed);
+hipError_t gf2_launch_fill_splitmix_rows(hipStream_t s, word *M, int64_t stride, int64_t row0, int64_t rows, int64_t ncols,
+                                         uint64_t seed);
+
+// ---- host side ----------------------------------------------------------------------------------------------------------------
+double gf2_small_host_cost(int64_t m, int64_t l, int64_t n);  // small_host.cpp: word operations of the host product
+int gf2_multi_wanted(int64_t m, int64_t l, int64_t n);         // multi.hip: would mzd_mul_mp spread this product over devices?
+void gf2_release_multi(void);                                  // multi.hip: the per-rank arenas of the multi-device path
+void gf2_release_staging(void);                                // mzd_api.hip: the host entry points' staging arena
+
+}  // extern "C"

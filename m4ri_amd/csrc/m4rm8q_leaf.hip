@@ -45,7 +45,7 @@
 // (/root/reference m4ri/brilliantrussian.c:1032-1190, :163-211, m4ri/xor_template.h:12-227).
 #include <hip/hip_runtime.h>
 #include <type_traits>
-#include "gf2_common.h"
+#include "gf2_internal.h"
 
 // which half of the workgroup builds the tables: 0 = waves 0..3 (dispatched first), 1 = waves 4..7
 #ifndef K8Q_BUILDER_HALF

@@ -25,7 +25,7 @@
 //   * A and B stream from L2/HBM through plain global loads issued one phase ahead (VMEM pipe is
 //     otherwise idle); the LDS pipe is the binding resource by design.
 #include <hip/hip_runtime.h>
-#include "gf2_common.h"
+#include "gf2_internal.h"
 
 // (rg, ug) instantiations.  Two variants of this kernel were measured and removed again: software-
 // pipelined gathers (two register sets; +-1 %) and B rows staged once per workgroup through LDS

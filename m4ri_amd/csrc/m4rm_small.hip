@@ -25,7 +25,7 @@
 // Replaces (result-identical) _mzd_mul_m4rm, mzd_make_table and _mzd_combine_N of the reference
 // (/root/reference m4ri/brilliantrussian.c:1032-1190, :163-211, m4ri/xor_template.h:12-227) on small operands.
 #include <hip/hip_runtime.h>
-#include "gf2_common.h"
+#include "gf2_internal.h"
 
 namespace {
 

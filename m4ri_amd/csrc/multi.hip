@@ -40,35 +40,10 @@
 #include <mutex>
 #include <thread>
 #include <vector>
-#include "gf2_common.h"
+#include "gf2_internal.h"
 #include "../../include/m4ri_amd.h"
 
-extern "C" {
-hipError_t gf2_launch_winograd_down(hipStream_t s, int bside, const word *parent, int64_t p_stride, int64_t p_bs, word *child,
-                                    int64_t nparents, int64_t crows, int64_t cw);
-hipError_t gf2_launch_winograd_up(hipStream_t s, int acc, const word *prod, word *parent, int64_t o_stride, int64_t o_bs,
-                                  int64_t nparents, int64_t crows, int64_t cw);
-hipError_t gf2_launch_winograd_down2(hipStream_t s, int bside, const word *gparent, int64_t p_stride, int64_t p_bs, word *gchild,
-                                     int64_t nparents, int64_t crows, int64_t cw);
-hipError_t gf2_launch_winograd_up2(hipStream_t s, int acc, const word *prod, word *gparent, int64_t o_stride, int64_t o_bs,
-                                   int64_t nparents, int64_t crows, int64_t cw);
-hipError_t gf2_launch_mask_tail(hipStream_t s, word *M, int64_t stride, int64_t rows, int64_t ncols);
-// the rank-R scheme of the 4 x 4 x 4 block product (scheme_passes.hip): two sharded levels = the scheme once, R sub-products instead of 49
-int gf2_scheme444_rank(void);
-int gf2_scheme444_ok(int levels, int64_t a_rows, int64_t a_cw, int64_t b_rows, int64_t b_cw);
-hipError_t gf2_launch_scheme_down(hipStream_t s, int levels, int bside, const word *anc, int64_t p_stride, int64_t p_bs, word *child, int64_t nparents,
-                                  int64_t crows, int64_t cw);
-hipError_t gf2_launch_scheme_up(hipStream_t s, int levels, int acc, const word *prod, word *anc, int64_t o_stride, int64_t o_bs, int64_t nparents,
-                                int64_t crows, int64_t cw);
-}
-
 namespace {
-
-#define HIPTRY(expr)                                  \
-  do {                                                \
-    hipError_t e_ = (hipError_t)(expr);               \
-    if (e_ != hipSuccess) return (int)e_;             \
-  } while (0)
 
 int64_t cut_of(int64_t rows, int world, int r) { return rows * (int64_t)r / (int64_t)world; }
 int64_t roundup(int64_t x, int64_t q) { return (x + q - 1) / q * q; }
@@ -171,16 +146,9 @@ int m4ri_amd_shard_down_dev(const m4ri_amd_shard_plan *p, int rank, const word *
   if (!p || rank < 0 || rank >= p->world) return (int)hipErrorInvalidValue;
   hipStream_t st = (hipStream_t)stream;
   const int64_t sa = m4ri_amd_shard_slab_rows(p, rank, 0), sb = m4ri_amd_shard_slab_rows(p, rank, 1);
-  if (p->levels == 1) {
-    if (A_local) HIPTRY(gf2_launch_winograd_down(st, 0, A_local, a_stride, 0, child_a, 1, sa, p->cwl));
-    if (B_local) HIPTRY(gf2_launch_winograd_down(st, 1, B_local, b_stride, 0, child_b, 1, sb, p->cwn));
-  } else if (plan_uses_scheme(p)) {
-    if (A_local && sa > 0) HIPTRY(gf2_launch_scheme_down(st, 2, 0, A_local, a_stride, 0, child_a, 1, sa, p->cwl));
-    if (B_local && sb > 0) HIPTRY(gf2_launch_scheme_down(st, 2, 1, B_local, b_stride, 0, child_b, 1, sb, p->cwn));
-  } else {
-    if (A_local) HIPTRY(gf2_launch_winograd_down2(st, 0, A_local, a_stride, 0, child_a, 1, sa, p->cwl));
-    if (B_local) HIPTRY(gf2_launch_winograd_down2(st, 1, B_local, b_stride, 0, child_b, 1, sb, p->cwn));
-  }
+  const int scheme = plan_uses_scheme(p);
+  if (A_local) HIPTRY(gf2_launch_pass_down(st, p->levels, scheme, 0, A_local, a_stride, 0, child_a, 1, sa, p->cwl));
+  if (B_local) HIPTRY(gf2_launch_pass_down(st, p->levels, scheme, 1, B_local, b_stride, 0, child_b, 1, sb, p->cwn));
   return 0;
 }
 
@@ -190,9 +158,7 @@ int m4ri_amd_shard_up_dev(const m4ri_amd_shard_plan *p, int rank, const word *sl
   if (!p || rank < 0 || rank >= p->world) return (int)hipErrorInvalidValue;
   hipStream_t st = (hipStream_t)stream;
   const int64_t sa = m4ri_amd_shard_slab_rows(p, rank, 0);
-  if (p->levels == 1) HIPTRY(gf2_launch_winograd_up(st, add ? 1 : 0, slabs_p, C_local, c_stride, 0, 1, sa, p->cwn));
-  else if (plan_uses_scheme(p)) { if (sa > 0) HIPTRY(gf2_launch_scheme_up(st, 2, add ? 1 : 0, slabs_p, C_local, c_stride, 0, 1, sa, p->cwn)); }
-  else HIPTRY(gf2_launch_winograd_up2(st, add ? 1 : 0, slabs_p, C_local, c_stride, 0, 1, sa, p->cwn));
+  HIPTRY(gf2_launch_pass_up(st, p->levels, plan_uses_scheme(p), add ? 1 : 0, slabs_p, C_local, c_stride, 0, 1, sa, p->cwn));
   return 0;
 }
 

@@ -29,7 +29,7 @@
 #include <mutex>
 #include <thread>
 #include <vector>
-#include "gf2_common.h"
+#include "gf2_internal.h"
 #include "../../include/m4ri_amd.h"
 
 namespace {
@@ -265,8 +265,6 @@ void late_begin(LateC &lc, rci_t r, rci_t c) {
   } catch (...) {  // fewer (or no) helpers: the downloads fault what is left
   }
 }
-
-extern "C" hipError_t gf2_launch_copy_masked(hipStream_t s, word *C, int64_t cs, const word *A, int64_t as, int64_t rows, int64_t ncols);
 
 // ---- staging arena ------------------------------------------------------------------------------
 // Device copies of host operands live in ONE grow-only buffer that is re-carved on every call: no
@@ -504,7 +502,6 @@ std::atomic<int64_t> g_small_count{0};  // products that took the host path
 // (gf2_small_host_cost of small_host.cpp: word operations of ITS algorithm) at most threshold / 240 -- 2^27 / 240 = 559240, 39 us at the
 // 0.07 ns per word operation it runs at: below the 25 ... 60 us a call through the GPU costs whatever its size.  The second bound is
 // what keeps degenerate shapes -- 1 x 1 x 2^26, 2^26 x 1 x 1 -- away from a single-threaded loop.
-extern "C" double gf2_small_host_cost(int64_t m, int64_t l, int64_t n);
 bool small_product_wanted(int64_t m, int64_t l, int64_t n, int64_t threshold) {
   if (threshold <= 0 || m <= 0 || n <= 0) return false;
   if ((double)m * (double)l * (double)n > (double)threshold) return false;
@@ -1602,8 +1599,6 @@ int m4ri_amd_is_pinned(const mzd_t *M) {
     if (M->data >= p.hbase && M->data < p.hbase + p.words && M->rowstride == p.rowstride) return is_newer(p) ? 2 : 1;
   return 0;
 }
-
-int gf2_multi_wanted(int64_t m, int64_t l, int64_t n);  // multi.hip
 
 // mp.c:277-297 / :299-324.  Several devices + a product large enough: the top Strassen-Winograd
 // sub-products go over the devices (multi.hip); else the single-GPU schedule.

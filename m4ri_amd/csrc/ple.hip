@@ -30,16 +30,10 @@
 #include <cstring>
 #include <mutex>
 #include <vector>
-#include "gf2_common.h"
+#include "gf2_internal.h"
 #include "../../include/m4ri_amd.h"
 
 namespace {
-
-#define HIPTRY(expr)                                  \
-  do {                                                \
-    hipError_t e_ = (hipError_t)(expr);               \
-    if (e_ != hipSuccess) return (int)e_;             \
-  } while (0)
 
 #ifndef PLE_SLICE_THREADS
 #define PLE_SLICE_THREADS 1024

@@ -18,7 +18,7 @@
 // one is unrolled with the scheme's masks as compile-time constants (16 words in registers).
 #include <hip/hip_runtime.h>
 #include <cstdlib>
-#include "gf2_common.h"
+#include "gf2_internal.h"
 #include "scheme444.h"
 
 namespace {

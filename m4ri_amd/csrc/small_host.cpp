@@ -26,6 +26,7 @@
 #include <cstring>
 #include <vector>
 #include "../../include/m4ri_amd.h"
+#include "gf2_internal.h"
 
 namespace {
 

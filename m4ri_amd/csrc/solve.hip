@@ -9,16 +9,10 @@
 // cross PCIe once per step).
 #include <hip/hip_runtime.h>
 #include <vector>
-#include "gf2_common.h"
+#include "gf2_internal.h"
 #include "../../include/m4ri_amd.h"
 
 namespace {
-
-#define HIPTRY(expr)                                  \
-  do {                                                \
-    hipError_t e_ = (hipError_t)(expr);               \
-    if (e_ != hipSuccess) return (int)e_;             \
-  } while (0)
 
 constexpr int SV_THREADS = 256;
 

@@ -17,16 +17,10 @@
 #include <hip/hip_runtime.h>
 #include <mutex>
 #include <stdlib.h>
-#include "gf2_common.h"
+#include "gf2_internal.h"
 #include "../../include/m4ri_amd.h"
 
 namespace {
-
-#define HIPTRY(expr)                                  \
-  do {                                                \
-    hipError_t e_ = (hipError_t)(expr);               \
-    if (e_ != hipSuccess) return (int)e_;             \
-  } while (0)
 
 constexpr int TRSM_THREADS = 64;
 
