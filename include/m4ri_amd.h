@@ -317,6 +317,32 @@ int m4ri_amd_echelonize_batch_dev(word *A, int64_t stride, int64_t a_bs, int64_t
  * number of words, plus a row index and flags, within 160 KiB); 2 one workgroup per member, in place in global memory (valid words
  * up to 512 KiB); 3 members one by one through m4ri_amd_echelonize_dev (blocking) */
 int m4ri_amd_plan_echelonize_batch(int64_t nrows, int64_t ncols);
+/* `batch` independent systems A_b X_b = B_b (mzd_solve_left, m4ri/solve.c:30-152; solve_batch.hip).  A_b: the m x n matrix at
+ * A + b * a_bs, READ ONLY (a_bs = 0: one A shared by all members).  B_b: the max(m, n) x k matrix at B + b * b_bs.  status[b]
+ * (DEVICE int32, required): 0, or -1 when A_b X = B_b has no solution, A_b padded with zero rows to max(m, n).  On status 0, B_b is
+ * overwritten exactly as m4ri_amd_solve_left_dev leaves it: X in rows 0 .. n-1 with the rows of the non-pivot columns zero, rows
+ * n .. max(m, n)-1 zero.  On -1, B_b is left untouched.  rank[b] (DEVICE int32, or NULL): the rank of A_b.
+ * Consistency is always checked, over all padding rows: for m < n a non-zero row m of B makes the member -1 here, while
+ * m4ri_amd_solve_left_dev (as _mzd_solve_left, solve.c:124) looks only from row m + 1 on and returns 0.
+ * Bits at columns >= k of a row's last word, the words from the width to the stride of a row, the words between members and A are
+ * never written.  hipErrorInvalidValue, before any HIP call, for negative sizes, strides or batch strides, a stride below the
+ * width, overlapping B members (batch > 1 and b_bs < (max(m, n) - 1) * b_stride + width), status == NULL with batch > 0, or a NULL
+ * A or B with a non-empty member.  Asynchronous on `stream` (one launch, no allocation, no copy) on paths 0 and 1 of
+ * m4ri_amd_plan_solve_batch; path 2 allocates and BLOCKS. */
+int m4ri_amd_solve_left_batch_dev(const word *A, int64_t a_stride, int64_t a_bs, int64_t m, int64_t n, word *B, int64_t b_stride, int64_t b_bs,
+                                  int64_t k, int64_t batch, int32_t *status, int32_t *rank, void *stream);
+/* `batch` inverses (mzd_inv_m4ri, m4ri/brilliantrussian.c:971-997): Binv_b (n x n at Binv + b * b_bs) <- the right half of the
+ * reduced echelon form of [A_b | I], bit-identical to m4ri_amd_inv_dev, singular members included.  rank[b] (DEVICE int32, or
+ * NULL) = the rank of A_b (n: invertible).  Binv == A with equal strides and batch strides (in place) is allowed; any other overlap
+ * of the two is not (hipErrorInvalidValue).  Memory rules, argument checks and paths as m4ri_amd_solve_left_batch_dev, with
+ * m = k = n. */
+int m4ri_amd_inv_batch_dev(word *Binv, int64_t b_stride, int64_t b_bs, const word *A, int64_t a_stride, int64_t a_bs, int64_t n, int64_t batch,
+                           int32_t *rank, void *stream);
+/* which path m4ri_amd_solve_left_batch_dev takes for this (m, n, k) and m4ri_amd_inv_batch_dev for (n, n, n) (pure host arithmetic;
+ * -1 for negative sizes): 0 one wave per member (max(m, n) <= 64 and k <= 64); 1 one workgroup per member in LDS (max(m, n) rows of
+ * words(n) + words(k) words padded to an odd count, plus a row index and three flag words per 64 rows, within 160 KiB: the largest
+ * inverse is 768 x 768); 2 members one by one through the per-member call (blocking) */
+int m4ri_amd_plan_solve_batch(int64_t m, int64_t n, int64_t k);
 int m4ri_amd_apply_p_right_dev(word *A, int64_t stride, int64_t nrows, int64_t ncols, const int32_t *P, int64_t length, int trans, void *stream);
 /* Row r <- its columns under the transpositions (i, Q[i]), i = r+1 .. ncols-1 ascending (mzd_apply_p_right_trans_tri,
  * m4ri/mzp.c:279-293).  Q: HOST array, ncols entries, Q[i] >= i.  Blocking. */

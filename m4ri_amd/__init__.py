@@ -175,6 +175,9 @@ SYMBOLS = {
     "m4ri_amd_echelonize_dev": (_I, [_P, _I64, _I64, _I64, _I, _P, _P]),
     "m4ri_amd_echelonize_batch_dev": (_I, [_P, _I64, _I64, _I64, _I64, _I64, _I, _P, _P, _P]),
     "m4ri_amd_plan_echelonize_batch": (_I, [_I64, _I64]),
+    "m4ri_amd_solve_left_batch_dev": (_I, [_P, _I64, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I64, _P, _P, _P]),
+    "m4ri_amd_inv_batch_dev": (_I, [_P, _I64, _I64, _P, _I64, _I64, _I64, _I64, _P, _P]),
+    "m4ri_amd_plan_solve_batch": (_I, [_I64, _I64, _I64]),
     "m4ri_amd_apply_p_right_dev": (_I, [_P, _I64, _I64, _I64, _P, _I64, _I, _P]),
     "m4ri_amd_mzd_init": (MzdPtr, [_I, _I]),
     "m4ri_amd_mzd_free": (None, [MzdPtr]),
@@ -480,6 +483,27 @@ def echelonize_batch_dev(A: int, stride: int, a_bs: int, nrows: int, ncols: int,
 def plan_echelonize_batch(nrows: int, ncols: int) -> int:
     """The path echelonize_batch_dev takes for members of this shape (0 wave, 1 LDS, 2 global, 3 one by one). Host arithmetic."""
     return int(lib().m4ri_amd_plan_echelonize_batch(nrows, ncols))
+
+
+def solve_left_batch_dev(A: int, a_stride: int, a_bs: int, m: int, n: int, B: int, b_stride: int, b_bs: int, k: int, batch: int, status: int,
+                         rank: int = 0, stream: int = 0) -> None:
+    """`batch` systems A_b X_b = B_b, A_b at A + b * a_bs words (read only; a_bs = 0: one shared A), B_b (max(m, n) x k) at B + b * b_bs
+    overwritten by X where status[b] = 0, untouched where it is -1 (no solution); status / rank: DEVICE int32 arrays (rank 0 = not
+    wanted).  Asynchronous on paths 0-1 of plan_solve_batch, blocking on path 2."""
+    _check(lib().m4ri_amd_solve_left_batch_dev(A, a_stride, a_bs, m, n, B, b_stride, b_bs, k, batch, status, rank or None, stream),
+           "m4ri_amd_solve_left_batch_dev")
+
+
+def inv_batch_dev(Binv: int, b_stride: int, b_bs: int, A: int, a_stride: int, a_bs: int, n: int, batch: int, rank: int = 0,
+                  stream: int = 0) -> None:
+    """`batch` inverses, Binv_b <- the right half of the reduced echelon form of [A_b | I] (Binv == A in place allowed); rank: DEVICE
+    int32 array (0 = not wanted).  Asynchronous on paths 0-1 of plan_solve_batch(n, n, n), blocking on path 2."""
+    _check(lib().m4ri_amd_inv_batch_dev(Binv, b_stride, b_bs, A, a_stride, a_bs, n, batch, rank or None, stream), "m4ri_amd_inv_batch_dev")
+
+
+def plan_solve_batch(m: int, n: int, k: int) -> int:
+    """The path solve_left_batch_dev takes for (m, n, k), and inv_batch_dev for (n, n, n) (0 wave, 1 LDS, 2 one by one). Host arithmetic."""
+    return int(lib().m4ri_amd_plan_solve_batch(m, n, k))
 
 
 def m4rm_dev(C: int, c_stride: int, A: int, a_stride: int, B: int, b_stride: int, m: int, l: int, n: int,

@@ -26,14 +26,6 @@ constexpr int64_t EB_LDS_BUDGET = 160 * 1024;          // path 1: the whole LDS 
 constexpr int64_t EB_CAP_BYTES  = 512 * 1024;          // path 2: valid words of a member, bytes
 constexpr int64_t EB_CHUNK      = (int64_t)1 << 30;    // workgroups per launch
 
-__device__ __forceinline__ word readlane64(word x, int lane) {
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)x, lane);
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(x >> 32), lane);
-  return ((word)hi << 32) | lo;
-}
-
-__device__ __forceinline__ word tail_mask(int ncols) { return (ncols & 63) ? (((word)1 << (ncols & 63)) - 1) : ~(word)0; }
-
 // path 0: a wave per member, lane i = row i (one word).  Members b0 + 4 * blockIdx.x + wave.
 __global__ __launch_bounds__(EB_WAVE_THREADS) void eb_wave_kernel(word *__restrict__ A, int64_t stride, int64_t a_bs, int nrows, int ncols,
                                                                   int64_t b0, int64_t batch, int full, int32_t *__restrict__ rank_out,

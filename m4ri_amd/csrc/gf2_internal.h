@@ -14,6 +14,17 @@
     if (e_ != hipSuccess) return (int)e_;             \
   } while (0)
 
+// ---- device helpers of the batched eliminations (echelon_batch.hip, solve_batch.hip) -------------------------------------------
+// lane `lane`'s 64-bit x (wave-uniform lane)
+__device__ __forceinline__ word readlane64(word x, int lane) {
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)x, lane);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(x >> 32), lane);
+  return ((word)hi << 32) | lo;
+}
+
+// the valid bits of a row's last word
+__device__ __forceinline__ word tail_mask(int ncols) { return (ncols & 63) ? (((word)1 << (ncols & 63)) - 1) : ~(word)0; }
+
 extern "C" {
 
 // ---- the M4RM leaves --------------------------------------------------------------------------------------------------------

@@ -1,0 +1,451 @@
+// solve_batch.hip -- linear solves A_b X_b = B_b and inverses A_b^-1 of many independent small matrices, one launch for the batch.
+//
+// Both are Gauss-Jordan on an augmented member: [A | B] for the solve, [A | I] for the inverse, with echelon_batch.hip's pivot rule
+// (columns left to right, the pivot of a column is the first row at or below the rank with the bit set, swapped up to the rank's
+// row) and a full update (every other row with the bit).
+//   solve:   the pivot search runs over A's n columns only.  Afterwards the rows at and below the rank have no bit of A left, so
+//            the system is consistent iff their B part is zero; X row c = the B part of the row whose pivot is column c, and zero
+//            for the non-pivot columns.  That is the solution with its free variables zero, the one PLUQ's Q gives
+//            m4ri_amd_solve_left_dev, because the pivot columns are A's column rank profile either way.
+//   inverse: the search runs over all 2n columns, so the member ends in the reduced echelon form of [A | I], which is unique: its
+//            right half is m4ri_amd_inv_dev's result, for singular members too.
+// A is padded with zero rows to R = max(m, n) rows (the solve's B has R rows).  The paths (m4ri_amd_plan_solve_batch):
+//   0  R <= 64 and k <= 64: a wave per member, lane i holds row i of A and of B (the identity's bit made in a register); pivot = the
+//      lowest lane >= rank of a ballot, the pivot row's words by readlane; X gathered by ds_bpermute.  No LDS, no barrier.
+//   1  the augmented member fits in LDS: a workgroup per member, as eb_block_kernel<true> (rows in LDS under a row index, the swap
+//      of a column as two index entries, a flag pass and ballot per column).
+//   2  larger members one by one through the per-member calls on scratch copies, then one copy of statuses and ranks.  Blocking.
+// Paths 0 and 1 are one launch each (plus chunking above 2^30 workgroups), no allocation, no copy, no host synchronisation.
+// Memory rules: A is never written (except as Binv in place); bits at columns >= k (resp. n) of a row's last word of B / Binv, the
+// words from the width to the stride of a row and anything between members are never written.  An inconsistent member's B is not
+// written at all.
+#include <hip/hip_runtime.h>
+#include <mutex>
+#include <vector>
+#include "gf2_internal.h"
+#include "../../include/m4ri_amd.h"
+
+namespace {
+
+constexpr int SB_WAVE_THREADS   = 256;                 // path 0: four members per workgroup
+constexpr int SB_MAX_THREADS    = 1024;                // path 1
+constexpr int64_t SB_LDS_BUDGET = 160 * 1024;          // path 1: the whole LDS of a CU
+constexpr int64_t SB_CHUNK      = (int64_t)1 << 30;    // workgroups per launch
+
+__device__ __forceinline__ word bpermute64(word x, int src) {  // lane `src`'s x; every lane of the wave must take part
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_ds_bpermute(src << 2, (int)(uint32_t)x);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_ds_bpermute(src << 2, (int)(uint32_t)(x >> 32));
+  return ((word)hi << 32) | lo;
+}
+
+// path 0: a wave per member, lane i = row i of A (a) and of B or the identity (x), one word each.  Members b0 + 4 * blockIdx.x + wave.
+template <bool INV>
+__global__ __launch_bounds__(SB_WAVE_THREADS) void sb_wave_kernel(const word *A, int64_t a_stride, int64_t a_bs, word *B,
+                                                                  int64_t b_stride, int64_t b_bs, int m, int n, int k, int64_t b0,
+                                                                  int64_t batch, int32_t *__restrict__ status, int32_t *__restrict__ rank_out) {
+  const int lane  = threadIdx.x & 63;
+  const int64_t b = b0 + (int64_t)blockIdx.x * (SB_WAVE_THREADS / 64) + (threadIdx.x >> 6);
+  if (b >= batch) return;  // wave-uniform, no barrier in this kernel
+  const int R      = m > n ? m : n;
+  const word amask = tail_mask(n), bmask = tail_mask(k);
+  word *gb         = B + b * b_bs;
+  word a = 0, x = 0, orig = 0;
+  if (lane < m && n > 0) a = A[b * a_bs + (int64_t)lane * a_stride] & amask;
+  if (lane < (INV ? n : R) && k > 0 && (!INV || bmask != ~(word)0)) orig = gb[(int64_t)lane * b_stride];  // the inverse: tail bits only
+  if (INV) x = lane < n ? (word)1 << lane : 0;
+  else x = orig & bmask;
+  // (Binv == A in place: every lane has loaded its row before any store below)
+  int rank = 0;
+  word pivcols = 0;  // bit c: column c < n has a pivot (wave-uniform)
+  for (int c = 0; c < (INV ? 2 * n : n) && rank < m; ++c) {
+    const int bit   = (int)(((INV && c >= n) ? (x >> (c - n)) : (a >> c)) & 1);
+    const word cand = __ballot(bit) & (~(word)0 << rank);
+    if (!cand) continue;
+    const int p    = (int)__builtin_ctzll(cand);
+    const word pa  = readlane64(a, p), px = readlane64(x, p);
+    if (bit && lane != p) {
+      a ^= pa;
+      x ^= px;
+    }
+    const word ra = readlane64(a, rank), rx = readlane64(x, rank);  // row `rank` has no bit c unless it is the pivot: not updated
+    if (lane == rank) {
+      a = pa;
+      x = px;
+    } else if (lane == p) {
+      a = ra;
+      x = rx;
+    }
+    if (c < n) pivcols |= (word)1 << c;
+    ++rank;
+  }
+  if (INV) {
+    if (lane < n) gb[(int64_t)lane * b_stride] = (x & bmask) | (orig & ~bmask);
+    if (lane == 0 && rank_out) rank_out[b] = __builtin_popcountll(pivcols);
+    return;
+  }
+  // rows >= rank have no bit of A left: consistent iff their B words are zero
+  const bool bad = __ballot(lane >= rank && x != 0) != 0;
+  if (!bad) {
+    // X row i (i a pivot column) = B word of the row whose pivot it is: pivots ascend with the rows, so that row is the number of
+    // pivot columns below i.  Non-pivot rows and rows n .. R-1 are zero.
+    const int src = __builtin_popcountll(pivcols & (((word)1 << lane) - 1));
+    word y        = bpermute64(x, src);
+    if (!((pivcols >> lane) & 1)) y = 0;
+    if (lane < R && k > 0) gb[(int64_t)lane * b_stride] = (y & bmask) | (orig & ~bmask);
+  }
+  if (lane == 0) {
+    status[b] = bad ? -1 : 0;
+    if (rank_out) rank_out[b] = rank;
+  }
+}
+
+// path 1: a workgroup per member.  Dynamic LDS (16-byte carve offsets):
+//   rows [R][ldw] words (wa words of A, then wb of B or the identity) | perm [R] int32 (rounded up to 16 B) | flags [2][nfw] words |
+//   pivcols [nfw] words (bit c: column c < n has a pivot; nfw = ceil(R / 64) >= words of n)
+// Row i of the flag pass is owned by thread i % blockDim.x (the lane of its ballot); flags[c & 1] bit i = bit c of logical row i.
+template <bool INV>
+__global__ __launch_bounds__(SB_MAX_THREADS) void sb_block_kernel(const word *A, int64_t a_stride, int64_t a_bs, word *B,
+                                                                  int64_t b_stride, int64_t b_bs, int m, int n, int k, int ldw, int64_t b0,
+                                                                  int32_t *__restrict__ status, int32_t *__restrict__ rank_out) {
+  extern __shared__ __attribute__((aligned(16))) char sb_smem[];
+  const int T = blockDim.x, t = threadIdx.x, lane = t & 63;
+  const int64_t b  = b0 + blockIdx.x;
+  const word *ga   = A + b * a_bs;
+  word *gb         = B + b * b_bs;
+  const int R      = m > n ? m : n;
+  const int wa     = (n + 63) >> 6, wb = (k + 63) >> 6, W = wa + wb;
+  const int nfw    = (R + 63) >> 6;
+  const word amask = tail_mask(n), bmask = tail_mask(k);
+  word *rows       = reinterpret_cast<word *>(sb_smem);
+  int32_t *perm    = reinterpret_cast<int32_t *>(sb_smem + (size_t)R * ldw * 8);
+  word *flags      = reinterpret_cast<word *>(sb_smem + (size_t)R * ldw * 8 + (((size_t)R * 4 + 15) & ~(size_t)15));
+  word *pivcols    = flags + 2 * nfw;
+
+  {
+    const int total = R * W;
+    for (int q = t; q < total; q += T) {
+      const int i = q / W, w = q - i * W;
+      word x = 0;
+      if (w < wa) {
+        if (i < m) {
+          x = ga[(int64_t)i * a_stride + w];
+          if (w == wa - 1) x &= amask;
+        }
+      } else if (INV) {
+        x = ((i >> 6) == w - wa) ? (word)1 << (i & 63) : 0;
+      } else {
+        x = gb[(int64_t)i * b_stride + (w - wa)];
+        if (w == W - 1) x &= bmask;
+      }
+      rows[i * ldw + w] = x;
+    }
+    for (int i = t; i < R; i += T) perm[i] = i;
+    for (int j = t; j < nfw; j += T) pivcols[j] = 0;
+    __syncthreads();
+  }
+
+  int rank = 0;
+  int sw_r = -1, sw_p = -1, sw_R = 0, sw_P = 0;  // the previous column's pending swap of perm[rank] and perm[p]
+  for (int c = 0; c < (INV ? 2 * n : n) && rank < m; ++c) {
+    word *buf    = flags + (c & 1) * nfw;
+    const int cw = c < n ? c >> 6 : wa + ((c - n) >> 6), cb = (c < n ? c : c - n) & 63;
+    // flag pass: each thread its own rows and their index entries
+    for (int base = t - lane; base < R; base += T) {
+      const int i = base + lane;
+      int bit     = 0;
+      if (i < R) {
+        int ph = (i == sw_r) ? sw_P : (i == sw_p) ? sw_R : perm[i];
+        if (i == sw_r || i == sw_p) perm[i] = ph;
+        bit = (int)((rows[ph * ldw + cw] >> cb) & 1);
+      }
+      const word bal = __ballot(bit);
+      if (lane == 0) buf[base >> 6] = bal;
+    }
+    sw_r = sw_p = -1;
+    __syncthreads();
+    int p = -1;
+    for (int j = rank >> 6; j < nfw; ++j) {
+      word f = buf[j];
+      if (j == (rank >> 6)) f &= ~(word)0 << (rank & 63);
+      if (f) {
+        p = j * 64 + (int)__builtin_ctzll(f);
+        break;
+      }
+    }
+    if (p < 0) continue;  // no writes this column; the next flag pass uses the other buffer
+    if (t == 0 && c < n) pivcols[c >> 6] |= (word)1 << (c & 63);
+    const int nw = W - cw;
+    const int P  = perm[p];
+    const word *prow = rows + P * ldw;
+    if (p != rank) {
+      sw_r = rank; sw_p = p; sw_P = P; sw_R = perm[rank];
+    }
+    // the full update: every flagged row i != p (row `rank` is unflagged when p != rank), words cw .. W-1 (the pivot row has no
+    // bit left of column c).  Item q = (i, w) with q = i * nw + (w - cw), q = t, t + T, ...: advanced by (qi, qw) without a division.
+    {
+      const int qi = T / nw, qw = T - qi * nw;
+      int i = t / nw, w = cw + (t - (t / nw) * nw);
+      while (i < R) {
+        const int f = (int)((buf[i >> 6] >> (i & 63)) & 1);
+        if (f && i != p) rows[perm[i] * ldw + w] ^= prow[w];
+        i += qi;
+        w += qw;
+        if (w >= W) {
+          w -= nw;
+          ++i;
+        }
+      }
+    }
+    ++rank;
+    __syncthreads();
+  }
+  if (sw_r >= 0) {  // the last column's swap (its owners only, as in the flag pass)
+    for (int i = t; i < R; i += T)
+      if (i == sw_r) perm[i] = sw_P;
+      else if (i == sw_p) perm[i] = sw_R;
+  }
+  __syncthreads();
+
+  if (INV) {
+    const int total = n * wb;
+    for (int q = t; q < total; q += T) {
+      const int i = q / wb, w = q - i * wb;
+      word x    = rows[perm[i] * ldw + wa + w];
+      word *dst = gb + (int64_t)i * b_stride + w;
+      if (w == wb - 1 && bmask != ~(word)0) x = (x & bmask) | (*dst & ~bmask);
+      *dst = x;
+    }
+    if (t == 0 && rank_out) {
+      int r = 0;
+      for (int j = 0; j < nfw; ++j) r += __builtin_popcountll(pivcols[j]);
+      rank_out[b] = r;
+    }
+    return;
+  }
+
+  // rows >= rank have no bit of A left: consistent iff their B words are zero.  The verdict in flags[0], the pivot rows below column
+  // j * 64 in the second flag buffer (both free now; no __syncthreads_or, whose static LDS would not fit beside a full budget).
+  if (t == 0) flags[0] = 0;
+  __syncthreads();
+  int nz = 0;
+  for (int q = rank * wb + t; q < R * wb; q += T) {
+    const int i = q / wb, w = q - i * wb;
+    nz |= rows[perm[i] * ldw + wa + w] != 0;
+  }
+  if (__ballot(nz) && lane == 0) flags[0] = 1;
+  __syncthreads();
+  const bool bad = flags[0] != 0;
+  if (!bad) {
+    int32_t *below = reinterpret_cast<int32_t *>(flags + nfw);
+    if (t == 0) {
+      int s = 0;
+      for (int j = 0; j < nfw; ++j) {
+        below[j] = s;
+        s += __builtin_popcountll(pivcols[j]);
+      }
+    }
+    __syncthreads();
+    const int total = R * wb;
+    for (int q = t; q < total; q += T) {
+      const int i = q / wb, w = q - i * wb;
+      word x      = 0;
+      if (i < n) {
+        const word pc = pivcols[i >> 6];
+        if ((pc >> (i & 63)) & 1) x = rows[perm[below[i >> 6] + __builtin_popcountll(pc & (((word)1 << (i & 63)) - 1))] * ldw + wa + w];
+      }
+      word *dst = gb + (int64_t)i * b_stride + w;
+      if (w == wb - 1 && bmask != ~(word)0) x = (x & bmask) | (*dst & ~bmask);
+      *dst = x;
+    }
+  }
+  if (t == 0) {
+    status[b] = bad ? -1 : 0;
+    if (rank_out) rank_out[b] = rank;
+  }
+}
+
+int64_t lds_row_words(int64_t width) { return width + ((width & 1) ^ 1); }  // odd: the flag pass reads one word per row
+
+int64_t lds_bytes_path1(int64_t R, int64_t W) {
+  return R * lds_row_words(W) * 8 + ((R * 4 + 15) & ~(int64_t)15) + 3 * ((R + 63) / 64) * 8;
+}
+
+int block_threads(int64_t R, int64_t W) { return R * W >= 8192 ? SB_MAX_THREADS : 256; }
+
+template <bool INV>
+int launch(const word *A, int64_t a_stride, int64_t a_bs, word *B, int64_t b_stride, int64_t b_bs, int64_t m, int64_t n, int64_t k,
+           int64_t batch, int path, int32_t *status, int32_t *rank, hipStream_t st) {
+  if (path == 0) {
+    const int64_t per = SB_WAVE_THREADS / 64;
+    for (int64_t b0 = 0; b0 < batch; b0 += SB_CHUNK * per) {
+      const int64_t cnt = (batch - b0 < SB_CHUNK * per) ? batch - b0 : SB_CHUNK * per;
+      hipLaunchKernelGGL(sb_wave_kernel<INV>, dim3((unsigned)((cnt + per - 1) / per)), dim3(SB_WAVE_THREADS), 0, st, A, a_stride, a_bs, B, b_stride,
+                         b_bs, (int)m, (int)n, (int)k, b0, batch, status, rank);
+      HIPTRY(hipGetLastError());
+    }
+    return 0;
+  }
+  static std::once_flag once;
+  std::call_once(once, [] {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(sb_block_kernel<INV>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SB_LDS_BUDGET);
+  });
+  const int64_t R = m > n ? m : n, W = words_of(n) + words_of(k);
+  const int threads = block_threads(R, W);
+  const size_t lds  = (size_t)lds_bytes_path1(R, W);
+  for (int64_t b0 = 0; b0 < batch; b0 += SB_CHUNK) {
+    const int64_t cnt = (batch - b0 < SB_CHUNK) ? batch - b0 : SB_CHUNK;
+    hipLaunchKernelGGL(sb_block_kernel<INV>, dim3((unsigned)cnt), dim3(threads), lds, st, A, a_stride, a_bs, B, b_stride, b_bs, (int)m, (int)n,
+                       (int)k, (int)lds_row_words(W), b0, status, rank);
+    HIPTRY(hipGetLastError());
+  }
+  return 0;
+}
+
+// path 2 helper: are rows r0 .. r1-1 of the k-column matrix at M (stride words) all zero?  Copies them to the host.  Blocking.
+int rows_zero(const word *M, int64_t stride, int64_t r0, int64_t r1, int64_t k, hipStream_t st, bool *zero) {
+  *zero = true;
+  const int64_t w = words_of(k);
+  if (r1 <= r0 || w == 0) return 0;
+  std::vector<word> h((size_t)((r1 - r0) * w));
+  HIPTRY(hipMemcpy2DAsync(h.data(), (size_t)w * 8, M + r0 * stride, (size_t)stride * 8, (size_t)w * 8, (size_t)(r1 - r0), hipMemcpyDeviceToHost, st));
+  HIPTRY(hipStreamSynchronize(st));
+  const word mask = (k & 63) ? (((word)1 << (k & 63)) - 1) : ~(word)0;
+  for (int64_t i = 0; i < r1 - r0; ++i)
+    for (int64_t j = 0; j < w; ++j)
+      if (h[(size_t)(i * w + j)] & (j == w - 1 ? mask : ~(word)0)) {
+        *zero = false;
+        return 0;
+      }
+  return 0;
+}
+
+// path 2: a clean copy (tail bits zero) of the m x n matrix at src into scratch
+int clean_copy(word *dst, int64_t dst_stride, const word *src, int64_t src_stride, int64_t m, int64_t n, hipStream_t st) {
+  HIPTRY(hipMemsetAsync(dst, 0, (size_t)(m * dst_stride) * 8, st));
+  HIPTRY(gf2_launch_copy_masked(st, dst, dst_stride, src, src_stride, m, n));
+  return 0;
+}
+
+// path 2 of the solve: per member, B's padding rows m .. R-1 checked first (all of them, see the header), then PLUQ of a copy of A_b
+// and the solve through it on a copy of B_b -- m4ri_amd_solve_left_dev's two steps, split to keep the rank -- and X copied back only
+// when it exists.
+int run_path2_solve(const word *A, int64_t a_stride, int64_t a_bs, int64_t m, int64_t n, word *B, int64_t b_stride, int64_t b_bs, int64_t k,
+                    int64_t batch, int32_t *status, int32_t *rank, hipStream_t st) {
+  const int64_t R = m > n ? m : n, wa = words_of(n), wb = words_of(k);
+  std::vector<int32_t> hs((size_t)batch), hr((size_t)batch), P((size_t)(m > 0 ? m : 1)), Q((size_t)(n > 0 ? n : 1));
+  word *sA = nullptr, *sB = nullptr;
+  auto run = [&]() -> int {
+    if (m > 0 && n > 0) HIPTRY(hipMalloc(reinterpret_cast<void **>(&sA), (size_t)(m * wa) * 8));
+    if (wb > 0) HIPTRY(hipMalloc(reinterpret_cast<void **>(&sB), (size_t)(R * wb) * 8));
+    for (int64_t b = 0; b < batch; ++b) {
+      const word *Ab = A + b * a_bs;
+      word *Bb       = B + b * b_bs;
+      int32_t r      = 0;
+      if (m > 0 && n > 0) {
+        if (int rc = clean_copy(sA, wa, Ab, a_stride, m, n, st)) return rc;
+        if (int rc = m4ri_amd_pluq_dev(sA, wa, m, n, P.data(), Q.data(), &r, M4RI_AMD_PLE_CUTOFF, st)) return rc;
+      }
+      hr[(size_t)b] = r;
+      bool zero     = true;
+      if (int rc = rows_zero(Bb, b_stride, (m > 0 && n > 0) ? m : 0, R, k, st, &zero)) return rc;  // A = 0: every row of B
+      int ret = zero ? 0 : -1;
+      if (ret == 0 && wb > 0 && m > 0 && n > 0) {
+        if (int rc = clean_copy(sB, wb, Bb, b_stride, R, k, st)) return rc;
+        if (int rc = m4ri_amd_pluq_solve_left_dev(sA, wa, m, n, r, P.data(), Q.data(), sB, wb, R, k, 0, 1, &ret, st)) return rc;
+        if (ret == 0) HIPTRY(gf2_launch_copy_masked(st, Bb, b_stride, sB, wb, R, k));
+      }
+      hs[(size_t)b] = ret;
+    }
+    HIPTRY(hipMemcpyAsync(status, hs.data(), (size_t)batch * 4, hipMemcpyHostToDevice, st));
+    if (rank) HIPTRY(hipMemcpyAsync(rank, hr.data(), (size_t)batch * 4, hipMemcpyHostToDevice, st));
+    return (int)hipStreamSynchronize(st);
+  };
+  const int rc = run();
+  if (rc) (void)hipStreamSynchronize(st);
+  if (sA) (void)hipFree(sA);
+  if (sB) (void)hipFree(sB);
+  return rc;
+}
+
+// path 2 of the inverse: per member, m4ri_amd_inv_dev on a clean copy of A_b into scratch, copied into Binv_b; the rank (when
+// wanted) by m4ri_amd_echelonize_dev of the copy afterwards.
+int run_path2_inv(word *Binv, int64_t b_stride, int64_t b_bs, const word *A, int64_t a_stride, int64_t a_bs, int64_t n, int64_t batch, int32_t *rank,
+                  hipStream_t st) {
+  const int64_t wn = words_of(n);
+  std::vector<int32_t> hr((size_t)batch);
+  word *sA = nullptr, *sX = nullptr;
+  auto run = [&]() -> int {
+    HIPTRY(hipMalloc(reinterpret_cast<void **>(&sA), (size_t)(n * wn) * 8));
+    HIPTRY(hipMalloc(reinterpret_cast<void **>(&sX), (size_t)(n * wn) * 8));
+    for (int64_t b = 0; b < batch; ++b) {
+      if (int rc = clean_copy(sA, wn, A + b * a_bs, a_stride, n, n, st)) return rc;
+      if (int rc = m4ri_amd_inv_dev(sX, wn, sA, wn, n, st)) return rc;
+      HIPTRY(gf2_launch_copy_masked(st, Binv + b * b_bs, b_stride, sX, wn, n, n));
+      if (rank) {
+        if (int rc = m4ri_amd_echelonize_dev(sA, wn, n, n, 0, &hr[(size_t)b], st)) return rc;
+      }
+    }
+    if (rank) HIPTRY(hipMemcpyAsync(rank, hr.data(), (size_t)batch * 4, hipMemcpyHostToDevice, st));
+    return (int)hipStreamSynchronize(st);
+  };
+  const int rc = run();
+  if (rc) (void)hipStreamSynchronize(st);
+  if (sA) (void)hipFree(sA);
+  if (sX) (void)hipFree(sX);
+  return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int m4ri_amd_plan_solve_batch(int64_t m, int64_t n, int64_t k) {
+  if (m < 0 || n < 0 || k < 0) return -1;
+  const int64_t R = m > n ? m : n;
+  if (R <= 64 && k <= 64) return 0;
+  const int64_t W = words_of(n) + words_of(k);
+  if (R > SB_LDS_BUDGET / 8 || W > SB_LDS_BUDGET / 8) return 2;
+  return lds_bytes_path1(R, W) <= SB_LDS_BUDGET ? 1 : 2;
+}
+
+int m4ri_amd_solve_left_batch_dev(const word *A, int64_t a_stride, int64_t a_bs, int64_t m, int64_t n, word *B, int64_t b_stride, int64_t b_bs,
+                                  int64_t k, int64_t batch, int32_t *status, int32_t *rank, void *stream) {
+  if (m < 0 || n < 0 || k < 0 || batch < 0 || a_stride < 0 || a_bs < 0 || b_stride < 0 || b_bs < 0) return (int)hipErrorInvalidValue;
+  const int64_t R = m > n ? m : n, wa = words_of(n), wb = words_of(k);
+  if (a_stride < wa || b_stride < wb) return (int)hipErrorInvalidValue;
+  if (batch > 1 && R > 0 && b_bs < (R - 1) * b_stride + wb) return (int)hipErrorInvalidValue;
+  if (batch > 0 && !status) return (int)hipErrorInvalidValue;
+  if (batch > 0 && ((m > 0 && n > 0 && !A) || (R > 0 && k > 0 && !B))) return (int)hipErrorInvalidValue;
+  if (batch == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  const int path = m4ri_amd_plan_solve_batch(m, n, k);
+  if (path == 2) return run_path2_solve(A, a_stride, a_bs, m, n, B, b_stride, b_bs, k, batch, status, rank, st);
+  return launch<false>(A, a_stride, a_bs, B, b_stride, b_bs, m, n, k, batch, path, status, rank, st);
+}
+
+int m4ri_amd_inv_batch_dev(word *Binv, int64_t b_stride, int64_t b_bs, const word *A, int64_t a_stride, int64_t a_bs, int64_t n, int64_t batch,
+                           int32_t *rank, void *stream) {
+  if (n < 0 || batch < 0 || b_stride < 0 || b_bs < 0 || a_stride < 0 || a_bs < 0) return (int)hipErrorInvalidValue;
+  const int64_t wn = words_of(n);
+  if (b_stride < wn || a_stride < wn) return (int)hipErrorInvalidValue;
+  if (batch > 1 && n > 0 && b_bs < (n - 1) * b_stride + wn) return (int)hipErrorInvalidValue;
+  if (batch > 0 && n > 0 && (!Binv || !A)) return (int)hipErrorInvalidValue;
+  if (batch > 0 && n > 0) {  // in place with the same layout, or no overlap at all
+    const uintptr_t bi = (uintptr_t)Binv, ai = (uintptr_t)A;
+    if (bi == ai) {
+      if (a_stride != b_stride || a_bs != b_bs) return (int)hipErrorInvalidValue;
+    } else {
+      const uintptr_t bend = bi + (uintptr_t)(((batch - 1) * b_bs + (n - 1) * b_stride + wn) * 8);
+      const uintptr_t aend = ai + (uintptr_t)(((batch - 1) * a_bs + (n - 1) * a_stride + wn) * 8);
+      if (bi < aend && ai < bend) return (int)hipErrorInvalidValue;
+    }
+  }
+  if (batch == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  if (n == 0) return rank ? (int)hipMemsetAsync(rank, 0, (size_t)batch * 4, st) : 0;
+  const int path = m4ri_amd_plan_solve_batch(n, n, n);
+  if (path == 2) return run_path2_inv(Binv, b_stride, b_bs, A, a_stride, a_bs, n, batch, rank, st);
+  return launch<true>(A, a_stride, a_bs, Binv, b_stride, b_bs, n, n, n, batch, path, nullptr, rank, st);
+}
+
+}  // extern "C"
