@@ -343,6 +343,25 @@ int m4ri_amd_inv_batch_dev(word *Binv, int64_t b_stride, int64_t b_bs, const wor
  * words(n) + words(k) words padded to an odd count, plus a row index and three flag words per 64 rows, within 160 KiB: the largest
  * inverse is 768 x 768); 2 members one by one through the per-member call (blocking) */
 int m4ri_amd_plan_solve_batch(int64_t m, int64_t n, int64_t k);
+/* `batch` null-space bases {x : A_b x = 0} (mzd_kernel_left_pluq, m4ri/solve.c:154-191; solve_batch.hip).  A_b: the m x n matrix
+ * at A + b * a_bs, READ ONLY (a_bs = 0: one A shared by all members; unlike m4ri_amd_kernel_left_pluq_dev, A is not overwritten).
+ * R_b: the n x kc matrix at R + b * r_bs (kc <= n).  Its first min(kc, n - rank[b]) columns are the first basis vectors exactly as
+ * m4ri_amd_kernel_left_pluq_dev lays them out; the columns from there up to kc are written zero (R need not be cleared).  kc = n
+ * holds the whole basis, kc = 1 one dependency (if any).  rank[b] (DEVICE int32, required) = the rank of A_b: the nullity is
+ * n - rank[b], and when it exceeds kc the basis was cut.  m = 0 gives the first kc columns of the identity; n = 0 writes only rank.
+ * Bits at columns >= kc of a row's last word, the words from the width to r_stride of a row, the words between members and A are
+ * never written.  hipErrorInvalidValue, before any HIP call, for negative sizes, strides or batch strides, kc > n, a_stride <
+ * words(n) or r_stride < words(kc), overlapping R members (batch > 1 and r_bs < (n - 1) * r_stride + words(kc)), R overlapping A
+ * (the span from the first member's start to the last member's end of each), rank == NULL with batch > 0, or a NULL A or R with a
+ * non-empty member.  batch = 0 succeeds without touching anything.  Asynchronous on `stream` (one launch, no allocation, no copy:
+ * capturable) on paths 0 and 1 of m4ri_amd_plan_kernel_batch; path 2 allocates and BLOCKS. */
+int m4ri_amd_kernel_left_batch_dev(const word *A, int64_t a_stride, int64_t a_bs, int64_t m, int64_t n, word *R, int64_t r_stride, int64_t r_bs,
+                                   int64_t kc, int64_t batch, int32_t *rank, void *stream);
+/* which path m4ri_amd_kernel_left_batch_dev takes for m x n members (pure host arithmetic; -1 for negative sizes): 0 one wave per
+ * member (m, n <= 64); 1 one workgroup per member in LDS (m rows of words(n) words padded to an odd count, a row index, three flag
+ * words per 64 of max(m, n), two int32 tables of n entries, within 160 KiB: 1024 x 1024 fits); 2 members one by one through
+ * m4ri_amd_kernel_left_pluq_dev on scratch copies (blocking) */
+int m4ri_amd_plan_kernel_batch(int64_t m, int64_t n);
 int m4ri_amd_apply_p_right_dev(word *A, int64_t stride, int64_t nrows, int64_t ncols, const int32_t *P, int64_t length, int trans, void *stream);
 /* Row r <- its columns under the transpositions (i, Q[i]), i = r+1 .. ncols-1 ascending (mzd_apply_p_right_trans_tri,
  * m4ri/mzp.c:279-293).  Q: HOST array, ncols entries, Q[i] >= i.  Blocking. */

@@ -178,6 +178,8 @@ SYMBOLS = {
     "m4ri_amd_solve_left_batch_dev": (_I, [_P, _I64, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I64, _P, _P, _P]),
     "m4ri_amd_inv_batch_dev": (_I, [_P, _I64, _I64, _P, _I64, _I64, _I64, _I64, _P, _P]),
     "m4ri_amd_plan_solve_batch": (_I, [_I64, _I64, _I64]),
+    "m4ri_amd_kernel_left_batch_dev": (_I, [_P, _I64, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I64, _P, _P]),
+    "m4ri_amd_plan_kernel_batch": (_I, [_I64, _I64]),
     "m4ri_amd_apply_p_right_dev": (_I, [_P, _I64, _I64, _I64, _P, _I64, _I, _P]),
     "m4ri_amd_mzd_init": (MzdPtr, [_I, _I]),
     "m4ri_amd_mzd_free": (None, [MzdPtr]),
@@ -504,6 +506,20 @@ def inv_batch_dev(Binv: int, b_stride: int, b_bs: int, A: int, a_stride: int, a_
 def plan_solve_batch(m: int, n: int, k: int) -> int:
     """The path solve_left_batch_dev takes for (m, n, k), and inv_batch_dev for (n, n, n) (0 wave, 1 LDS, 2 one by one). Host arithmetic."""
     return int(lib().m4ri_amd_plan_solve_batch(m, n, k))
+
+
+def kernel_left_batch_dev(A: int, a_stride: int, a_bs: int, m: int, n: int, R: int, r_stride: int, r_bs: int, kc: int, batch: int, rank: int,
+                          stream: int = 0) -> None:
+    """`batch` null-space bases, A_b (m x n) at A + b * a_bs words (read only; a_bs = 0: one shared A), R_b (n x kc) at R + b * r_bs <- the
+    first min(kc, n - rank[b]) vectors of mzd_kernel_left_pluq's basis, zero columns up to kc; rank: DEVICE int32 array (required).
+    Asynchronous on paths 0-1 of plan_kernel_batch, blocking on path 2."""
+    _check(lib().m4ri_amd_kernel_left_batch_dev(A, a_stride, a_bs, m, n, R, r_stride, r_bs, kc, batch, rank or None, stream),
+           "m4ri_amd_kernel_left_batch_dev")
+
+
+def plan_kernel_batch(m: int, n: int) -> int:
+    """The path kernel_left_batch_dev takes for m x n members (0 wave, 1 LDS, 2 one by one). Host arithmetic."""
+    return int(lib().m4ri_amd_plan_kernel_batch(m, n))
 
 
 def m4rm_dev(C: int, c_stride: int, A: int, a_stride: int, B: int, b_stride: int, m: int, l: int, n: int,

@@ -1,6 +1,8 @@
-// solve_batch.hip -- linear solves A_b X_b = B_b and inverses A_b^-1 of many independent small matrices, one launch for the batch.
+// solve_batch.hip -- linear solves A_b X_b = B_b, inverses A_b^-1 and null-space bases of many independent small matrices, one launch
+// for the batch.
 //
-// Both are Gauss-Jordan on an augmented member: [A | B] for the solve, [A | I] for the inverse, with echelon_batch.hip's pivot rule
+// All three are Gauss-Jordan: on an augmented member [A | B] for the solve, [A | I] for the inverse, on A alone for the null space
+// (the op, SB_SOLVE / SB_INV / SB_KER, is the kernels' template argument), with echelon_batch.hip's pivot rule
 // (columns left to right, the pivot of a column is the first row at or below the rank with the bit set, swapped up to the rank's
 // row) and a full update (every other row with the bit).
 //   solve:   the pivot search runs over A's n columns only.  Afterwards the rows at and below the rank have no bit of A left, so
@@ -9,16 +11,21 @@
 //            m4ri_amd_solve_left_dev, because the pivot columns are A's column rank profile either way.
 //   inverse: the search runs over all 2n columns, so the member ends in the reduced echelon form of [A | I], which is unique: its
 //            right half is m4ri_amd_inv_dev's result, for singular members too.
-// A is padded with zero rows to R = max(m, n) rows (the solve's B has R rows).  The paths (m4ri_amd_plan_solve_batch):
+//   kernel:  the search runs over A's n columns; the member ends in the reduced echelon form E of A with pivot columns
+//            p_0 < ... < p_{r-1}.  mzd_kernel_left_pluq's basis (solve.c:154-191) depends on E alone: pos = [0 .. n-1], swap pos[i]
+//            and pos[p_i] for i = 0 .. r-1 ascending (PLUQ's Q; behind the rank Q is the identity at these sizes), the free
+//            columns in basis order are f_j = pos[r + j], and column j of the basis has a 1 in row f_j and E[i][f_j] in row p_i.
+// For the solve and the inverse A is padded with zero rows to R = max(m, n) rows (the solve's B has R rows); the kernel keeps R = m.
+// The paths (m4ri_amd_plan_solve_batch, m4ri_amd_plan_kernel_batch):
 //   0  R <= 64 and k <= 64: a wave per member, lane i holds row i of A and of B (the identity's bit made in a register); pivot = the
 //      lowest lane >= rank of a ballot, the pivot row's words by readlane; X gathered by ds_bpermute.  No LDS, no barrier.
 //   1  the augmented member fits in LDS: a workgroup per member, as eb_block_kernel<true> (rows in LDS under a row index, the swap
 //      of a column as two index entries, a flag pass and ballot per column).
 //   2  larger members one by one through the per-member calls on scratch copies, then one copy of statuses and ranks.  Blocking.
 // Paths 0 and 1 are one launch each (plus chunking above 2^30 workgroups), no allocation, no copy, no host synchronisation.
-// Memory rules: A is never written (except as Binv in place); bits at columns >= k (resp. n) of a row's last word of B / Binv, the
-// words from the width to the stride of a row and anything between members are never written.  An inconsistent member's B is not
-// written at all.
+// Memory rules: A is never written (except as Binv in place); bits at columns >= k (resp. n, kc) of a row's last word of B / Binv /
+// the basis, the words from the width to the stride of a row and anything between members are never written.  An inconsistent
+// member's B is not written at all.
 #include <hip/hip_runtime.h>
 #include <mutex>
 #include <vector>
@@ -31,6 +38,7 @@ constexpr int SB_WAVE_THREADS   = 256;                 // path 0: four members p
 constexpr int SB_MAX_THREADS    = 1024;                // path 1
 constexpr int64_t SB_LDS_BUDGET = 160 * 1024;          // path 1: the whole LDS of a CU
 constexpr int64_t SB_CHUNK      = (int64_t)1 << 30;    // workgroups per launch
+constexpr int SB_SOLVE = 0, SB_INV = 1, SB_KER = 2;    // the op: X of [A | B], the inverse from [A | I], a null-space basis of A
 
 __device__ __forceinline__ word bpermute64(word x, int src) {  // lane `src`'s x; every lane of the wave must take part
   const uint32_t lo = (uint32_t)__builtin_amdgcn_ds_bpermute(src << 2, (int)(uint32_t)x);
@@ -38,11 +46,13 @@ __device__ __forceinline__ word bpermute64(word x, int src) {  // lane `src`'s x
   return ((word)hi << 32) | lo;
 }
 
-// path 0: a wave per member, lane i = row i of A (a) and of B or the identity (x), one word each.  Members b0 + 4 * blockIdx.x + wave.
-template <bool INV>
+// path 0: a wave per member, lane i = row i of A (a) and of B or the identity (x, zero for the kernel), one word each.  Members
+// b0 + 4 * blockIdx.x + wave.  The kernel's B is the basis R (n x k).
+template <int OP>
 __global__ __launch_bounds__(SB_WAVE_THREADS) void sb_wave_kernel(const word *A, int64_t a_stride, int64_t a_bs, word *B,
                                                                   int64_t b_stride, int64_t b_bs, int m, int n, int k, int64_t b0,
                                                                   int64_t batch, int32_t *__restrict__ status, int32_t *__restrict__ rank_out) {
+  constexpr bool INV = OP == SB_INV, AUG = OP != SB_KER;
   const int lane  = threadIdx.x & 63;
   const int64_t b = b0 + (int64_t)blockIdx.x * (SB_WAVE_THREADS / 64) + (threadIdx.x >> 6);
   if (b >= batch) return;  // wave-uniform, no barrier in this kernel
@@ -51,9 +61,9 @@ __global__ __launch_bounds__(SB_WAVE_THREADS) void sb_wave_kernel(const word *A,
   word *gb         = B + b * b_bs;
   word a = 0, x = 0, orig = 0;
   if (lane < m && n > 0) a = A[b * a_bs + (int64_t)lane * a_stride] & amask;
-  if (lane < (INV ? n : R) && k > 0 && (!INV || bmask != ~(word)0)) orig = gb[(int64_t)lane * b_stride];  // the inverse: tail bits only
+  if (AUG && lane < (INV ? n : R) && k > 0 && (!INV || bmask != ~(word)0)) orig = gb[(int64_t)lane * b_stride];  // the inverse: tail bits only
   if (INV) x = lane < n ? (word)1 << lane : 0;
-  else x = orig & bmask;
+  else if (AUG) x = orig & bmask;
   // (Binv == A in place: every lane has loaded its row before any store below)
   int rank = 0;
   word pivcols = 0;  // bit c: column c < n has a pivot (wave-uniform)
@@ -62,12 +72,12 @@ __global__ __launch_bounds__(SB_WAVE_THREADS) void sb_wave_kernel(const word *A,
     const word cand = __ballot(bit) & (~(word)0 << rank);
     if (!cand) continue;
     const int p    = (int)__builtin_ctzll(cand);
-    const word pa  = readlane64(a, p), px = readlane64(x, p);
+    const word pa  = readlane64(a, p), px = AUG ? readlane64(x, p) : 0;
     if (bit && lane != p) {
       a ^= pa;
       x ^= px;
     }
-    const word ra = readlane64(a, rank), rx = readlane64(x, rank);  // row `rank` has no bit c unless it is the pivot: not updated
+    const word ra = readlane64(a, rank), rx = AUG ? readlane64(x, rank) : 0;  // row `rank` has no bit c unless it is the pivot: not updated
     if (lane == rank) {
       a = pa;
       x = px;
@@ -77,6 +87,39 @@ __global__ __launch_bounds__(SB_WAVE_THREADS) void sb_wave_kernel(const word *A,
     }
     if (c < n) pivcols |= (word)1 << c;
     ++rank;
+  }
+  if (OP == SB_KER) {
+    // The swap rule with lane l following the column that starts at position l (q: where it is), lane i < rank taking p_i.  Then
+    // free column f is basis column q - rank of lane f: row f of R is that bit, row p_i (lane i) gathers E's bits at the free
+    // columns.  Every row of R is stored once, by lane f or by lane i.
+    int q = lane, pi = 0;
+    word rest = pivcols;
+    for (int i = 0; rest; ++i, rest &= rest - 1) {
+      const int p = (int)__builtin_ctzll(rest);
+      if (q == i) q = p;
+      else if (q == p) q = i;
+      if (lane == i) pi = p;
+    }
+    const word freecols = n > 0 ? ~pivcols & amask : 0;
+    word y = 0;
+    for (word fr = freecols; fr; fr &= fr - 1) {
+      const int f = (int)__builtin_ctzll(fr), j = __builtin_amdgcn_readlane(q, f) - rank;
+      if (j < k) y |= ((a >> f) & 1) << j;
+    }
+    if (k > 0) {
+      if (lane < rank) {
+        word *dst = gb + (int64_t)pi * b_stride;
+        *dst      = bmask == ~(word)0 ? y : (y & bmask) | (*dst & ~bmask);
+      }
+      if ((freecols >> lane) & 1) {
+        const int j = q - rank;
+        const word v = j < k ? (word)1 << j : 0;
+        word *dst    = gb + (int64_t)lane * b_stride;
+        *dst         = bmask == ~(word)0 ? v : (v & bmask) | (*dst & ~bmask);
+      }
+    }
+    if (lane == 0) rank_out[b] = rank;
+    return;
   }
   if (INV) {
     if (lane < n) gb[(int64_t)lane * b_stride] = (x & bmask) | (orig & ~bmask);
@@ -100,21 +143,23 @@ __global__ __launch_bounds__(SB_WAVE_THREADS) void sb_wave_kernel(const word *A,
 }
 
 // path 1: a workgroup per member.  Dynamic LDS (16-byte carve offsets):
-//   rows [R][ldw] words (wa words of A, then wb of B or the identity) | perm [R] int32 (rounded up to 16 B) | flags [2][nfw] words |
-//   pivcols [nfw] words (bit c: column c < n has a pivot; nfw = ceil(R / 64) >= words of n)
+//   rows [R][ldw] words (wa words of A, then wb of B or the identity; the kernel: wa only, R = m) | perm [R] int32 (rounded up to
+//   16 B) | flags [2][nfw] words | pivcols [nfw] words (bit c: column c < n has a pivot; nfw = ceil(max(R, n) / 64)) | the kernel
+//   only: pos [n] int32 (the swap rule's arrangement) | idx [n] int32 (a pivot column's pivot row, a free column's basis column)
 // Row i of the flag pass is owned by thread i % blockDim.x (the lane of its ballot); flags[c & 1] bit i = bit c of logical row i.
-template <bool INV>
+template <int OP>
 __global__ __launch_bounds__(SB_MAX_THREADS) void sb_block_kernel(const word *A, int64_t a_stride, int64_t a_bs, word *B,
                                                                   int64_t b_stride, int64_t b_bs, int m, int n, int k, int ldw, int64_t b0,
                                                                   int32_t *__restrict__ status, int32_t *__restrict__ rank_out) {
+  constexpr bool INV = OP == SB_INV;
   extern __shared__ __attribute__((aligned(16))) char sb_smem[];
   const int T = blockDim.x, t = threadIdx.x, lane = t & 63;
   const int64_t b  = b0 + blockIdx.x;
   const word *ga   = A + b * a_bs;
   word *gb         = B + b * b_bs;
-  const int R      = m > n ? m : n;
-  const int wa     = (n + 63) >> 6, wb = (k + 63) >> 6, W = wa + wb;
-  const int nfw    = (R + 63) >> 6;
+  const int R      = (OP == SB_KER || m > n) ? m : n;
+  const int wa     = (n + 63) >> 6, wb = OP == SB_KER ? 0 : (k + 63) >> 6, W = wa + wb;
+  const int rfw    = (R + 63) >> 6, nfw = ((R > n ? R : n) + 63) >> 6;  // flag words of the rows; words of the flag and pivot buffers
   const word amask = tail_mask(n), bmask = tail_mask(k);
   word *rows       = reinterpret_cast<word *>(sb_smem);
   int32_t *perm    = reinterpret_cast<int32_t *>(sb_smem + (size_t)R * ldw * 8);
@@ -133,7 +178,7 @@ __global__ __launch_bounds__(SB_MAX_THREADS) void sb_block_kernel(const word *A,
         }
       } else if (INV) {
         x = ((i >> 6) == w - wa) ? (word)1 << (i & 63) : 0;
-      } else {
+      } else if (OP == SB_SOLVE) {
         x = gb[(int64_t)i * b_stride + (w - wa)];
         if (w == W - 1) x &= bmask;
       }
@@ -164,7 +209,7 @@ __global__ __launch_bounds__(SB_MAX_THREADS) void sb_block_kernel(const word *A,
     sw_r = sw_p = -1;
     __syncthreads();
     int p = -1;
-    for (int j = rank >> 6; j < nfw; ++j) {
+    for (int j = rank >> 6; j < rfw; ++j) {
       word f = buf[j];
       if (j == (rank >> 6)) f &= ~(word)0 << (rank & 63);
       if (f) {
@@ -205,6 +250,52 @@ __global__ __launch_bounds__(SB_MAX_THREADS) void sb_block_kernel(const word *A,
       else if (i == sw_p) perm[i] = sw_R;
   }
   __syncthreads();
+
+  if (OP == SB_KER) {
+    // The swap rule (file comment): step i moves the column at position i to position p_i, so pos[i] = p_i for i < rank, and a free
+    // column f goes f -> p_f -> p_{p_f} -> ... until its position is >= rank.  A row of R is a single bit (a free column) or the
+    // bits of a row of E at the free columns (a pivot column).
+    int32_t *pos = reinterpret_cast<int32_t *>(pivcols + nfw), *idx = pos + n;
+    for (int c = t; c < n; c += T) {
+      const word pc = pivcols[c >> 6];
+      if ((pc >> (c & 63)) & 1) {
+        int i = __builtin_popcountll(pc & (((word)1 << (c & 63)) - 1));
+        for (int j = 0; j < (c >> 6); ++j) i += __builtin_popcountll(pivcols[j]);
+        pos[i] = c;
+        idx[c] = i;
+      }
+    }
+    __syncthreads();
+    for (int f = t; f < n; f += T) {
+      if (!((pivcols[f >> 6] >> (f & 63)) & 1)) {
+        int q = f;
+        while (q < rank) q = pos[q];
+        pos[q] = f;  // q >= rank: no thread reads it in this loop
+        idx[f] = q - rank;
+      }
+    }
+    __syncthreads();
+    const int wr = (k + 63) >> 6, nb = (n - rank < k) ? n - rank : k;  // nb: the basis columns stored
+    for (int q = t; q < n * wr; q += T) {
+      const int i = q / wr, w = q - i * wr;
+      word x = 0;
+      if ((pivcols[i >> 6] >> (i & 63)) & 1) {
+        const word *er = rows + perm[idx[i]] * ldw;
+        const int je   = (w + 1) * 64 < nb ? (w + 1) * 64 : nb;
+        for (int j = w * 64; j < je; ++j) {
+          const int f = pos[rank + j];
+          x |= ((er[f >> 6] >> (f & 63)) & 1) << (j & 63);
+        }
+      } else if (idx[i] < k && (idx[i] >> 6) == w) {
+        x = (word)1 << (idx[i] & 63);
+      }
+      word *dst = gb + (int64_t)i * b_stride + w;
+      if (w == wr - 1 && bmask != ~(word)0) x = (x & bmask) | (*dst & ~bmask);
+      *dst = x;
+    }
+    if (t == 0) rank_out[b] = rank;
+    return;
+  }
 
   if (INV) {
     const int total = n * wb;
@@ -266,20 +357,24 @@ __global__ __launch_bounds__(SB_MAX_THREADS) void sb_block_kernel(const word *A,
 
 int64_t lds_row_words(int64_t width) { return width + ((width & 1) ^ 1); }  // odd: the flag pass reads one word per row
 
-int64_t lds_bytes_path1(int64_t R, int64_t W) {
-  return R * lds_row_words(W) * 8 + ((R * 4 + 15) & ~(int64_t)15) + 3 * ((R + 63) / 64) * 8;
+// path 1's LDS (sb_block_kernel): R rows of W words, the row index, flags and pivot columns over max(R, n), `tab` int32 entries
+int64_t lds_bytes_path1(int64_t R, int64_t W, int64_t n, int64_t tab) {
+  return R * lds_row_words(W) * 8 + ((R * 4 + 15) & ~(int64_t)15) + 3 * (((R > n ? R : n) + 63) / 64) * 8 + tab * 4;
 }
+
+// the kernel's path 1: m rows of words(n), the swap rule's arrangement and the index table (n entries each)
+int64_t lds_bytes_kernel(int64_t m, int64_t n) { return lds_bytes_path1(m, words_of(n), n, 2 * n); }
 
 int block_threads(int64_t R, int64_t W) { return R * W >= 8192 ? SB_MAX_THREADS : 256; }
 
-template <bool INV>
+template <int OP>
 int launch(const word *A, int64_t a_stride, int64_t a_bs, word *B, int64_t b_stride, int64_t b_bs, int64_t m, int64_t n, int64_t k,
            int64_t batch, int path, int32_t *status, int32_t *rank, hipStream_t st) {
   if (path == 0) {
     const int64_t per = SB_WAVE_THREADS / 64;
     for (int64_t b0 = 0; b0 < batch; b0 += SB_CHUNK * per) {
       const int64_t cnt = (batch - b0 < SB_CHUNK * per) ? batch - b0 : SB_CHUNK * per;
-      hipLaunchKernelGGL(sb_wave_kernel<INV>, dim3((unsigned)((cnt + per - 1) / per)), dim3(SB_WAVE_THREADS), 0, st, A, a_stride, a_bs, B, b_stride,
+      hipLaunchKernelGGL(sb_wave_kernel<OP>, dim3((unsigned)((cnt + per - 1) / per)), dim3(SB_WAVE_THREADS), 0, st, A, a_stride, a_bs, B, b_stride,
                          b_bs, (int)m, (int)n, (int)k, b0, batch, status, rank);
       HIPTRY(hipGetLastError());
     }
@@ -287,14 +382,15 @@ int launch(const word *A, int64_t a_stride, int64_t a_bs, word *B, int64_t b_str
   }
   static std::once_flag once;
   std::call_once(once, [] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(sb_block_kernel<INV>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SB_LDS_BUDGET);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(sb_block_kernel<OP>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SB_LDS_BUDGET);
   });
-  const int64_t R = m > n ? m : n, W = words_of(n) + words_of(k);
+  const bool ker    = OP == SB_KER;
+  const int64_t R   = (ker || m > n) ? m : n, W = words_of(n) + (ker ? 0 : words_of(k));
   const int threads = block_threads(R, W);
-  const size_t lds  = (size_t)lds_bytes_path1(R, W);
+  const size_t lds  = (size_t)(ker ? lds_bytes_kernel(m, n) : lds_bytes_path1(R, W, n, 0));
   for (int64_t b0 = 0; b0 < batch; b0 += SB_CHUNK) {
     const int64_t cnt = (batch - b0 < SB_CHUNK) ? batch - b0 : SB_CHUNK;
-    hipLaunchKernelGGL(sb_block_kernel<INV>, dim3((unsigned)cnt), dim3(threads), lds, st, A, a_stride, a_bs, B, b_stride, b_bs, (int)m, (int)n,
+    hipLaunchKernelGGL(sb_block_kernel<OP>, dim3((unsigned)cnt), dim3(threads), lds, st, A, a_stride, a_bs, B, b_stride, b_bs, (int)m, (int)n,
                        (int)k, (int)lds_row_words(W), b0, status, rank);
     HIPTRY(hipGetLastError());
   }
@@ -395,6 +491,36 @@ int run_path2_inv(word *Binv, int64_t b_stride, int64_t b_bs, const word *A, int
   return rc;
 }
 
+// path 2 of the kernel: per member, m4ri_amd_kernel_left_pluq_dev on a clean copy of A_b (m = 0: one zero row, the same basis)
+// into an n x n scratch basis cleared before each member, whose first kc columns are copied under the mask.
+int run_path2_kernel(const word *A, int64_t a_stride, int64_t a_bs, int64_t m, int64_t n, word *R, int64_t r_stride, int64_t r_bs, int64_t kc,
+                     int64_t batch, int32_t *rank, hipStream_t st) {
+  const int64_t wn = words_of(n), rows = m > 0 ? m : 1;
+  std::vector<int32_t> hr((size_t)batch);
+  word *sA = nullptr, *sR = nullptr;
+  auto run = [&]() -> int {
+    HIPTRY(hipMalloc(reinterpret_cast<void **>(&sA), (size_t)(rows * wn) * 8));
+    HIPTRY(hipMalloc(reinterpret_cast<void **>(&sR), (size_t)(n * wn) * 8));
+    for (int64_t b = 0; b < batch; ++b) {
+      if (m > 0) {
+        if (int rc = clean_copy(sA, wn, A + b * a_bs, a_stride, m, n, st)) return rc;
+      } else {
+        HIPTRY(hipMemsetAsync(sA, 0, (size_t)wn * 8, st));
+      }
+      HIPTRY(hipMemsetAsync(sR, 0, (size_t)(n * wn) * 8, st));
+      if (int rc = m4ri_amd_kernel_left_pluq_dev(sA, wn, rows, n, sR, wn, 0, &hr[(size_t)b], st)) return rc;
+      if (kc > 0) HIPTRY(gf2_launch_copy_masked(st, R + b * r_bs, r_stride, sR, wn, n, kc));
+    }
+    HIPTRY(hipMemcpyAsync(rank, hr.data(), (size_t)batch * 4, hipMemcpyHostToDevice, st));
+    return (int)hipStreamSynchronize(st);
+  };
+  const int rc = run();
+  if (rc) (void)hipStreamSynchronize(st);
+  if (sA) (void)hipFree(sA);
+  if (sR) (void)hipFree(sR);
+  return rc;
+}
+
 }  // namespace
 
 extern "C" {
@@ -405,7 +531,7 @@ int m4ri_amd_plan_solve_batch(int64_t m, int64_t n, int64_t k) {
   if (R <= 64 && k <= 64) return 0;
   const int64_t W = words_of(n) + words_of(k);
   if (R > SB_LDS_BUDGET / 8 || W > SB_LDS_BUDGET / 8) return 2;
-  return lds_bytes_path1(R, W) <= SB_LDS_BUDGET ? 1 : 2;
+  return lds_bytes_path1(R, W, n, 0) <= SB_LDS_BUDGET ? 1 : 2;
 }
 
 int m4ri_amd_solve_left_batch_dev(const word *A, int64_t a_stride, int64_t a_bs, int64_t m, int64_t n, word *B, int64_t b_stride, int64_t b_bs,
@@ -420,7 +546,7 @@ int m4ri_amd_solve_left_batch_dev(const word *A, int64_t a_stride, int64_t a_bs,
   hipStream_t st = (hipStream_t)stream;
   const int path = m4ri_amd_plan_solve_batch(m, n, k);
   if (path == 2) return run_path2_solve(A, a_stride, a_bs, m, n, B, b_stride, b_bs, k, batch, status, rank, st);
-  return launch<false>(A, a_stride, a_bs, B, b_stride, b_bs, m, n, k, batch, path, status, rank, st);
+  return launch<SB_SOLVE>(A, a_stride, a_bs, B, b_stride, b_bs, m, n, k, batch, path, status, rank, st);
 }
 
 int m4ri_amd_inv_batch_dev(word *Binv, int64_t b_stride, int64_t b_bs, const word *A, int64_t a_stride, int64_t a_bs, int64_t n, int64_t batch,
@@ -445,7 +571,37 @@ int m4ri_amd_inv_batch_dev(word *Binv, int64_t b_stride, int64_t b_bs, const wor
   if (n == 0) return rank ? (int)hipMemsetAsync(rank, 0, (size_t)batch * 4, st) : 0;
   const int path = m4ri_amd_plan_solve_batch(n, n, n);
   if (path == 2) return run_path2_inv(Binv, b_stride, b_bs, A, a_stride, a_bs, n, batch, rank, st);
-  return launch<true>(A, a_stride, a_bs, Binv, b_stride, b_bs, n, n, n, batch, path, nullptr, rank, st);
+  return launch<SB_INV>(A, a_stride, a_bs, Binv, b_stride, b_bs, n, n, n, batch, path, nullptr, rank, st);
+}
+
+int m4ri_amd_plan_kernel_batch(int64_t m, int64_t n) {
+  if (m < 0 || n < 0) return -1;
+  if (m <= 64 && n <= 64) return 0;
+  if (m > SB_LDS_BUDGET / 8 || n > SB_LDS_BUDGET / 8) return 2;
+  return lds_bytes_kernel(m, n) <= SB_LDS_BUDGET ? 1 : 2;
+}
+
+int m4ri_amd_kernel_left_batch_dev(const word *A, int64_t a_stride, int64_t a_bs, int64_t m, int64_t n, word *R, int64_t r_stride, int64_t r_bs,
+                                   int64_t kc, int64_t batch, int32_t *rank, void *stream) {
+  if (m < 0 || n < 0 || kc < 0 || batch < 0 || a_stride < 0 || a_bs < 0 || r_stride < 0 || r_bs < 0 || kc > n) return (int)hipErrorInvalidValue;
+  const int64_t wa = words_of(n), wr = words_of(kc);
+  if (a_stride < wa || r_stride < wr) return (int)hipErrorInvalidValue;
+  if (batch > 1 && n > 0 && r_bs < (n - 1) * r_stride + wr) return (int)hipErrorInvalidValue;
+  if (batch > 0 && !rank) return (int)hipErrorInvalidValue;
+  const bool a_data = m > 0 && n > 0, r_data = kc > 0;  // kc <= n
+  if (batch > 0 && ((a_data && !A) || (r_data && !R))) return (int)hipErrorInvalidValue;
+  if (batch > 0 && a_data && r_data) {  // R's span and A's span (first member's start to last member's end) must not meet
+    const uintptr_t ri = (uintptr_t)R, ai = (uintptr_t)A;
+    const uintptr_t rend = ri + (uintptr_t)(((batch - 1) * r_bs + (n - 1) * r_stride + wr) * 8);
+    const uintptr_t aend = ai + (uintptr_t)(((batch - 1) * a_bs + (m - 1) * a_stride + wa) * 8);
+    if (ri < aend && ai < rend) return (int)hipErrorInvalidValue;
+  }
+  if (batch == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  if (n == 0) return (int)hipMemsetAsync(rank, 0, (size_t)batch * 4, st);
+  const int path = m4ri_amd_plan_kernel_batch(m, n);
+  if (path == 2) return run_path2_kernel(A, a_stride, a_bs, m, n, R, r_stride, r_bs, kc, batch, rank, st);
+  return launch<SB_KER>(A, a_stride, a_bs, R, r_stride, r_bs, m, n, kc, batch, path, nullptr, rank, st);
 }
 
 }  // extern "C"
