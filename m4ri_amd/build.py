@@ -17,6 +17,12 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "csrc", "_obj")
 LIB = os.path.join(HERE, "libm4ri_amd.so")
 SOURCES = ["m4rm_leaf.hip", "a4_pack.hip", "m4rm8q_leaf.hip", "m4rm_small.hip", "aux_kernels.hip", "scheme_passes.hip", "engine.hip", "mzd_api.hip", "multi.hip", "trsm.hip", "ple.hip", "elim.hip", "echelon.hip", "echelon_batch.hip", "solve.hip", "solve_batch.hip", "transpose.hip", "io.cpp", "small_host.cpp"]
+# The test-only library of the fused passes (tests/pass_lib.py binds it; it is not API and not part of the product): the objects of the
+# pass sources linked a second time, with the internal launchers the pass tests call as its only exports.  libm4ri_amd.so keeps them local.
+PASS_LIB = os.path.join(HERE, "libm4ri_amd_passes.so")
+PASS_SOURCES = ["aux_kernels.hip", "scheme_passes.hip", "a4_pack.hip"]
+PASS_EXPORTS = ["gf2_launch_pass_down", "gf2_launch_pass_down_pack", "gf2_launch_pass_up", "gf2_pass_down_pack_ok", "gf2_scheme444_rank",
+                "gf2_scheme444_leaves", "gf2_scheme444_ok", "gf2_launch_a4_pack_rot", "gf2_m4rm8_a4_words"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-fvisibility-inlines-hidden"]
 
 
@@ -43,6 +49,16 @@ def export_map() -> str:
     program, so only the declared names leave the .so; everything else is local."""
     path = os.path.join(OBJ, "exports.map")
     text = "{\n  global:\n" + "".join(f"    {n};\n" for n in declared_functions()) + "  local:\n    *;\n};\n"
+    if not os.path.exists(path) or open(path).read() != text:
+        with open(path, "w") as f:
+            f.write(text)
+    return path
+
+
+def pass_export_map() -> str:
+    """Version script of the test-only pass library: just the names tests/pass_lib.py binds."""
+    path = os.path.join(OBJ, "pass_exports.map")
+    text = "{\n  global:\n" + "".join(f"    {n};\n" for n in PASS_EXPORTS) + "  local:\n    *;\n};\n"
     if not os.path.exists(path) or open(path).read() != text:
         with open(path, "w") as f:
             f.write(text)
@@ -81,6 +97,10 @@ def build(force: bool = False, verbose: bool = True) -> str:
     emap = export_map()
     if force or jobs or _stale(LIB, objs + [emap]):
         run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB, *objs, f"-Wl,--version-script={emap}", "-ldl", "-lz"])
+    pobjs = [os.path.join(OBJ, os.path.splitext(s)[0] + ".o") for s in PASS_SOURCES]
+    pmap = pass_export_map()
+    if force or jobs or _stale(PASS_LIB, pobjs + [pmap]):
+        run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", PASS_LIB, *pobjs, f"-Wl,--version-script={pmap}", "-Wl,--no-undefined"])
     return LIB
 
 

@@ -11,7 +11,7 @@
 //     each, 16 KiB) are built straight from registers -- a thread owns one 16-byte slot of four entries of one table and needs that slot of four
 //     rows of B, loaded from global memory one step ahead, under the lookups -- into the OTHER of two table sets, and every row adds its sixteen
 //     entries: 64 ds_read_b128 per row and step, ONE barrier per step (the first version staged the rows in LDS: two barriers, nothing in flight;
-//     2048^3 33.0 -> 30.5 us, 1024 x 1024 x 16384 36.6 -> 30.2, 3 x 100000 x 5000 143 -> 100);
+//     2048^3 33.0 -> 29.8 us, 1024 x 1024 x 16384 36.6 -> 29.9, 3 x 100000 x 5000 143 -> 100);
 //   * entries are stored with their four 16-byte slots XOR-swizzled by (entry >> 2): the sixteen entries of a table then occupy sixteen
 //     different bank positions for every slot number, so lanes with different indices never collide and lanes with equal indices
 //     broadcast -- conflict-free for ANY indices, writes included;

@@ -62,7 +62,29 @@ def _filled(rows, ncols, stride, batch, bs, seed0):
 def test_batched_strassen_products_match_oracle(oracle, m, l, n, batch, cutoff, add):
     wl, wn = (l + 63) // 64, (n + 63) // 64
     sa, sb, sc = wl + 2, wn + (wn & 1), wn + 4
-    abs_, bbs, cbs = m * sa + 6, l * sb, m * sc + 2
+    _batched_strassen_against_oracle(oracle, m, l, n, batch, cutoff, add, sa, sb, sc, m * sa + 6, l * sb, m * sc + 2)
+
+
+@pytest.mark.parametrize("m,l,n,batch,cutoff,add", [
+    (1024, 1024, 1024, 3, 256, 0),        # two levels
+    (2048, 1024, 1536, 2, 256, 1),        # accumulate, rectangular
+    (2048, 2048, 2048, 2, 256, 0),        # three levels
+    (1024, 1024, 1024, 2, 512, 1),        # one level
+])
+def test_batched_strassen_products_with_odd_strides_match_oracle(oracle, m, l, n, batch, cutoff, add):
+    """Odd row strides of A and C and odd batch strides of A and C at a depth >= 1: no operand or result pass of the batch can take its
+    16-byte form (vec_ok in aux_kernels.hip), so the scalar passes run with a batch stride -- the way a caller reaches what
+    test_gpu_passes.py runs directly."""
+    wl, wn = (l + 63) // 64, (n + 63) // 64
+    sa, sb, sc = wl + 1, wn + (wn & 1), wn + 3
+    abs_, cbs = m * sa + 5, m * sc + 1
+    assert sa % 2 == 1 and sc % 2 == 1 and abs_ % 2 == 1 and cbs % 2 == 1
+    _batched_strassen_against_oracle(oracle, m, l, n, batch, cutoff, add, sa, sb, sc, abs_, l * sb, cbs)
+    assert m4ri_amd.get_stats().levels >= 1
+
+
+def _batched_strassen_against_oracle(oracle, m, l, n, batch, cutoff, add, sa, sb, sc, abs_, bbs, cbs):
+    wl, wn = (l + 63) // 64, (n + 63) // 64
     A = [Mzd.random(m, l, 110 + b) for b in range(batch)]
     B = [Mzd.random(l, n, 150 + b) for b in range(batch)]
     C = [Mzd.random(m, n, 190 + b) for b in range(batch)]

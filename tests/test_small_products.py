@@ -93,8 +93,8 @@ def test_entry_points_take_the_host_routine_exactly_when_they_should(oracle):
 
 
 def test_host_routine_fuzz_shapes_and_windows(oracle):
-    """Seeded fuzz of the host routine alone: random shapes around its regimes (at most 8 rows: no tables; 3- to 8-bit tables by the
-    number of rows; one to several column blocks), mul and addmul, operands and result windows of larger parents; every word of C's
+    """Seeded fuzz of the host routine alone: random shapes around its regimes (at most bitwise_rows() = 12 or 24 rows: no tables;
+    3- to 8-bit tables by the number of rows; one to several column blocks), mul and addmul, operands and result windows of larger parents; every word of C's
     parent is compared."""
     import os
     rng = np.random.default_rng(int(os.environ.get("M4RI_AMD_FUZZ_SEED", "20260929")))
