@@ -362,6 +362,50 @@ int m4ri_amd_kernel_left_batch_dev(const word *A, int64_t a_stride, int64_t a_bs
  * words per 64 of max(m, n), two int32 tables of n entries, within 160 KiB: 1024 x 1024 fits); 2 members one by one through
  * m4ri_amd_kernel_left_pluq_dev on scratch copies (blocking) */
 int m4ri_amd_plan_kernel_batch(int64_t m, int64_t n);
+/* `batch` PLE (pluq == 0) or PLUQ (pluq != 0) decompositions in place (ple_batch.hip).  Member b is the nrows x ncols matrix at
+ * A + b * a_bs (words), rows `stride` words apart; it comes out bit-identical to m4ri_amd_ple_dev / m4ri_amd_pluq_dev with
+ * recursion_cutoff = 0 (_mzd_ple_russian / _mzd_pluq_russian).  P (DEVICE int32, batch * nrows entries, member b at b * nrows),
+ * Q (DEVICE int32, batch * ncols entries, member b at b * ncols) and rank (DEVICE int32, batch entries) are all required: the
+ * reference's LAPACK-style transpositions, the identity behind the rank in both.  For every member small enough for paths 0-2
+ * _mzd_ple and _mzd_ple_russian leave the same Q (the recursion of ple.c only starts above M4RI_AMD_PLE_CUTOFF words); path 3 calls
+ * the per-member functions with recursion_cutoff = 0, so its Q is _mzd_ple_russian's as well.
+ * Bits at columns >= ncols of a row's last word, the words from the width to `stride` of a row and the words between members are
+ * never written.  hipErrorInvalidValue, before any HIP call, for negative sizes, strides or batch strides, stride < words(ncols),
+ * overlapping members (batch > 1 and a_bs < (nrows - 1) * stride + words(ncols)), a NULL A with a non-empty member, rank == NULL with
+ * batch > 0, P == NULL with batch * nrows > 0 or Q == NULL with batch * ncols > 0.  batch = 0 succeeds without touching anything;
+ * nrows = 0 or ncols = 0 writes rank 0 and the identity to P and Q and no matrix word.  Asynchronous on `stream` (one launch, no
+ * allocation, no copy, no host synchronisation) on paths 0-2 of m4ri_amd_plan_ple_batch; path 3 allocates and BLOCKS. */
+int m4ri_amd_ple_batch_dev(word *A, int64_t stride, int64_t a_bs, int64_t nrows, int64_t ncols, int64_t batch, int pluq, int32_t *P, int32_t *Q,
+                           int32_t *rank, void *stream);
+/* which path m4ri_amd_ple_batch_dev takes for members of this shape (pure host arithmetic; -1 for negative sizes): 0 one wave per
+ * member, rows, P and Q in registers (nrows, ncols <= 64); 1 one workgroup per member, member in LDS (rows padded to an odd number
+ * of words, a row index, P, Q -- each int32 array rounded up to 16 bytes -- and two flag words per 64 rows, within 160 KiB); 2 one
+ * workgroup per member, in place in global memory (valid words up to 512 KiB); 3 members one by one through m4ri_amd_ple_dev /
+ * m4ri_amd_pluq_dev (blocking) */
+int m4ri_amd_plan_ple_batch(int64_t nrows, int64_t ncols);
+/* `batch` solves A_b X_b = B_b from stored factors (mzd_pluq_solve_left, m4ri/solve.c:57-121; ple_batch.hip).  A_b (m x n at
+ * A + b * a_bs), rank[b], P (member b at b * m) and Q (member b at b * n) are what m4ri_amd_ple_batch_dev(pluq = 1) left; they are
+ * READ ONLY, and only the bits of A_b on the proper side of the diagonal are read.  a_bs = 0: one decomposition (A, rank[0], the
+ * first m entries of P, the first n of Q) serves every member.  B_b: the max(m, n) x k matrix at B + b * b_bs.
+ * The result is that of m4ri_amd_solve_left_batch_dev on the original A_b, byte for byte: status[b] (DEVICE int32, required) is 0,
+ * or -1 when there is no solution, consistency checked over all padding rows; on status 0, B_b holds X in rows 0 .. n-1 with the
+ * rows of the non-pivot columns zero, rows n .. max(m, n)-1 zero; on -1, B_b is left untouched.  So "factor once, solve later" and
+ * "solve in one call" can be exchanged freely.
+ * Bits at columns >= k of a row's last word, the words from the width to the stride of a row, the words between members, A, rank,
+ * P and Q are never written.  hipErrorInvalidValue, before any HIP call, for negative sizes, strides or batch strides, a stride
+ * below the width, overlapping B members (batch > 1 and b_bs < (max(m, n) - 1) * b_stride + words(k)), B overlapping A (the span
+ * from the first member's start to the last member's end of each), status or rank == NULL with batch > 0, P == NULL with
+ * batch * m > 0, Q == NULL with batch * n > 0, or a NULL A or B with a non-empty member.  Asynchronous on `stream` (one launch, no
+ * allocation, no copy) on paths 0 and 1 of m4ri_amd_plan_pluq_solve_batch; path 2 allocates and BLOCKS. */
+int m4ri_amd_pluq_solve_left_batch_dev(const word *A, int64_t a_stride, int64_t a_bs, int64_t m, int64_t n, const int32_t *rank, const int32_t *P,
+                                       const int32_t *Q, word *B, int64_t b_stride, int64_t b_bs, int64_t k, int64_t batch, int32_t *status,
+                                       void *stream);
+/* which path m4ri_amd_pluq_solve_left_batch_dev takes (pure host arithmetic; -1 for negative sizes): 0 one wave per member
+ * (max(m, n) <= 64 and k <= 64); 1 one workgroup per member, B_b in LDS (max(m, n) rows of words(k) words padded to an odd count,
+ * a row index of max(m, n) and a table of min(m, n) int32 entries, each rounded up to 16 bytes, 16 bytes of flags and a word per
+ * row of A, within 160 KiB -- only B is staged, so the boundary lies above m4ri_amd_plan_solve_batch's); 2 members one by one through
+ * m4ri_amd_pluq_solve_left_dev on scratch copies (blocking) */
+int m4ri_amd_plan_pluq_solve_batch(int64_t m, int64_t n, int64_t k);
 int m4ri_amd_apply_p_right_dev(word *A, int64_t stride, int64_t nrows, int64_t ncols, const int32_t *P, int64_t length, int trans, void *stream);
 /* Row r <- its columns under the transpositions (i, Q[i]), i = r+1 .. ncols-1 ascending (mzd_apply_p_right_trans_tri,
  * m4ri/mzp.c:279-293).  Q: HOST array, ncols entries, Q[i] >= i.  Blocking. */

@@ -180,6 +180,10 @@ SYMBOLS = {
     "m4ri_amd_plan_solve_batch": (_I, [_I64, _I64, _I64]),
     "m4ri_amd_kernel_left_batch_dev": (_I, [_P, _I64, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I64, _P, _P]),
     "m4ri_amd_plan_kernel_batch": (_I, [_I64, _I64]),
+    "m4ri_amd_ple_batch_dev": (_I, [_P, _I64, _I64, _I64, _I64, _I64, _I, _P, _P, _P, _P]),
+    "m4ri_amd_plan_ple_batch": (_I, [_I64, _I64]),
+    "m4ri_amd_pluq_solve_left_batch_dev": (_I, [_P, _I64, _I64, _I64, _I64, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _P, _P]),
+    "m4ri_amd_plan_pluq_solve_batch": (_I, [_I64, _I64, _I64]),
     "m4ri_amd_apply_p_right_dev": (_I, [_P, _I64, _I64, _I64, _P, _I64, _I, _P]),
     "m4ri_amd_mzd_init": (MzdPtr, [_I, _I]),
     "m4ri_amd_mzd_free": (None, [MzdPtr]),
@@ -520,6 +524,33 @@ def kernel_left_batch_dev(A: int, a_stride: int, a_bs: int, m: int, n: int, R: i
 def plan_kernel_batch(m: int, n: int) -> int:
     """The path kernel_left_batch_dev takes for m x n members (0 wave, 1 LDS, 2 one by one). Host arithmetic."""
     return int(lib().m4ri_amd_plan_kernel_batch(m, n))
+
+
+def ple_batch_dev(A: int, stride: int, a_bs: int, nrows: int, ncols: int, batch: int, pluq: bool, P: int, Q: int, rank: int,
+                  stream: int = 0) -> None:
+    """`batch` PLE (pluq false) or PLUQ decompositions in place, member b at A + b * a_bs words; P (batch * nrows), Q (batch * ncols) and
+    rank (batch): DEVICE int32 arrays, all required.  Asynchronous on paths 0-2 of plan_ple_batch, blocking on path 3."""
+    _check(lib().m4ri_amd_ple_batch_dev(A, stride, a_bs, nrows, ncols, batch, int(bool(pluq)), P or None, Q or None, rank or None, stream),
+           "m4ri_amd_ple_batch_dev")
+
+
+def plan_ple_batch(nrows: int, ncols: int) -> int:
+    """The path ple_batch_dev takes for members of this shape (0 wave, 1 LDS, 2 global, 3 one by one). Host arithmetic."""
+    return int(lib().m4ri_amd_plan_ple_batch(nrows, ncols))
+
+
+def pluq_solve_left_batch_dev(A: int, a_stride: int, a_bs: int, m: int, n: int, rank: int, P: int, Q: int, B: int, b_stride: int, b_bs: int,
+                              k: int, batch: int, status: int, stream: int = 0) -> None:
+    """`batch` systems A_b X_b = B_b from what ple_batch_dev(pluq=True) left in A, rank, P and Q (read only; a_bs = 0: one decomposition
+    for all), B_b (max(m, n) x k) at B + b * b_bs <- X, exactly as solve_left_batch_dev on the original A; status: DEVICE int32 array
+    (0, or -1 = no solution, B_b untouched).  Asynchronous on paths 0-1 of plan_pluq_solve_batch, blocking on path 2."""
+    _check(lib().m4ri_amd_pluq_solve_left_batch_dev(A, a_stride, a_bs, m, n, rank or None, P or None, Q or None, B, b_stride, b_bs, k, batch,
+                                                    status or None, stream), "m4ri_amd_pluq_solve_left_batch_dev")
+
+
+def plan_pluq_solve_batch(m: int, n: int, k: int) -> int:
+    """The path pluq_solve_left_batch_dev takes for (m, n, k) (0 wave, 1 LDS, 2 one by one). Host arithmetic."""
+    return int(lib().m4ri_amd_plan_pluq_solve_batch(m, n, k))
 
 
 def m4rm_dev(C: int, c_stride: int, A: int, a_stride: int, B: int, b_stride: int, m: int, l: int, n: int,
