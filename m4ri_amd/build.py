@@ -23,6 +23,13 @@ PASS_LIB = os.path.join(HERE, "libm4ri_amd_passes.so")
 PASS_SOURCES = ["aux_kernels.hip", "scheme_passes.hip", "a4_pack.hip"]
 PASS_EXPORTS = ["gf2_launch_pass_down", "gf2_launch_pass_down_pack", "gf2_launch_pass_up", "gf2_pass_down_pack_ok", "gf2_scheme444_rank",
                 "gf2_scheme444_leaves", "gf2_scheme444_ok", "gf2_launch_a4_pack_rot", "gf2_m4rm8_a4_words"]
+# The test-only library of the M4RM leaves (tests/leaf_lib.py binds it; not API, not part of the product), made the same way: the objects of
+# the leaf sources and of the helpers that go with a split launch linked a second time (scheme_passes: what aux_kernels.hip calls), with the
+# launchers tests/test_gpu_leaves.py calls as its only exports.
+LEAF_LIB = os.path.join(HERE, "libm4ri_amd_leaves.so")
+LEAF_SOURCES = ["m4rm_leaf.hip", "a4_pack.hip", "m4rm8q_leaf.hip", "m4rm_small.hip", "aux_kernels.hip", "scheme_passes.hip"]
+LEAF_EXPORTS = ["gf2_launch_m4rm_leaf", "gf2_launch_m4rm_leaf_variant", "gf2_launch_m4rm_small", "gf2_m4rm_small_ksplit", "gf2_m4rm8_a4_words",
+                "gf2_launch_a4_pack_rot", "gf2_m4rm8q_effective_ksplit", "gf2_launch_m4rm8q", "gf2_launch_reduce_partials", "gf2_launch_zero_tiles"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-fvisibility-inlines-hidden"]
 
 
@@ -55,14 +62,23 @@ def export_map() -> str:
     return path
 
 
-def pass_export_map() -> str:
-    """Version script of the test-only pass library: just the names tests/pass_lib.py binds."""
-    path = os.path.join(OBJ, "pass_exports.map")
-    text = "{\n  global:\n" + "".join(f"    {n};\n" for n in PASS_EXPORTS) + "  local:\n    *;\n};\n"
+def _test_export_map(name: str, exports: list[str]) -> str:
+    path = os.path.join(OBJ, name)
+    text = "{\n  global:\n" + "".join(f"    {n};\n" for n in exports) + "  local:\n    *;\n};\n"
     if not os.path.exists(path) or open(path).read() != text:
         with open(path, "w") as f:
             f.write(text)
     return path
+
+
+def pass_export_map() -> str:
+    """Version script of the test-only pass library: just the names tests/pass_lib.py binds."""
+    return _test_export_map("pass_exports.map", PASS_EXPORTS)
+
+
+def leaf_export_map() -> str:
+    """Version script of the test-only leaf library: just the names tests/leaf_lib.py binds."""
+    return _test_export_map("leaf_exports.map", LEAF_EXPORTS)
 
 
 def _stale(target: str, deps: list[str]) -> bool:
@@ -101,6 +117,10 @@ def build(force: bool = False, verbose: bool = True) -> str:
     pmap = pass_export_map()
     if force or jobs or _stale(PASS_LIB, pobjs + [pmap]):
         run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", PASS_LIB, *pobjs, f"-Wl,--version-script={pmap}", "-Wl,--no-undefined"])
+    lobjs = [os.path.join(OBJ, os.path.splitext(s)[0] + ".o") for s in LEAF_SOURCES]
+    lmap = leaf_export_map()
+    if force or jobs or _stale(LEAF_LIB, lobjs + [lmap]):
+        run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LEAF_LIB, *lobjs, f"-Wl,--version-script={lmap}", "-Wl,--no-undefined"])
     return LIB
 
 

@@ -1,8 +1,10 @@
 // gf2_internal.h -- the functions the library's translation units call across files, declared once.
 //
 // Every file that defines one of them includes this header, so the compiler checks each definition against the one
-// declaration here.  C linkage: tools/leaf_check.cpp links the leaf sources directly.  None of these names leaves the
-// shared library (build.py's export map lists only include/m4ri_amd.h).
+// declaration here.  C linkage: tools/leaf_check.cpp links the leaf sources directly, and so do the two test-only
+// libraries of build.py (libm4ri_amd_passes.so for tests/pass_lib.py, libm4ri_amd_leaves.so for tests/leaf_lib.py), which
+// export the launchers their tests call.  None of these names leaves the product's shared library (build.py's export
+// map lists only include/m4ri_amd.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include "gf2_common.h"
