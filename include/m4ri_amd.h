@@ -246,6 +246,27 @@ int m4ri_amd_m4rm_batch_dev(word *C, int64_t c_stride, int64_t c_bs, const word 
  * multi.hip; the sub-products of strassen.c:111-150 are independent).  Bit-identical to `batch` calls of m4ri_amd_mul_dev. */
 int m4ri_amd_mul_batch_dev(word *C, int64_t c_stride, int64_t c_bs, const word *A, int64_t a_stride, int64_t a_bs, const word *B,
                            int64_t b_stride, int64_t b_bs, int64_t m, int64_t l, int64_t n, int64_t batch, int add, int cutoff, void *stream);
+/* `batch` products of TINY matrices of one shape, C_b (+)= A_b * B_b (mul_small_batch.hip): A_b m x l, B_b l x n, C_b m x n, member b
+ * at X + b * x_bs words, rows x_stride words apart.  The valid bits of every C_b are those of m4ri_amd_m4rm_batch_dev (mzd_mul /
+ * mzd_addmul); bits of A at columns >= l and bits of B at columns >= n never influence a valid bit of C.  l = 0 clears the valid
+ * bits of C_b (add == 0) or keeps them (add != 0); m = 0 or n = 0 touches nothing.  a_bs = 0 / b_bs = 0: one A / one B shared by
+ * all members; A and B may overlap each other (A == B squares).  On paths 0 and 1 of m4ri_amd_plan_mul_small_batch, bits at
+ * columns >= n of a row's last word, the words from the width to c_stride of a row, the words between members, A and B are never
+ * written, and the call is asynchronous on `stream`: one launch (several for a batch beyond one grid), no allocation, no copy, no
+ * engine workspace -- so no engine lock and no ordering behind the previous product; capturable.  Path 2 IS the launch of
+ * m4ri_amd_m4rm_batch_dev, with its locking and its contract (whole last words of C included).  hipErrorInvalidValue, before any
+ * HIP call, for negative sizes, strides or batch strides, a_stride < words(l), b_stride < words(n) or c_stride < words(n),
+ * overlapping C members (batch > 1 and c_bs < (m - 1) * c_stride + words(n)), C overlapping A or B (the span from the first
+ * member's start to the last member's end of each), or a NULL pointer with a non-empty member.  batch = 0 succeeds without
+ * touching anything. */
+int m4ri_amd_mul_small_batch_dev(word *C, int64_t c_stride, int64_t c_bs, const word *A, int64_t a_stride, int64_t a_bs, const word *B,
+                                 int64_t b_stride, int64_t b_bs, int64_t m, int64_t l, int64_t n, int64_t batch, int add, void *stream);
+/* which path m4ri_amd_mul_small_batch_dev takes for this (m, l, n) (pure host arithmetic; -1 for negative sizes): 0 one wave per
+ * member, registers and cross-lane broadcasts only (m, l, n <= 64); 1 one wave per 64 x 64 block of C (max(m, l, n) <= the measured
+ * bound D1, a multiple of 64 in [64, 256]; 64 = no such shape); 2 forwarded to m4ri_amd_m4rm_batch_dev.  The environment variable
+ * M4RI_AMD_MUL_SMALL_BATCH_PATH1_MAX (read per call, clamped to [64, 256] in multiples of 64) replaces D1 in the routing of
+ * m4ri_amd_mul_small_batch_dev; this function does not read it. */
+int m4ri_amd_plan_mul_small_batch(int64_t m, int64_t l, int64_t n);
 /* the time model's estimate for `batch` products m x l x n scheduled as one at `levels` levels (pure host arithmetic) */
 double m4ri_amd_model_seconds_batch(int64_t m, int64_t l, int64_t n, int levels, int64_t batch);
 /* C = A ^ B on rows x ncols bits: the device twin of _mzd_add (mzd.c:1471-1583).  In-place allowed,

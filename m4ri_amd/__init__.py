@@ -170,6 +170,8 @@ SYMBOLS = {
     "m4ri_amd_transpose_dev": (_I, [_P, _I64, _P, _I64, _I64, _I64, _P]),
     "m4ri_amd_m4rm_batch_dev": (_I, [_P, _I64, _I64, _P, _I64, _I64, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I, _P]),
     "m4ri_amd_mul_batch_dev": (_I, [_P, _I64, _I64, _P, _I64, _I64, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I, _I, _P]),
+    "m4ri_amd_mul_small_batch_dev": (_I, [_P, _I64, _I64, _P, _I64, _I64, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I, _P]),
+    "m4ri_amd_plan_mul_small_batch": (_I, [_I64, _I64, _I64]),
     "m4ri_amd_model_seconds_batch": (ctypes.c_double, [_I64, _I64, _I64, _I, _I64]),
     "m4ri_amd_trtri_upper_dev": (_I, [_P, _I64, _I64, _P]),
     "m4ri_amd_echelonize_dev": (_I, [_P, _I64, _I64, _I64, _I, _P, _P]),
@@ -471,6 +473,20 @@ def mul_batch_dev(C: int, c_stride: int, c_bs: int, A: int, a_stride: int, a_bs:
     """`batch` products of one shape, X_b = X + b * x_bs words, with the levels of mul_dev and every launch shared by the batch."""
     _check(lib().m4ri_amd_mul_batch_dev(C, c_stride, c_bs, A, a_stride, a_bs, B, b_stride, b_bs, m, l, n, batch, int(add), cutoff, stream),
            "m4ri_amd_mul_batch_dev")
+
+
+def mul_small_batch_dev(C: int, c_stride: int, c_bs: int, A: int, a_stride: int, a_bs: int, B: int, b_stride: int, b_bs: int, m: int, l: int,
+                        n: int, batch: int, add: bool = False, stream: int = 0) -> None:
+    """`batch` products of tiny matrices, C_b (+)= A_b * B_b with X_b = X + b * x_bs words (a_bs = 0 / b_bs = 0: one shared A / B; A == B
+    allowed), only the valid bits of C written.  Asynchronous, lock-free and capturable on paths 0-1 of plan_mul_small_batch; path 2 is
+    m4ri_amd_m4rm_batch_dev's launch."""
+    _check(lib().m4ri_amd_mul_small_batch_dev(C, c_stride, c_bs, A, a_stride, a_bs, B, b_stride, b_bs, m, l, n, batch, int(bool(add)), stream),
+           "m4ri_amd_mul_small_batch_dev")
+
+
+def plan_mul_small_batch(m: int, l: int, n: int) -> int:
+    """The path mul_small_batch_dev takes for (m, l, n) (0 wave per member, 1 wave per 64 x 64 block of C, 2 forwarded). Host arithmetic."""
+    return int(lib().m4ri_amd_plan_mul_small_batch(m, l, n))
 
 
 def model_seconds_batch(m: int, l: int, n: int, levels: int = -1, batch: int = 1) -> float:
