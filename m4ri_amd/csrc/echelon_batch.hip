@@ -6,8 +6,9 @@
 //   0  nrows, ncols <= 64: a wave per member, lane i holds row i; pivot = lowest lane >= rank of a ballot, no LDS, no barrier.
 //   1  the member fits in LDS: a workgroup per member, rows staged in LDS under a row-permutation index (the swap of a column is
 //      two index entries, applied by their owner threads in the next column's flag pass); two barriers per column with a pivot.
-//   2  larger members up to EB_CAP_BYTES: a workgroup per member, rows in place in global memory, rows swapped physically (the last
+//   2  larger members up to BATCH_CAP_BYTES: a workgroup per member, rows in place in global memory, rows swapped physically (the last
 //      word under the column mask); three barriers per column with a pivot.
+//   (Paths 1 and 2 are batch_common.h's workgroup-per-member scheme; the column's pieces are there, the update is here.)
 //   3  above the cap: the members one by one through m4ri_amd_echelonize_dev, then one launch for the pivots.  Blocking.
 // Paths 0-2 are one launch each (plus chunking above 2^30 workgroups), no allocation, no copy, no host synchronisation.
 // Memory rules: bits at columns >= ncols of a row's last word are never changed, nor the words from `width` to `stride` of a row,
@@ -15,23 +16,17 @@
 #include <hip/hip_runtime.h>
 #include <mutex>
 #include <vector>
-#include "gf2_internal.h"
+#include "batch_common.h"
 #include "../../include/m4ri_amd.h"
 
 namespace {
 
-constexpr int EB_WAVE_THREADS   = 256;                 // path 0: four members per workgroup
-constexpr int EB_MAX_THREADS    = 1024;                // paths 1, 2
-constexpr int64_t EB_LDS_BUDGET = 160 * 1024;          // path 1: the whole LDS of a CU
-constexpr int64_t EB_CAP_BYTES  = 512 * 1024;          // path 2: valid words of a member, bytes
-constexpr int64_t EB_CHUNK      = (int64_t)1 << 30;    // workgroups per launch
-
 // path 0: a wave per member, lane i = row i (one word).  Members b0 + 4 * blockIdx.x + wave.
-__global__ __launch_bounds__(EB_WAVE_THREADS) void eb_wave_kernel(word *__restrict__ A, int64_t stride, int64_t a_bs, int nrows, int ncols,
-                                                                  int64_t b0, int64_t batch, int full, int32_t *__restrict__ rank_out,
-                                                                  int32_t *__restrict__ pivots, int mn) {
+__global__ __launch_bounds__(BATCH_WAVE_THREADS) void eb_wave_kernel(word *__restrict__ A, int64_t stride, int64_t a_bs, int nrows, int ncols,
+                                                                     int64_t b0, int64_t batch, int full, int32_t *__restrict__ rank_out,
+                                                                     int32_t *__restrict__ pivots, int mn) {
   const int lane  = threadIdx.x & 63;
-  const int64_t b = b0 + (int64_t)blockIdx.x * (EB_WAVE_THREADS / 64) + (threadIdx.x >> 6);
+  const int64_t b = b0 + (int64_t)blockIdx.x * (BATCH_WAVE_THREADS / 64) + (threadIdx.x >> 6);
   if (b >= batch) return;  // wave-uniform, no barrier in this kernel
   word *g          = A + b * a_bs;
   const word mask  = tail_mask(ncols);
@@ -67,11 +62,11 @@ __global__ __launch_bounds__(EB_WAVE_THREADS) void eb_wave_kernel(word *__restri
 //   else:  flags [2][nfw] words
 // Row i of the flag pass is owned by thread i % blockDim.x (the lane of its ballot); flags[c & 1] bit i = bit c of logical row i.
 template <bool INLDS>
-__global__ __launch_bounds__(EB_MAX_THREADS) void eb_block_kernel(word *__restrict__ A, int64_t stride, int64_t a_bs, int nrows, int ncols,
-                                                                  int ldw, int64_t b0, int full, int32_t *__restrict__ rank_out,
-                                                                  int32_t *__restrict__ pivots, int mn) {
+__global__ __launch_bounds__(BATCH_MAX_THREADS) void eb_block_kernel(word *__restrict__ A, int64_t stride, int64_t a_bs, int nrows, int ncols,
+                                                                     int ldw, int64_t b0, int full, int32_t *__restrict__ rank_out,
+                                                                     int32_t *__restrict__ pivots, int mn) {
   extern __shared__ __attribute__((aligned(16))) char eb_smem[];
-  const int T = blockDim.x, t = threadIdx.x, lane = t & 63;
+  const int T = blockDim.x, t = threadIdx.x;
   const int64_t b  = b0 + blockIdx.x;
   word *g          = A + b * a_bs;
   const int width  = (ncols + 63) >> 6;
@@ -79,124 +74,57 @@ __global__ __launch_bounds__(EB_MAX_THREADS) void eb_block_kernel(word *__restri
   const word mask  = tail_mask(ncols);
   word *rows       = reinterpret_cast<word *>(eb_smem);
   int32_t *perm    = reinterpret_cast<int32_t *>(eb_smem + (INLDS ? (size_t)nrows * ldw * 8 : 0));
-  word *flags      = reinterpret_cast<word *>(eb_smem + (INLDS ? (size_t)nrows * ldw * 8 + (((size_t)nrows * 4 + 15) & ~(size_t)15) : 0));
+  word *flags      = reinterpret_cast<word *>(eb_smem + (INLDS ? (size_t)nrows * ldw * 8 + pad16((size_t)nrows * 4) : 0));
 
   if (INLDS) {
-    const int total = nrows * width;
-    for (int k = t; k < total; k += T) {
-      const int i = k / width, w = k - i * width;
-      word x = g[(int64_t)i * stride + w];
-      if (w == width - 1) x &= mask;
-      rows[i * ldw + w] = x;
-    }
+    stage_rows_in(rows, ldw, g, stride, nrows, width, mask, t, T);
     for (int i = t; i < nrows; i += T) perm[i] = i;
     __syncthreads();
   }
 
   int rank = 0;
-  int sw_r = -1, sw_p = -1, sw_R = 0, sw_P = 0;  // INLDS: the previous column's pending swap of perm[rank] and perm[p]
+  PendingSwap sw;  // INLDS: the previous column's pending swap of perm[rank] and perm[p]
   for (int c = 0; c < ncols && rank < nrows; ++c) {
     word *buf    = flags + (c & 1) * nfw;
     const int cw = c >> 6, cb = c & 63;
-    // flag pass: each thread its own rows (and, INLDS, their index entries)
-    for (int base = t - lane; base < nrows; base += T) {
-      const int i = base + lane;
-      int bit     = 0;
-      if (i < nrows) {
-        word x;
-        if (INLDS) {
-          int ph = (i == sw_r) ? sw_P : (i == sw_p) ? sw_R : perm[i];
-          if (i == sw_r || i == sw_p) perm[i] = ph;
-          x = rows[ph * ldw + cw];
-        } else {
-          x = g[(int64_t)i * stride + cw];
-        }
-        bit = (int)((x >> cb) & 1);
-      }
-      const word bal = __ballot(bit);
-      if (lane == 0) buf[base >> 6] = bal;
-    }
-    sw_r = sw_p = -1;
+    if (INLDS) flag_pass<true>(buf, rows, ldw, perm, sw, nrows, cw, cb, t, T);
+    else flag_pass<false>(buf, g, stride, perm, sw, nrows, cw, cb, t, T);
     __syncthreads();
-    int p = -1;
-    for (int j = rank >> 6; j < nfw; ++j) {
-      word f = buf[j];
-      if (j == (rank >> 6)) f &= ~(word)0 << (rank & 63);
-      if (f) {
-        p = j * 64 + (int)__builtin_ctzll(f);
-        break;
-      }
-    }
+    const int p = find_pivot(buf, rank, nfw);
     if (p < 0) continue;  // no writes this column; the next flag pass uses the other buffer
     if (t == 0 && pivots) pivots[b * mn + rank] = c;
-    const int nw = width - cw;
     const word *prow;
     if (INLDS) {
       const int P = perm[p];
       prow        = rows + P * ldw;
-      if (p != rank) {
-        sw_r = rank; sw_p = p; sw_P = P; sw_R = perm[rank];
-      }
+      sw.record(perm, rank, p, P);
     } else {
       if (p != rank) {  // physical swap, the bits behind ncols stay where they are
-        word *rp = g + (int64_t)rank * stride, *pp = g + (int64_t)p * stride;
-        for (int w = cw + t; w < width; w += T) {
-          const word x = rp[w], y = pp[w];
-          if (w == width - 1) {
-            rp[w] = (y & mask) | (x & ~mask);
-            pp[w] = (x & mask) | (y & ~mask);
-          } else {
-            rp[w] = y;
-            pp[w] = x;
-          }
-        }
+        swap_rows_global(g + (int64_t)rank * stride, g + (int64_t)p * stride, cw, width, mask, t, T);
         __syncthreads();
       }
       prow = g + (int64_t)rank * stride;
     }
     // the update: flagged rows i != p (row `rank` is unflagged when p != rank), below the rank only unless full.
-    // Item k = (i, w) with k = i * nw + (w - cw), k = t, t + T, ...: advanced by (qi, qw) without a division per item.
-    {
-      const int qi = T / nw, qw = T - qi * nw;
-      int i = t / nw, w = cw + (t - (t / nw) * nw);
-      while (i < nrows) {
-        const int f = (int)((buf[i >> 6] >> (i & 63)) & 1);
-        if (f && i != p && (full || i > rank)) {
-          word x = prow[w];
-          if (INLDS) {
-            rows[perm[i] * ldw + w] ^= x;
-          } else {
-            if (w == width - 1) x &= mask;
-            g[(int64_t)i * stride + w] ^= x;
-          }
-        }
-        i += qi;
-        w += qw;
-        if (w >= width) {
-          w -= nw;
-          ++i;
+    for_each_item(0, nrows, cw, width, t, T, [&](int i, int w) {
+      if (flag_of(buf, i) && i != p && (full || i > rank)) {
+        word x = prow[w];
+        if (INLDS) {
+          rows[perm[i] * ldw + w] ^= x;
+        } else {
+          if (w == width - 1) x &= mask;
+          g[(int64_t)i * stride + w] ^= x;
         }
       }
-    }
+    });
     ++rank;
     __syncthreads();
   }
 
   if (INLDS) {
-    if (sw_r >= 0) {  // the last column's swap (its owners only, as in the flag pass)
-      for (int i = t; i < nrows; i += T)
-        if (i == sw_r) perm[i] = sw_P;
-        else if (i == sw_p) perm[i] = sw_R;
-    }
+    sw.finish(perm, nrows, t, T);
     __syncthreads();
-    const int total = nrows * width;
-    for (int k = t; k < total; k += T) {
-      const int i = k / width, w = k - i * width;
-      word x      = rows[perm[i] * ldw + w];
-      word *dst   = g + (int64_t)i * stride + w;
-      if (w == width - 1 && mask != ~(word)0) x = (x & mask) | (*dst & ~mask);
-      *dst = x;
-    }
+    store_rows_out(g, stride, rows, ldw, perm, nrows, width, mask, t, T);
   }
   if (pivots)
     for (int i = rank + t; i < mn; i += T) pivots[b * mn + i] = -1;
@@ -247,49 +175,37 @@ __global__ __launch_bounds__(256) void eb_pivots_kernel(const word *__restrict__
   if (lane == 0) pivots[k] = piv;
 }
 
-int64_t lds_row_words(int64_t width) { return width + ((width & 1) ^ 1); }  // odd: the flag pass reads one word per row
-
 int64_t lds_bytes_path1(int64_t nrows, int64_t width) {
-  return nrows * lds_row_words(width) * 8 + ((nrows * 4 + 15) & ~(int64_t)15) + 2 * ((nrows + 63) / 64) * 8;
+  return nrows * lds_row_words(width) * 8 + (int64_t)pad16((size_t)nrows * 4) + 2 * ((nrows + 63) / 64) * 8;
 }
-
-int block_threads(int64_t nrows, int64_t width) { return nrows * width >= 8192 ? EB_MAX_THREADS : 256; }
 
 int run_path3(word *A, int64_t stride, int64_t a_bs, int64_t nrows, int64_t ncols, int64_t batch, int full, int32_t *rank, int32_t *pivots,
               hipStream_t st) {
   const int64_t width = words_of(ncols), mn = nrows < ncols ? nrows : ncols;
-  const word mask     = (ncols & 63) ? (((word)1 << (ncols & 63)) - 1) : ~(word)0;
+  const word mask     = tail_mask((int)(ncols & 63));
   const int64_t total = batch * nrows;
   word *save          = nullptr;
   std::vector<int32_t> ranks((size_t)batch);
-  auto run = [&]() -> int {
-    if (ncols & 63) {
-      HIPTRY(hipMalloc(reinterpret_cast<void **>(&save), (size_t)total * 8));
-      hipLaunchKernelGGL(eb_tail_save_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, A, stride, a_bs, nrows, width, mask, total, save);
-      HIPTRY(hipGetLastError());
-    }
-    for (int64_t b = 0; b < batch; ++b)
-      if (int rc = m4ri_amd_echelonize_dev(A + b * a_bs, stride, nrows, ncols, full, &ranks[(size_t)b], st)) return rc;
-    if (save) {
-      hipLaunchKernelGGL(eb_tail_restore_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, A, stride, a_bs, nrows, width, mask, total,
-                         save);
-      HIPTRY(hipGetLastError());
-    }
-    HIPTRY(hipMemcpyAsync(rank, ranks.data(), (size_t)batch * 4, hipMemcpyHostToDevice, st));
-    if (pivots) {
-      const int64_t rows = batch * mn;
-      hipLaunchKernelGGL(eb_pivots_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, A, stride, a_bs, width, mask, mn, rows, rank, pivots);
-      HIPTRY(hipGetLastError());
-    }
-    HIPTRY(hipStreamSynchronize(st));
-    return 0;
-  };
-  const int rc = run();
-  if (save) {
-    if (rc) (void)hipStreamSynchronize(st);
-    (void)hipFree(save);
+  Scratch scratch(st);
+  if (ncols & 63) {
+    HIPTRY(scratch.words(&save, total));
+    hipLaunchKernelGGL(eb_tail_save_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, A, stride, a_bs, nrows, width, mask, total, save);
+    HIPTRY(hipGetLastError());
   }
-  return rc;
+  for (int64_t b = 0; b < batch; ++b)
+    if (int rc = m4ri_amd_echelonize_dev(A + b * a_bs, stride, nrows, ncols, full, &ranks[(size_t)b], st)) return rc;
+  if (save) {
+    hipLaunchKernelGGL(eb_tail_restore_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, A, stride, a_bs, nrows, width, mask, total, save);
+    HIPTRY(hipGetLastError());
+  }
+  HIPTRY(hipMemcpyAsync(rank, ranks.data(), (size_t)batch * 4, hipMemcpyHostToDevice, st));
+  if (pivots) {
+    const int64_t rows = batch * mn;
+    hipLaunchKernelGGL(eb_pivots_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, A, stride, a_bs, width, mask, mn, rows, rank, pivots);
+    HIPTRY(hipGetLastError());
+  }
+  HIPTRY(hipStreamSynchronize(st));
+  return scratch.done();
 }
 
 }  // namespace
@@ -300,8 +216,8 @@ int m4ri_amd_plan_echelonize_batch(int64_t nrows, int64_t ncols) {
   if (nrows < 0 || ncols < 0) return -1;
   if (nrows <= 64 && ncols <= 64) return 0;
   const int64_t width = words_of(ncols);
-  if (nrows > EB_CAP_BYTES / 8 || width > EB_CAP_BYTES / 8 || nrows * width > EB_CAP_BYTES / 8) return 3;
-  return lds_bytes_path1(nrows, width) <= EB_LDS_BUDGET ? 1 : 2;
+  if (nrows > BATCH_CAP_BYTES / 8 || width > BATCH_CAP_BYTES / 8 || nrows * width > BATCH_CAP_BYTES / 8) return 3;
+  return lds_bytes_path1(nrows, width) <= BATCH_LDS_BUDGET ? 1 : 2;
 }
 
 int m4ri_amd_echelonize_batch_dev(word *A, int64_t stride, int64_t a_bs, int64_t nrows, int64_t ncols, int64_t batch, int full, int32_t *rank,
@@ -318,14 +234,11 @@ int m4ri_amd_echelonize_batch_dev(word *A, int64_t stride, int64_t a_bs, int64_t
   const int mn   = (int)(nrows < ncols ? nrows : ncols);
   const int path = m4ri_amd_plan_echelonize_batch(nrows, ncols);
   if (path == 0) {
-    const int64_t per = EB_WAVE_THREADS / 64;
-    for (int64_t b0 = 0; b0 < batch; b0 += EB_CHUNK * per) {
-      const int64_t n = (batch - b0 < EB_CHUNK * per) ? batch - b0 : EB_CHUNK * per;
-      hipLaunchKernelGGL(eb_wave_kernel, dim3((unsigned)((n + per - 1) / per)), dim3(EB_WAVE_THREADS), 0, st, A, stride, a_bs, (int)nrows, (int)ncols,
+    const int64_t per = BATCH_WAVE_THREADS / 64;
+    return launch_chunked(batch, BATCH_CHUNK * per, [&](int64_t b0, int64_t n) {
+      hipLaunchKernelGGL(eb_wave_kernel, dim3((unsigned)((n + per - 1) / per)), dim3(BATCH_WAVE_THREADS), 0, st, A, stride, a_bs, (int)nrows, (int)ncols,
                          b0, batch, full, rank, pivots, mn);
-      HIPTRY(hipGetLastError());
-    }
-    return 0;
+    });
   }
   if (path == 3) return run_path3(A, stride, a_bs, nrows, ncols, batch, full, rank, pivots, st);
   const bool inlds   = path == 1;
@@ -334,20 +247,17 @@ int m4ri_amd_echelonize_batch_dev(word *A, int64_t stride, int64_t a_bs, int64_t
   const size_t lds   = inlds ? (size_t)lds_bytes_path1(nrows, width) : (size_t)(2 * ((nrows + 63) / 64) * 8);
   static std::once_flag once;
   std::call_once(once, [] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(eb_block_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)EB_LDS_BUDGET);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(eb_block_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)EB_LDS_BUDGET);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(eb_block_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)BATCH_LDS_BUDGET);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(eb_block_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)BATCH_LDS_BUDGET);
   });
-  for (int64_t b0 = 0; b0 < batch; b0 += EB_CHUNK) {
-    const int64_t n = (batch - b0 < EB_CHUNK) ? batch - b0 : EB_CHUNK;
+  return launch_chunked(batch, BATCH_CHUNK, [&](int64_t b0, int64_t n) {
     if (inlds)
       hipLaunchKernelGGL(eb_block_kernel<true>, dim3((unsigned)n), dim3(threads), lds, st, A, stride, a_bs, (int)nrows, (int)ncols, ldw, b0, full, rank,
                          pivots, mn);
     else
       hipLaunchKernelGGL(eb_block_kernel<false>, dim3((unsigned)n), dim3(threads), lds, st, A, stride, a_bs, (int)nrows, (int)ncols, ldw, b0, full, rank,
                          pivots, mn);
-    HIPTRY(hipGetLastError());
-  }
-  return 0;
+  });
 }
 
 }  // extern "C"

@@ -1,4 +1,4 @@
-// gf2_internal.h -- the functions the library's translation units call across files, declared once.
+// gf2_internal.h -- the functions the library's translation units call across files, declared once (and the HIPTRY macro they return errors with).
 //
 // Every file that defines one of them includes this header, so the compiler checks each definition against the one
 // declaration here.  C linkage: tools/leaf_check.cpp links the leaf sources directly, and so do the two test-only
@@ -15,17 +15,6 @@
     hipError_t e_ = (hipError_t)(expr);               \
     if (e_ != hipSuccess) return (int)e_;             \
   } while (0)
-
-// ---- device helpers of the batched eliminations (echelon_batch.hip, solve_batch.hip) -------------------------------------------
-// lane `lane`'s 64-bit x (wave-uniform lane)
-__device__ __forceinline__ word readlane64(word x, int lane) {
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)x, lane);
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(x >> 32), lane);
-  return ((word)hi << 32) | lo;
-}
-
-// the valid bits of a row's last word
-__device__ __forceinline__ word tail_mask(int ncols) { return (ncols & 63) ? (((word)1 << (ncols & 63)) - 1) : ~(word)0; }
 
 extern "C" {
 

@@ -14,13 +14,12 @@
 // Paths 0 and 1 are plain launches on the caller's stream: no allocation, no copy, no engine workspace, hence no engine lock.
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
-#include "gf2_internal.h"
+#include "batch_common.h"
 #include "../../include/m4ri_amd.h"
 
 namespace {
 
-constexpr int MSB_THREADS   = 256;                 // four waves = four members (path 0) or four blocks of C (path 1)
-constexpr int64_t MSB_CHUNK = (int64_t)1 << 30;    // workgroups per launch
+// (a workgroup is BATCH_WAVE_THREADS threads: four waves = four members (path 0) or four blocks of C (path 1))
 // Path 1 up to this max(m, l, n); a multiple of 64 in [64, 256], 64 = path 1 empty.  Measured (tools/bench_mul_small_batch.py,
 // profiles/mul_small_batch_bench.txt): on operands of 256 MB path 1 beats m4ri_amd_m4rm_batch_dev 10.7x / 6.6x / 3.8x
 // on the cubes of 128 / 192 / 256 with spreads under 1 %, so the bound is the largest candidate.  (At a thousand members the old
@@ -62,11 +61,11 @@ __device__ __forceinline__ void fold64(uint32_t &clo, uint32_t &chi, word a, wor
 
 // path 0: a wave per member.  Members b0 + 4 * blockIdx.x + wave.
 template <bool HI>
-__global__ __launch_bounds__(MSB_THREADS) void msb_wave_kernel(word *__restrict__ C, int64_t c_stride, int64_t c_bs, const word *A, int64_t a_stride,
-                                                               int64_t a_bs, const word *B, int64_t b_stride, int64_t b_bs, int m, int l, int n,
-                                                               int64_t b0, int64_t batch, int add) {
+__global__ __launch_bounds__(BATCH_WAVE_THREADS) void msb_wave_kernel(word *__restrict__ C, int64_t c_stride, int64_t c_bs, const word *A, int64_t a_stride,
+                                                                      int64_t a_bs, const word *B, int64_t b_stride, int64_t b_bs, int m, int l, int n,
+                                                                      int64_t b0, int64_t batch, int add) {
   const int lane  = threadIdx.x & 63;
-  const int64_t b = b0 + (int64_t)blockIdx.x * (MSB_THREADS / 64) + (threadIdx.x >> 6);
+  const int64_t b = b0 + (int64_t)blockIdx.x * (BATCH_WAVE_THREADS / 64) + (threadIdx.x >> 6);
   if (b >= batch) return;  // wave-uniform, no barrier in this kernel
   const word mask = tail_mask(n);
   const bool old  = add || (n & 63);  // the old word of C: to accumulate into, or for the bits beyond the last column
@@ -83,11 +82,11 @@ __global__ __launch_bounds__(MSB_THREADS) void msb_wave_kernel(word *__restrict_
 
 // path 1: a wave per 64 x 64 block of C.  Block t = 4 * blockIdx.x + wave of the launch is member b0 + t / (mb * wn), row block
 // (t / wn) % mb, word column t % wn; the four blocks of a workgroup may belong to different members.
-__global__ __launch_bounds__(MSB_THREADS) void msb_block_kernel(word *__restrict__ C, int64_t c_stride, int64_t c_bs, const word *A, int64_t a_stride,
-                                                                int64_t a_bs, const word *B, int64_t b_stride, int64_t b_bs, int m, int l, int n,
-                                                                int mb, int wn, int64_t b0, int64_t batch, int add) {
+__global__ __launch_bounds__(BATCH_WAVE_THREADS) void msb_block_kernel(word *__restrict__ C, int64_t c_stride, int64_t c_bs, const word *A, int64_t a_stride,
+                                                                       int64_t a_bs, const word *B, int64_t b_stride, int64_t b_bs, int m, int l, int n,
+                                                                       int mb, int wn, int64_t b0, int64_t batch, int add) {
   const int lane    = threadIdx.x & 63;
-  const uint32_t t  = blockIdx.x * (uint32_t)(MSB_THREADS / 64) + (threadIdx.x >> 6);
+  const uint32_t t  = blockIdx.x * (uint32_t)(BATCH_WAVE_THREADS / 64) + (threadIdx.x >> 6);
   const uint32_t per = (uint32_t)(mb * wn);
   const int64_t b   = b0 + (int64_t)(t / per);
   if (b >= batch) return;  // wave-uniform, no barrier in this kernel
@@ -137,9 +136,6 @@ int plan(int64_t m, int64_t l, int64_t n, int64_t d1) {
   return mx <= 64 ? 0 : mx <= d1 ? 1 : 2;
 }
 
-// do [p, p + pn) and [q, q + qn) (bytes) meet?
-bool spans_meet(uintptr_t p, uintptr_t pn, uintptr_t q, uintptr_t qn) { return p < q + qn && q < p + pn; }
-
 }  // namespace
 
 extern "C" {
@@ -156,40 +152,32 @@ int m4ri_amd_mul_small_batch_dev(word *C, int64_t c_stride, int64_t c_bs, const 
   const bool c_data = m > 0 && n > 0, a_data = m > 0 && l > 0, b_data = l > 0 && n > 0;
   if (batch > 0 && ((c_data && !C) || (a_data && !A) || (b_data && !B))) return (int)hipErrorInvalidValue;
   if (batch > 0 && c_data) {  // C's span (first member's start to last member's end) must not meet A's or B's
-    const uintptr_t cn = (uintptr_t)(((batch - 1) * c_bs + (m - 1) * c_stride + wn) * 8);
-    if (a_data && spans_meet((uintptr_t)C, cn, (uintptr_t)A, (uintptr_t)(((batch - 1) * a_bs + (m - 1) * a_stride + wl) * 8)))
-      return (int)hipErrorInvalidValue;
-    if (b_data && spans_meet((uintptr_t)C, cn, (uintptr_t)B, (uintptr_t)(((batch - 1) * b_bs + (l - 1) * b_stride + wn) * 8)))
-      return (int)hipErrorInvalidValue;
+    const uintptr_t cn = member_span_bytes(batch, c_bs, m, c_stride, wn);
+    if (a_data && spans_meet(C, cn, A, member_span_bytes(batch, a_bs, m, a_stride, wl))) return (int)hipErrorInvalidValue;
+    if (b_data && spans_meet(C, cn, B, member_span_bytes(batch, b_bs, l, b_stride, wn))) return (int)hipErrorInvalidValue;
   }
   if (batch == 0 || m == 0 || n == 0) return 0;
   const int path = plan(m, l, n, path1_max());
   if (path == 2) return m4ri_amd_m4rm_batch_dev(C, c_stride, c_bs, A, a_stride, a_bs, B, b_stride, b_bs, m, l, n, batch, add, stream);
   hipStream_t st    = (hipStream_t)stream;
-  const int64_t per = MSB_THREADS / 64;
+  const int64_t per = BATCH_WAVE_THREADS / 64;
   if (path == 0) {
-    for (int64_t b0 = 0; b0 < batch; b0 += MSB_CHUNK * per) {
-      const int64_t nb  = (batch - b0 < MSB_CHUNK * per) ? batch - b0 : MSB_CHUNK * per;
+    return launch_chunked(batch, BATCH_CHUNK * per, [&](int64_t b0, int64_t nb) {
       const dim3 grid((unsigned)((nb + per - 1) / per));
       if (n > 32)
-        hipLaunchKernelGGL(msb_wave_kernel<true>, grid, dim3(MSB_THREADS), 0, st, C, c_stride, c_bs, A, a_stride, a_bs, B, b_stride, b_bs, (int)m, (int)l,
+        hipLaunchKernelGGL(msb_wave_kernel<true>, grid, dim3(BATCH_WAVE_THREADS), 0, st, C, c_stride, c_bs, A, a_stride, a_bs, B, b_stride, b_bs, (int)m, (int)l,
                            (int)n, b0, batch, add != 0);
       else
-        hipLaunchKernelGGL(msb_wave_kernel<false>, grid, dim3(MSB_THREADS), 0, st, C, c_stride, c_bs, A, a_stride, a_bs, B, b_stride, b_bs, (int)m, (int)l,
+        hipLaunchKernelGGL(msb_wave_kernel<false>, grid, dim3(BATCH_WAVE_THREADS), 0, st, C, c_stride, c_bs, A, a_stride, a_bs, B, b_stride, b_bs, (int)m, (int)l,
                            (int)n, b0, batch, add != 0);
-      HIPTRY(hipGetLastError());
-    }
-    return 0;
+    });
   }
   const int64_t mb = (m + 63) / 64, blocks = mb * wn;       // waves per member: at most 16
-  const int64_t members = MSB_CHUNK * per / blocks;         // members per launch
-  for (int64_t b0 = 0; b0 < batch; b0 += members) {
-    const int64_t nb = (batch - b0 < members) ? batch - b0 : members;
-    hipLaunchKernelGGL(msb_block_kernel, dim3((unsigned)((nb * blocks + per - 1) / per)), dim3(MSB_THREADS), 0, st, C, c_stride, c_bs, A, a_stride, a_bs,
+  const int64_t members = BATCH_CHUNK * per / blocks;         // members per launch
+  return launch_chunked(batch, members, [&](int64_t b0, int64_t nb) {
+    hipLaunchKernelGGL(msb_block_kernel, dim3((unsigned)((nb * blocks + per - 1) / per)), dim3(BATCH_WAVE_THREADS), 0, st, C, c_stride, c_bs, A, a_stride, a_bs,
                        B, b_stride, b_bs, (int)m, (int)l, (int)n, (int)mb, (int)wn, b0, batch, add != 0);
-    HIPTRY(hipGetLastError());
-  }
-  return 0;
+  });
 }
 
 }  // extern "C"

@@ -9,9 +9,9 @@
 // rank, so together with the compression every row takes the swaps j = 0 .. rank - 1.  The paths (m4ri_amd_plan_ple_batch):
 //   0  nrows, ncols <= 64: a wave per member, lane i holds row i, lane t entry t of P and of Q; pivot = lowest lane >= rank of a
 //      ballot; the compression is a wave-uniform loop over j of bit swaps predicated on the lane.  No LDS, no barrier.
-//   1  the member fits in LDS: a workgroup per member, rows staged in LDS under a row-permutation index as echelon_batch.hip's path 1,
+//   1  the member fits in LDS: a workgroup per member, rows staged in LDS under a row-permutation index (batch_common.h's scheme),
 //      P and Q beside them; two barriers per column with a pivot; the compression is a loop of bit swaps per row, a thread per row.
-//   2  larger members up to PB_CAP_BYTES: a workgroup per member, rows in place in global memory, whole rows swapped physically (the
+//   2  larger members up to BATCH_CAP_BYTES: a workgroup per member, rows in place in global memory, whole rows swapped physically (the
 //      last word under the column mask), P and Q written straight to the output; three barriers per column with a pivot.
 //   3  above the cap: the members one by one through m4ri_amd_ple_dev / m4ri_amd_pluq_dev (recursion_cutoff = 0) on a scratch copy,
 //      then P, Q and rank in one copy each.  Blocking.
@@ -31,16 +31,10 @@
 #include <hip/hip_runtime.h>
 #include <mutex>
 #include <vector>
-#include "gf2_internal.h"
+#include "batch_common.h"
 #include "../../include/m4ri_amd.h"
 
 namespace {
-
-constexpr int PB_WAVE_THREADS   = 256;                 // path 0: four members per workgroup
-constexpr int PB_MAX_THREADS    = 1024;                // the workgroup paths
-constexpr int64_t PB_LDS_BUDGET = 160 * 1024;          // path 1: the whole LDS of a CU
-constexpr int64_t PB_CAP_BYTES  = 512 * 1024;          // path 2 of the decomposition: valid words of a member, bytes
-constexpr int64_t PB_CHUNK      = (int64_t)1 << 30;    // workgroups per launch
 
 __device__ __forceinline__ word swap_bits(word v, int a, int b) {  // bits a and b of v exchanged
   const word x = ((v >> a) ^ (v >> b)) & 1;
@@ -59,11 +53,11 @@ __device__ __forceinline__ void swap_cols(word *row, int a, int b) {
 // ---- the decomposition ----------------------------------------------------------------------------------------------------------
 
 // path 0: a wave per member, lane i = row i (one word), lane t = P[t] and Q[t].  Members b0 + 4 * blockIdx.x + wave.
-__global__ __launch_bounds__(PB_WAVE_THREADS) void pb_wave_kernel(word *__restrict__ A, int64_t stride, int64_t a_bs, int nrows, int ncols,
-                                                                  int64_t b0, int64_t batch, int pluq, int32_t *__restrict__ P,
-                                                                  int32_t *__restrict__ Q, int32_t *__restrict__ rank_out) {
+__global__ __launch_bounds__(BATCH_WAVE_THREADS) void pb_wave_kernel(word *__restrict__ A, int64_t stride, int64_t a_bs, int nrows, int ncols,
+                                                                     int64_t b0, int64_t batch, int pluq, int32_t *__restrict__ P,
+                                                                     int32_t *__restrict__ Q, int32_t *__restrict__ rank_out) {
   const int lane  = threadIdx.x & 63;
-  const int64_t b = b0 + (int64_t)blockIdx.x * (PB_WAVE_THREADS / 64) + (threadIdx.x >> 6);
+  const int64_t b = b0 + (int64_t)blockIdx.x * (BATCH_WAVE_THREADS / 64) + (threadIdx.x >> 6);
   if (b >= batch) return;  // wave-uniform, no barrier in this kernel
   word *g         = A + b * a_bs;
   const word mask = tail_mask(ncols);
@@ -103,18 +97,16 @@ __global__ __launch_bounds__(PB_WAVE_THREADS) void pb_wave_kernel(word *__restri
   if (lane == 0) rank_out[b] = rank;
 }
 
-__host__ __device__ inline size_t pad16(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
-
 // paths 1 (INLDS) and 2: a workgroup per member.  Dynamic LDS (16-byte carve offsets):
 //   INLDS: rows [nrows][ldw] words | perm [nrows] int32 | P [nrows] int32 | Q [ncols] int32 (each rounded up to 16 B) | flags [2][nfw] words
 //   else:  flags [2][nfw] words; P and Q are the output arrays
 // Row i of the flag pass is owned by thread i % blockDim.x (the lane of its ballot); flags[c & 1] bit i = bit c of logical row i.
 template <bool INLDS>
-__global__ __launch_bounds__(PB_MAX_THREADS) void pb_block_kernel(word *__restrict__ A, int64_t stride, int64_t a_bs, int nrows, int ncols,
-                                                                  int ldw, int64_t b0, int pluq, int32_t *__restrict__ P_out,
-                                                                  int32_t *__restrict__ Q_out, int32_t *__restrict__ rank_out) {
+__global__ __launch_bounds__(BATCH_MAX_THREADS) void pb_block_kernel(word *__restrict__ A, int64_t stride, int64_t a_bs, int nrows, int ncols,
+                                                                     int ldw, int64_t b0, int pluq, int32_t *__restrict__ P_out,
+                                                                     int32_t *__restrict__ Q_out, int32_t *__restrict__ rank_out) {
   extern __shared__ __attribute__((aligned(16))) char pb_smem[];
-  const int T = blockDim.x, t = threadIdx.x, lane = t & 63;
+  const int T = blockDim.x, t = threadIdx.x;
   const int64_t b = b0 + blockIdx.x;
   word *g         = A + b * a_bs;
   const int width = (ncols + 63) >> 6;
@@ -132,13 +124,7 @@ __global__ __launch_bounds__(PB_MAX_THREADS) void pb_block_kernel(word *__restri
   word *flags = reinterpret_cast<word *>(pb_smem + off);
 
   if (INLDS) {
-    const int total = nrows * width;
-    for (int k = t; k < total; k += T) {
-      const int i = k / width, w = k - i * width;
-      word x = g[(int64_t)i * stride + w];
-      if (w == width - 1) x &= mask;
-      rows[i * ldw + w] = x;
-    }
+    stage_rows_in(rows, ldw, g, stride, nrows, width, mask, t, T);
     for (int i = t; i < nrows; i += T) perm[i] = i;
   }
   for (int i = t; i < nrows; i += T) Pv[i] = i;
@@ -146,39 +132,14 @@ __global__ __launch_bounds__(PB_MAX_THREADS) void pb_block_kernel(word *__restri
   __syncthreads();
 
   int rank = 0;
-  int sw_r = -1, sw_p = -1, sw_R = 0, sw_P = 0;  // INLDS: the previous column's pending swap of perm[rank] and perm[p]
+  PendingSwap sw;  // INLDS: the previous column's pending swap of perm[rank] and perm[p]
   for (int c = 0; c < ncols && rank < nrows; ++c) {
     word *buf    = flags + (c & 1) * nfw;
     const int cw = c >> 6, cb = c & 63;
-    // flag pass: each thread its own rows (and, INLDS, their index entries)
-    for (int base = t - lane; base < nrows; base += T) {
-      const int i = base + lane;
-      int bit     = 0;
-      if (i < nrows) {
-        word x;
-        if (INLDS) {
-          int ph = (i == sw_r) ? sw_P : (i == sw_p) ? sw_R : perm[i];
-          if (i == sw_r || i == sw_p) perm[i] = ph;
-          x = rows[ph * ldw + cw];
-        } else {
-          x = g[(int64_t)i * stride + cw];
-        }
-        bit = (int)((x >> cb) & 1);
-      }
-      const word bal = __ballot(bit);
-      if (lane == 0) buf[base >> 6] = bal;
-    }
-    sw_r = sw_p = -1;
+    if (INLDS) flag_pass<true>(buf, rows, ldw, perm, sw, nrows, cw, cb, t, T);
+    else flag_pass<false>(buf, g, stride, perm, sw, nrows, cw, cb, t, T);
     __syncthreads();
-    int p = -1;
-    for (int j = rank >> 6; j < nfw; ++j) {
-      word f = buf[j];
-      if (j == (rank >> 6)) f &= ~(word)0 << (rank & 63);
-      if (f) {
-        p = j * 64 + (int)__builtin_ctzll(f);
-        break;
-      }
-    }
+    const int p = find_pivot(buf, rank, nfw);
     if (p < 0) continue;  // no writes this column; the next flag pass uses the other buffer
     if (t == 0) {
       Pv[rank] = p;
@@ -188,63 +149,34 @@ __global__ __launch_bounds__(PB_MAX_THREADS) void pb_block_kernel(word *__restri
     if (INLDS) {
       const int Pp = perm[p];
       prow         = rows + Pp * ldw;
-      if (p != rank) {
-        sw_r = rank; sw_p = p; sw_P = Pp; sw_R = perm[rank];
-      }
+      sw.record(perm, rank, p, Pp);
     } else {
       if (p != rank) {  // physical swap of the whole rows (the multipliers to the left move too), the bits behind ncols stay
-        word *rp = g + (int64_t)rank * stride, *pp = g + (int64_t)p * stride;
-        for (int w = t; w < width; w += T) {
-          const word x = rp[w], y = pp[w];
-          if (w == width - 1) {
-            rp[w] = (y & mask) | (x & ~mask);
-            pp[w] = (x & mask) | (y & ~mask);
-          } else {
-            rp[w] = y;
-            pp[w] = x;
-          }
-        }
+        swap_rows_global(g + (int64_t)rank * stride, g + (int64_t)p * stride, 0, width, mask, t, T);
         __syncthreads();
       }
       prow = g + (int64_t)rank * stride;
     }
     // the update: flagged rows i > rank, i != p (row p holds the old row `rank`, which had no bit c), columns c + 1 .. ncols - 1.
-    // Item k = (i, w) with k = (i - rank - 1) * nw + (w - cw), k = t, t + T, ...: advanced by (qi, qw) without a division per item.
-    {
-      const word first = cb < 63 ? ~(word)0 << (cb + 1) : 0;
-      const int nw = width - cw;
-      const int qi = T / nw, qw = T - qi * nw;
-      int i = rank + 1 + t / nw, w = cw + (t - (t / nw) * nw);
-      while (i < nrows) {
-        const int f = (int)((buf[i >> 6] >> (i & 63)) & 1);
-        if (f && i != p) {
-          word x = prow[w];
-          if (w == cw) x &= first;
-          if (INLDS) {
-            rows[perm[i] * ldw + w] ^= x;
-          } else {
-            if (w == width - 1) x &= mask;
-            g[(int64_t)i * stride + w] ^= x;
-          }
-        }
-        i += qi;
-        w += qw;
-        if (w >= width) {
-          w -= nw;
-          ++i;
+    const word first = cb < 63 ? ~(word)0 << (cb + 1) : 0;
+    for_each_item(rank + 1, nrows, cw, width, t, T, [&](int i, int w) {
+      if (flag_of(buf, i) && i != p) {
+        word x = prow[w];
+        if (w == cw) x &= first;
+        if (INLDS) {
+          rows[perm[i] * ldw + w] ^= x;
+        } else {
+          if (w == width - 1) x &= mask;
+          g[(int64_t)i * stride + w] ^= x;
         }
       }
-    }
+    });
     ++rank;
     __syncthreads();
   }
 
   if (INLDS) {
-    if (sw_r >= 0) {  // the last column's swap (its owners only, as in the flag pass)
-      for (int i = t; i < nrows; i += T)
-        if (i == sw_r) perm[i] = sw_P;
-        else if (i == sw_p) perm[i] = sw_R;
-    }
+    sw.finish(perm, nrows, t, T);
     __syncthreads();
   }
   // L to the left (and PLUQ's column step): a thread per row, the swaps in order.  Path 2 pays up to `rank` uncoalesced global
@@ -259,14 +191,7 @@ __global__ __launch_bounds__(PB_MAX_THREADS) void pb_block_kernel(word *__restri
   }
   if (INLDS) {
     __syncthreads();
-    const int total = nrows * width;
-    for (int k = t; k < total; k += T) {
-      const int i = k / width, w = k - i * width;
-      word x      = rows[perm[i] * ldw + w];
-      word *dst   = g + (int64_t)i * stride + w;
-      if (w == width - 1 && mask != ~(word)0) x = (x & mask) | (*dst & ~mask);
-      *dst = x;
-    }
+    store_rows_out(g, stride, rows, ldw, perm, nrows, width, mask, t, T);
     for (int i = t; i < nrows; i += T) Pg[i] = Pv[i];
     for (int j = t; j < ncols; j += T) Qg[j] = Qv[j];
   }
@@ -276,7 +201,7 @@ __global__ __launch_bounds__(PB_MAX_THREADS) void pb_block_kernel(word *__restri
 // nrows == 0 or ncols == 0: rank 0, P and Q the identity
 __global__ void pb_identity_kernel(int32_t *__restrict__ P, int64_t nrows, int32_t *__restrict__ Q, int64_t ncols, int32_t *__restrict__ rank,
                                    int64_t batch) {
-  const int64_t step = (int64_t)gridDim.x * blockDim.x;  // grid-stride: the grid is capped at PB_CHUNK workgroups
+  const int64_t step = (int64_t)gridDim.x * blockDim.x;  // grid-stride: the grid is capped at BATCH_CHUNK workgroups
   for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < batch * nrows || k < batch * ncols || k < batch; k += step) {
     if (k < batch * nrows) P[k] = (int32_t)(k % nrows);
     if (k < batch * ncols) Q[k] = (int32_t)(k % ncols);
@@ -284,20 +209,9 @@ __global__ void pb_identity_kernel(int32_t *__restrict__ P, int64_t nrows, int32
   }
 }
 
-int64_t lds_row_words(int64_t width) { return width + ((width & 1) ^ 1); }  // odd: the flag pass reads one word per row
-
 int64_t lds_bytes_ple(int64_t nrows, int64_t ncols) {
   return nrows * lds_row_words(words_of(ncols)) * 8 + 2 * (int64_t)pad16((size_t)nrows * 4) + (int64_t)pad16((size_t)ncols * 4) +
          2 * ((nrows + 63) / 64) * 8;
-}
-
-int block_threads(int64_t rows, int64_t width) { return rows * width >= 8192 ? PB_MAX_THREADS : 256; }
-
-// a clean copy (tail bits zero) of the rows x ncols matrix at src into scratch
-int clean_copy(word *dst, int64_t dst_stride, const word *src, int64_t src_stride, int64_t rows, int64_t ncols, hipStream_t st) {
-  HIPTRY(hipMemsetAsync(dst, 0, (size_t)(rows * dst_stride) * 8, st));
-  HIPTRY(gf2_launch_copy_masked(st, dst, dst_stride, src, src_stride, rows, ncols));
-  return 0;
 }
 
 int run_ple_path3(word *A, int64_t stride, int64_t a_bs, int64_t nrows, int64_t ncols, int64_t batch, int pluq, int32_t *P, int32_t *Q,
@@ -305,26 +219,21 @@ int run_ple_path3(word *A, int64_t stride, int64_t a_bs, int64_t nrows, int64_t 
   const int64_t width = words_of(ncols);
   std::vector<int32_t> hp((size_t)(batch * nrows)), hq((size_t)(batch * ncols)), hr((size_t)batch);
   word *s = nullptr;
-  auto run = [&]() -> int {
-    HIPTRY(hipMalloc(reinterpret_cast<void **>(&s), (size_t)(nrows * width) * 8));
-    for (int64_t b = 0; b < batch; ++b) {
-      word *Ab = A + b * a_bs;
-      if (int rc = clean_copy(s, width, Ab, stride, nrows, ncols, st)) return rc;
-      int32_t *p = &hp[(size_t)(b * nrows)], *q = &hq[(size_t)(b * ncols)];
-      if (int rc = pluq ? m4ri_amd_pluq_dev(s, width, nrows, ncols, p, q, &hr[(size_t)b], 0, st)
-                        : m4ri_amd_ple_dev(s, width, nrows, ncols, p, q, &hr[(size_t)b], 0, st))
-        return rc;
-      HIPTRY(gf2_launch_copy_masked(st, Ab, stride, s, width, nrows, ncols));
-    }
-    HIPTRY(hipMemcpyAsync(P, hp.data(), hp.size() * 4, hipMemcpyHostToDevice, st));
-    HIPTRY(hipMemcpyAsync(Q, hq.data(), hq.size() * 4, hipMemcpyHostToDevice, st));
-    HIPTRY(hipMemcpyAsync(rank, hr.data(), hr.size() * 4, hipMemcpyHostToDevice, st));
-    return (int)hipStreamSynchronize(st);
-  };
-  const int rc = run();
-  if (rc) (void)hipStreamSynchronize(st);
-  if (s) (void)hipFree(s);
-  return rc;
+  Scratch scratch(st);
+  HIPTRY(scratch.words(&s, nrows * width));
+  for (int64_t b = 0; b < batch; ++b) {
+    word *Ab = A + b * a_bs;
+    HIPTRY(clean_copy(s, width, Ab, stride, nrows, ncols, st));
+    int32_t *p = &hp[(size_t)(b * nrows)], *q = &hq[(size_t)(b * ncols)];
+    HIPTRY(pluq ? m4ri_amd_pluq_dev(s, width, nrows, ncols, p, q, &hr[(size_t)b], 0, st)
+                : m4ri_amd_ple_dev(s, width, nrows, ncols, p, q, &hr[(size_t)b], 0, st));
+    HIPTRY(gf2_launch_copy_masked(st, Ab, stride, s, width, nrows, ncols));
+  }
+  HIPTRY(hipMemcpyAsync(P, hp.data(), hp.size() * 4, hipMemcpyHostToDevice, st));
+  HIPTRY(hipMemcpyAsync(Q, hq.data(), hq.size() * 4, hipMemcpyHostToDevice, st));
+  HIPTRY(hipMemcpyAsync(rank, hr.data(), hr.size() * 4, hipMemcpyHostToDevice, st));
+  HIPTRY(hipStreamSynchronize(st));
+  return scratch.done();
 }
 
 // ---- the solve from the factors -------------------------------------------------------------------------------------------------
@@ -336,12 +245,12 @@ __device__ __forceinline__ int clamp_rank(int r, int m, int n) {
 
 // path 0: a wave per member, lane i = row i of B (x) and of A (a), lane t = P[t] and Q[t].  fb: the member whose decomposition is
 // used (0 when one serves all).
-__global__ __launch_bounds__(PB_WAVE_THREADS) void ps_wave_kernel(const word *__restrict__ A, int64_t a_stride, int64_t a_bs, int m, int n,
-                                                                  const int32_t *__restrict__ rank_in, const int32_t *__restrict__ P,
-                                                                  const int32_t *__restrict__ Q, word *__restrict__ B, int64_t b_stride,
-                                                                  int64_t b_bs, int k, int64_t b0, int64_t batch, int32_t *__restrict__ status) {
+__global__ __launch_bounds__(BATCH_WAVE_THREADS) void ps_wave_kernel(const word *__restrict__ A, int64_t a_stride, int64_t a_bs, int m, int n,
+                                                                     const int32_t *__restrict__ rank_in, const int32_t *__restrict__ P,
+                                                                     const int32_t *__restrict__ Q, word *__restrict__ B, int64_t b_stride,
+                                                                     int64_t b_bs, int k, int64_t b0, int64_t batch, int32_t *__restrict__ status) {
   const int lane  = threadIdx.x & 63;
-  const int64_t b = b0 + (int64_t)blockIdx.x * (PB_WAVE_THREADS / 64) + (threadIdx.x >> 6);
+  const int64_t b = b0 + (int64_t)blockIdx.x * (BATCH_WAVE_THREADS / 64) + (threadIdx.x >> 6);
   if (b >= batch) return;  // wave-uniform, no barrier in this kernel
   const int64_t fb = a_bs ? b : 0;
   const int R      = m > n ? m : n;
@@ -396,10 +305,10 @@ __global__ __launch_bounds__(PB_WAVE_THREADS) void ps_wave_kernel(const word *__
 //   first `rank` entries (each rounded up to 16 B) | two flag words | acol [m] words: the word of A's rows that holds the 64 columns
 //   being applied, fetched once per 64 columns (a row of A is a cache line apart from the next: re-read per column it is the
 //   kernel's whole memory traffic, 16 times over)
-__global__ __launch_bounds__(PB_MAX_THREADS) void ps_block_kernel(const word *__restrict__ A, int64_t a_stride, int64_t a_bs, int m, int n,
-                                                                  const int32_t *__restrict__ rank_in, const int32_t *__restrict__ P,
-                                                                  const int32_t *__restrict__ Q, word *__restrict__ B, int64_t b_stride,
-                                                                  int64_t b_bs, int k, int ldw, int64_t b0, int32_t *__restrict__ status) {
+__global__ __launch_bounds__(BATCH_MAX_THREADS) void ps_block_kernel(const word *__restrict__ A, int64_t a_stride, int64_t a_bs, int m, int n,
+                                                                     const int32_t *__restrict__ rank_in, const int32_t *__restrict__ P,
+                                                                     const int32_t *__restrict__ Q, word *__restrict__ B, int64_t b_stride,
+                                                                     int64_t b_bs, int k, int ldw, int64_t b0, int32_t *__restrict__ status) {
   extern __shared__ __attribute__((aligned(16))) char ps_smem[];
   const int T = blockDim.x, t = threadIdx.x, lane = t & 63;
   const int64_t b  = b0 + blockIdx.x;
@@ -417,12 +326,7 @@ __global__ __launch_bounds__(PB_MAX_THREADS) void ps_block_kernel(const word *__
   word *acol       = flag + 2;
 
   const int total = R * wb;
-  for (int q = t; q < total; q += T) {
-    const int i = q / wb, w = q - i * wb;
-    word x = gb[(int64_t)i * b_stride + w];
-    if (w == wb - 1) x &= bmask;
-    rows[i * ldw + w] = x;
-  }
+  stage_rows_in(rows, ldw, gb, b_stride, R, wb, bmask, t, T);
   for (int i = t; i < R; i += T) idx[i] = i;
   for (int i = t; i < rank; i += T) pq[i] = P[fb * m + i];
   if (t == 0) *flag = 0;
@@ -488,10 +392,7 @@ __global__ __launch_bounds__(PB_MAX_THREADS) void ps_block_kernel(const word *__
     __syncthreads();
     for (int q = t; q < total; q += T) {
       const int i = q / wb, w = q - i * wb;
-      word x      = idx[i] < 0 ? 0 : rows[idx[i] * ldw + w];
-      word *dst   = gb + (int64_t)i * b_stride + w;
-      if (w == wb - 1 && bmask != ~(word)0) x = (x & bmask) | (*dst & ~bmask);
-      *dst = x;
+      store_masked(gb + (int64_t)i * b_stride + w, idx[i] < 0 ? 0 : rows[idx[i] * ldw + w], w == wb - 1, bmask);
     }
   }
   if (t == 0) status[b] = bad ? -1 : 0;
@@ -502,24 +403,6 @@ int64_t lds_bytes_solve(int64_t m, int64_t n, int64_t k) {
   return R * lds_row_words(words_of(k)) * 8 + (int64_t)pad16((size_t)R * 4) + (int64_t)pad16((size_t)mn * 4) + 16 + m * 8;
 }
 
-// path 2 helper: are rows r0 .. r1-1 of the k-column matrix at M (stride words) all zero?  Copies them to the host.  Blocking.
-int rows_zero(const word *M, int64_t stride, int64_t r0, int64_t r1, int64_t k, hipStream_t st, bool *zero) {
-  *zero = true;
-  const int64_t w = words_of(k);
-  if (r1 <= r0 || w == 0) return 0;
-  std::vector<word> h((size_t)((r1 - r0) * w));
-  HIPTRY(hipMemcpy2DAsync(h.data(), (size_t)w * 8, M + r0 * stride, (size_t)stride * 8, (size_t)w * 8, (size_t)(r1 - r0), hipMemcpyDeviceToHost, st));
-  HIPTRY(hipStreamSynchronize(st));
-  const word mask = (k & 63) ? (((word)1 << (k & 63)) - 1) : ~(word)0;
-  for (int64_t i = 0; i < r1 - r0; ++i)
-    for (int64_t j = 0; j < w; ++j)
-      if (h[(size_t)(i * w + j)] & (j == w - 1 ? mask : ~(word)0)) {
-        *zero = false;
-        return 0;
-      }
-  return 0;
-}
-
 // path 2: rank, P and Q to the host once; per member B's padding rows m .. R-1 checked, then m4ri_amd_pluq_solve_left_dev with the
 // check on clean copies of A_b (once when shared) and B_b, and X copied back only when it exists.  (R > 64 or k > 64 here, so k > 0.)
 int run_solve_path2(const word *A, int64_t a_stride, int64_t a_bs, int64_t m, int64_t n, const int32_t *rank, const int32_t *P, const int32_t *Q,
@@ -527,38 +410,32 @@ int run_solve_path2(const word *A, int64_t a_stride, int64_t a_bs, int64_t m, in
   const int64_t R = m > n ? m : n, mn = m < n ? m : n, wa = words_of(n), wb = words_of(k), nf = a_bs ? batch : 1;
   std::vector<int32_t> hs((size_t)batch), hr((size_t)nf), hp((size_t)(nf * m)), hq((size_t)(nf * n));
   word *sA = nullptr, *sB = nullptr;
-  auto run = [&]() -> int {
-    HIPTRY(hipMemcpyAsync(hr.data(), rank, hr.size() * 4, hipMemcpyDeviceToHost, st));
-    if (!hp.empty()) HIPTRY(hipMemcpyAsync(hp.data(), P, hp.size() * 4, hipMemcpyDeviceToHost, st));
-    if (!hq.empty()) HIPTRY(hipMemcpyAsync(hq.data(), Q, hq.size() * 4, hipMemcpyDeviceToHost, st));
-    HIPTRY(hipStreamSynchronize(st));
-    if (mn > 0) HIPTRY(hipMalloc(reinterpret_cast<void **>(&sA), (size_t)(m * wa) * 8));
-    HIPTRY(hipMalloc(reinterpret_cast<void **>(&sB), (size_t)(R * wb) * 8));
-    for (int64_t b = 0; b < batch; ++b) {
-      const int64_t fb = a_bs ? b : 0;
-      word *Bb         = B + b * b_bs;
-      int32_t r        = hr[(size_t)fb];
-      r                = r < 0 ? 0 : r > mn ? (int32_t)mn : r;
-      bool zero        = true;
-      if (int rc = rows_zero(Bb, b_stride, mn > 0 ? m : 0, R, k, st, &zero)) return rc;  // A empty: every row of B
-      int ret = zero ? 0 : -1;
-      if (ret == 0 && mn > 0) {
-        if (b == 0 || a_bs)
-          if (int rc = clean_copy(sA, wa, A + b * a_bs, a_stride, m, n, st)) return rc;
-        if (int rc = clean_copy(sB, wb, Bb, b_stride, R, k, st)) return rc;
-        if (int rc = m4ri_amd_pluq_solve_left_dev(sA, wa, m, n, r, &hp[(size_t)(fb * m)], &hq[(size_t)(fb * n)], sB, wb, R, k, 0, 1, &ret, st)) return rc;
-        if (ret == 0) HIPTRY(gf2_launch_copy_masked(st, Bb, b_stride, sB, wb, R, k));
-      }
-      hs[(size_t)b] = ret;
+  Scratch scratch(st);
+  HIPTRY(hipMemcpyAsync(hr.data(), rank, hr.size() * 4, hipMemcpyDeviceToHost, st));
+  if (!hp.empty()) HIPTRY(hipMemcpyAsync(hp.data(), P, hp.size() * 4, hipMemcpyDeviceToHost, st));
+  if (!hq.empty()) HIPTRY(hipMemcpyAsync(hq.data(), Q, hq.size() * 4, hipMemcpyDeviceToHost, st));
+  HIPTRY(hipStreamSynchronize(st));
+  if (mn > 0) HIPTRY(scratch.words(&sA, m * wa));
+  HIPTRY(scratch.words(&sB, R * wb));
+  for (int64_t b = 0; b < batch; ++b) {
+    const int64_t fb = a_bs ? b : 0;
+    word *Bb         = B + b * b_bs;
+    int32_t r        = hr[(size_t)fb];
+    r                = r < 0 ? 0 : r > mn ? (int32_t)mn : r;
+    bool zero        = true;
+    HIPTRY(rows_zero(Bb, b_stride, mn > 0 ? m : 0, R, k, st, &zero));  // A empty: every row of B
+    int ret = zero ? 0 : -1;
+    if (ret == 0 && mn > 0) {
+      if (b == 0 || a_bs) HIPTRY(clean_copy(sA, wa, A + b * a_bs, a_stride, m, n, st));
+      HIPTRY(clean_copy(sB, wb, Bb, b_stride, R, k, st));
+      HIPTRY(m4ri_amd_pluq_solve_left_dev(sA, wa, m, n, r, &hp[(size_t)(fb * m)], &hq[(size_t)(fb * n)], sB, wb, R, k, 0, 1, &ret, st));
+      if (ret == 0) HIPTRY(gf2_launch_copy_masked(st, Bb, b_stride, sB, wb, R, k));
     }
-    HIPTRY(hipMemcpyAsync(status, hs.data(), (size_t)batch * 4, hipMemcpyHostToDevice, st));
-    return (int)hipStreamSynchronize(st);
-  };
-  const int rc = run();
-  if (rc) (void)hipStreamSynchronize(st);
-  if (sA) (void)hipFree(sA);
-  if (sB) (void)hipFree(sB);
-  return rc;
+    hs[(size_t)b] = ret;
+  }
+  HIPTRY(hipMemcpyAsync(status, hs.data(), (size_t)batch * 4, hipMemcpyHostToDevice, st));
+  HIPTRY(hipStreamSynchronize(st));
+  return scratch.done();
 }
 
 }  // namespace
@@ -569,8 +446,8 @@ int m4ri_amd_plan_ple_batch(int64_t nrows, int64_t ncols) {
   if (nrows < 0 || ncols < 0) return -1;
   if (nrows <= 64 && ncols <= 64) return 0;
   const int64_t width = words_of(ncols);
-  if (nrows > PB_CAP_BYTES / 8 || width > PB_CAP_BYTES / 8 || nrows * width > PB_CAP_BYTES / 8) return 3;
-  return lds_bytes_ple(nrows, ncols) <= PB_LDS_BUDGET ? 1 : 2;
+  if (nrows > BATCH_CAP_BYTES / 8 || width > BATCH_CAP_BYTES / 8 || nrows * width > BATCH_CAP_BYTES / 8) return 3;
+  return lds_bytes_ple(nrows, ncols) <= BATCH_LDS_BUDGET ? 1 : 2;
 }
 
 int m4ri_amd_ple_batch_dev(word *A, int64_t stride, int64_t a_bs, int64_t nrows, int64_t ncols, int64_t batch, int pluq, int32_t *P, int32_t *Q,
@@ -585,19 +462,16 @@ int m4ri_amd_ple_batch_dev(word *A, int64_t stride, int64_t a_bs, int64_t nrows,
   hipStream_t st = (hipStream_t)stream;
   if (nrows == 0 || ncols == 0) {
     const int64_t total = batch * (nrows > ncols ? nrows : ncols > 0 ? ncols : 1), blocks = (total + 255) / 256;
-    hipLaunchKernelGGL(pb_identity_kernel, dim3((unsigned)(blocks < PB_CHUNK ? blocks : PB_CHUNK)), dim3(256), 0, st, P, nrows, Q, ncols, rank, batch);
+    hipLaunchKernelGGL(pb_identity_kernel, dim3((unsigned)(blocks < BATCH_CHUNK ? blocks : BATCH_CHUNK)), dim3(256), 0, st, P, nrows, Q, ncols, rank, batch);
     return (int)hipGetLastError();
   }
   const int path = m4ri_amd_plan_ple_batch(nrows, ncols);
   if (path == 0) {
-    const int64_t per = PB_WAVE_THREADS / 64;
-    for (int64_t b0 = 0; b0 < batch; b0 += PB_CHUNK * per) {
-      const int64_t n = (batch - b0 < PB_CHUNK * per) ? batch - b0 : PB_CHUNK * per;
-      hipLaunchKernelGGL(pb_wave_kernel, dim3((unsigned)((n + per - 1) / per)), dim3(PB_WAVE_THREADS), 0, st, A, stride, a_bs, (int)nrows, (int)ncols,
+    const int64_t per = BATCH_WAVE_THREADS / 64;
+    return launch_chunked(batch, BATCH_CHUNK * per, [&](int64_t b0, int64_t n) {
+      hipLaunchKernelGGL(pb_wave_kernel, dim3((unsigned)((n + per - 1) / per)), dim3(BATCH_WAVE_THREADS), 0, st, A, stride, a_bs, (int)nrows, (int)ncols,
                          b0, batch, pluq, P, Q, rank);
-      HIPTRY(hipGetLastError());
-    }
-    return 0;
+    });
   }
   if (path == 3) return run_ple_path3(A, stride, a_bs, nrows, ncols, batch, pluq, P, Q, rank, st);
   const bool inlds  = path == 1;
@@ -606,28 +480,25 @@ int m4ri_amd_ple_batch_dev(word *A, int64_t stride, int64_t a_bs, int64_t nrows,
   const size_t lds  = inlds ? (size_t)lds_bytes_ple(nrows, ncols) : (size_t)(2 * ((nrows + 63) / 64) * 8);
   static std::once_flag once;
   std::call_once(once, [] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(pb_block_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)PB_LDS_BUDGET);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(pb_block_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)PB_LDS_BUDGET);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(pb_block_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)BATCH_LDS_BUDGET);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(pb_block_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)BATCH_LDS_BUDGET);
   });
-  for (int64_t b0 = 0; b0 < batch; b0 += PB_CHUNK) {
-    const int64_t n = (batch - b0 < PB_CHUNK) ? batch - b0 : PB_CHUNK;
+  return launch_chunked(batch, BATCH_CHUNK, [&](int64_t b0, int64_t n) {
     if (inlds)
       hipLaunchKernelGGL(pb_block_kernel<true>, dim3((unsigned)n), dim3(threads), lds, st, A, stride, a_bs, (int)nrows, (int)ncols, ldw, b0, pluq, P, Q,
                          rank);
     else
       hipLaunchKernelGGL(pb_block_kernel<false>, dim3((unsigned)n), dim3(threads), lds, st, A, stride, a_bs, (int)nrows, (int)ncols, ldw, b0, pluq, P, Q,
                          rank);
-    HIPTRY(hipGetLastError());
-  }
-  return 0;
+  });
 }
 
 int m4ri_amd_plan_pluq_solve_batch(int64_t m, int64_t n, int64_t k) {
   if (m < 0 || n < 0 || k < 0) return -1;
   const int64_t R = m > n ? m : n;
   if (R <= 64 && k <= 64) return 0;
-  if (R > PB_LDS_BUDGET / 8 || words_of(k) > PB_LDS_BUDGET / 8) return 2;
-  return lds_bytes_solve(m, n, k) <= PB_LDS_BUDGET ? 1 : 2;
+  if (R > BATCH_LDS_BUDGET / 8 || words_of(k) > BATCH_LDS_BUDGET / 8) return 2;
+  return lds_bytes_solve(m, n, k) <= BATCH_LDS_BUDGET ? 1 : 2;
 }
 
 int m4ri_amd_pluq_solve_left_batch_dev(const word *A, int64_t a_stride, int64_t a_bs, int64_t m, int64_t n, const int32_t *rank, const int32_t *P,
@@ -640,40 +511,32 @@ int m4ri_amd_pluq_solve_left_batch_dev(const word *A, int64_t a_stride, int64_t 
   if (batch > 0 && (!status || !rank || (m > 0 && !P) || (n > 0 && !Q))) return (int)hipErrorInvalidValue;
   const bool a_data = m > 0 && n > 0, b_data = R > 0 && k > 0;
   if (batch > 0 && ((a_data && !A) || (b_data && !B))) return (int)hipErrorInvalidValue;
-  if (batch > 0 && a_data && b_data) {  // B's span and A's span (first member's start to last member's end) must not meet
-    const uintptr_t bi = (uintptr_t)B, ai = (uintptr_t)A;
-    const uintptr_t bend = bi + (uintptr_t)(((batch - 1) * b_bs + (R - 1) * b_stride + wb) * 8);
-    const uintptr_t aend = ai + (uintptr_t)(((batch - 1) * a_bs + (m - 1) * a_stride + wa) * 8);
-    if (bi < aend && ai < bend) return (int)hipErrorInvalidValue;
-  }
+  // B's span and A's span (first member's start to last member's end) must not meet
+  if (batch > 0 && a_data && b_data &&
+      spans_meet(B, member_span_bytes(batch, b_bs, R, b_stride, wb), A, member_span_bytes(batch, a_bs, m, a_stride, wa)))
+    return (int)hipErrorInvalidValue;
   if (batch == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
   if (k == 0) return (int)hipMemsetAsync(status, 0, (size_t)batch * 4, st);  // no right-hand side: nothing to contradict
   const int path = m4ri_amd_plan_pluq_solve_batch(m, n, k);
   if (path == 2) return run_solve_path2(A, a_stride, a_bs, m, n, rank, P, Q, B, b_stride, b_bs, k, batch, status, st);
   if (path == 0) {
-    const int64_t per = PB_WAVE_THREADS / 64;
-    for (int64_t b0 = 0; b0 < batch; b0 += PB_CHUNK * per) {
-      const int64_t cnt = (batch - b0 < PB_CHUNK * per) ? batch - b0 : PB_CHUNK * per;
-      hipLaunchKernelGGL(ps_wave_kernel, dim3((unsigned)((cnt + per - 1) / per)), dim3(PB_WAVE_THREADS), 0, st, A, a_stride, a_bs, (int)m, (int)n, rank,
+    const int64_t per = BATCH_WAVE_THREADS / 64;
+    return launch_chunked(batch, BATCH_CHUNK * per, [&](int64_t b0, int64_t cnt) {
+      hipLaunchKernelGGL(ps_wave_kernel, dim3((unsigned)((cnt + per - 1) / per)), dim3(BATCH_WAVE_THREADS), 0, st, A, a_stride, a_bs, (int)m, (int)n, rank,
                          P, Q, B, b_stride, b_bs, (int)k, b0, batch, status);
-      HIPTRY(hipGetLastError());
-    }
-    return 0;
+    });
   }
   static std::once_flag once;
   std::call_once(once, [] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(ps_block_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)PB_LDS_BUDGET);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(ps_block_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)BATCH_LDS_BUDGET);
   });
   const int threads = block_threads(R, wb);
   const size_t lds  = (size_t)lds_bytes_solve(m, n, k);
-  for (int64_t b0 = 0; b0 < batch; b0 += PB_CHUNK) {
-    const int64_t cnt = (batch - b0 < PB_CHUNK) ? batch - b0 : PB_CHUNK;
+  return launch_chunked(batch, BATCH_CHUNK, [&](int64_t b0, int64_t cnt) {
     hipLaunchKernelGGL(ps_block_kernel, dim3((unsigned)cnt), dim3(threads), lds, st, A, a_stride, a_bs, (int)m, (int)n, rank, P, Q, B, b_stride, b_bs,
                        (int)k, (int)lds_row_words(wb), b0, status);
-    HIPTRY(hipGetLastError());
-  }
-  return 0;
+  });
 }
 
 }  // extern "C"

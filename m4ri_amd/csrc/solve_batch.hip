@@ -19,8 +19,8 @@
 // The paths (m4ri_amd_plan_solve_batch, m4ri_amd_plan_kernel_batch):
 //   0  R <= 64 and k <= 64: a wave per member, lane i holds row i of A and of B (the identity's bit made in a register); pivot = the
 //      lowest lane >= rank of a ballot, the pivot row's words by readlane; X gathered by ds_bpermute.  No LDS, no barrier.
-//   1  the augmented member fits in LDS: a workgroup per member, as eb_block_kernel<true> (rows in LDS under a row index, the swap
-//      of a column as two index entries, a flag pass and ballot per column).
+//   1  the augmented member fits in LDS: a workgroup per member, batch_common.h's scheme with the rows in LDS (rows under a row
+//      index, the swap of a column as two index entries, a flag pass and ballot per column).
 //   2  larger members one by one through the per-member calls on scratch copies, then one copy of statuses and ranks.  Blocking.
 // Paths 0 and 1 are one launch each (plus chunking above 2^30 workgroups), no allocation, no copy, no host synchronisation.
 // Memory rules: A is never written (except as Binv in place); bits at columns >= k (resp. n, kc) of a row's last word of B / Binv /
@@ -29,32 +29,22 @@
 #include <hip/hip_runtime.h>
 #include <mutex>
 #include <vector>
-#include "gf2_internal.h"
+#include "batch_common.h"
 #include "../../include/m4ri_amd.h"
 
 namespace {
 
-constexpr int SB_WAVE_THREADS   = 256;                 // path 0: four members per workgroup
-constexpr int SB_MAX_THREADS    = 1024;                // path 1
-constexpr int64_t SB_LDS_BUDGET = 160 * 1024;          // path 1: the whole LDS of a CU
-constexpr int64_t SB_CHUNK      = (int64_t)1 << 30;    // workgroups per launch
 constexpr int SB_SOLVE = 0, SB_INV = 1, SB_KER = 2;    // the op: X of [A | B], the inverse from [A | I], a null-space basis of A
-
-__device__ __forceinline__ word bpermute64(word x, int src) {  // lane `src`'s x; every lane of the wave must take part
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_ds_bpermute(src << 2, (int)(uint32_t)x);
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_ds_bpermute(src << 2, (int)(uint32_t)(x >> 32));
-  return ((word)hi << 32) | lo;
-}
 
 // path 0: a wave per member, lane i = row i of A (a) and of B or the identity (x, zero for the kernel), one word each.  Members
 // b0 + 4 * blockIdx.x + wave.  The kernel's B is the basis R (n x k).
 template <int OP>
-__global__ __launch_bounds__(SB_WAVE_THREADS) void sb_wave_kernel(const word *A, int64_t a_stride, int64_t a_bs, word *B,
-                                                                  int64_t b_stride, int64_t b_bs, int m, int n, int k, int64_t b0,
-                                                                  int64_t batch, int32_t *__restrict__ status, int32_t *__restrict__ rank_out) {
+__global__ __launch_bounds__(BATCH_WAVE_THREADS) void sb_wave_kernel(const word *A, int64_t a_stride, int64_t a_bs, word *B,
+                                                                     int64_t b_stride, int64_t b_bs, int m, int n, int k, int64_t b0,
+                                                                     int64_t batch, int32_t *__restrict__ status, int32_t *__restrict__ rank_out) {
   constexpr bool INV = OP == SB_INV, AUG = OP != SB_KER;
   const int lane  = threadIdx.x & 63;
-  const int64_t b = b0 + (int64_t)blockIdx.x * (SB_WAVE_THREADS / 64) + (threadIdx.x >> 6);
+  const int64_t b = b0 + (int64_t)blockIdx.x * (BATCH_WAVE_THREADS / 64) + (threadIdx.x >> 6);
   if (b >= batch) return;  // wave-uniform, no barrier in this kernel
   const int R      = m > n ? m : n;
   const word amask = tail_mask(n), bmask = tail_mask(k);
@@ -148,9 +138,9 @@ __global__ __launch_bounds__(SB_WAVE_THREADS) void sb_wave_kernel(const word *A,
 //   only: pos [n] int32 (the swap rule's arrangement) | idx [n] int32 (a pivot column's pivot row, a free column's basis column)
 // Row i of the flag pass is owned by thread i % blockDim.x (the lane of its ballot); flags[c & 1] bit i = bit c of logical row i.
 template <int OP>
-__global__ __launch_bounds__(SB_MAX_THREADS) void sb_block_kernel(const word *A, int64_t a_stride, int64_t a_bs, word *B,
-                                                                  int64_t b_stride, int64_t b_bs, int m, int n, int k, int ldw, int64_t b0,
-                                                                  int32_t *__restrict__ status, int32_t *__restrict__ rank_out) {
+__global__ __launch_bounds__(BATCH_MAX_THREADS) void sb_block_kernel(const word *A, int64_t a_stride, int64_t a_bs, word *B,
+                                                                     int64_t b_stride, int64_t b_bs, int m, int n, int k, int ldw, int64_t b0,
+                                                                     int32_t *__restrict__ status, int32_t *__restrict__ rank_out) {
   constexpr bool INV = OP == SB_INV;
   extern __shared__ __attribute__((aligned(16))) char sb_smem[];
   const int T = blockDim.x, t = threadIdx.x, lane = t & 63;
@@ -163,7 +153,7 @@ __global__ __launch_bounds__(SB_MAX_THREADS) void sb_block_kernel(const word *A,
   const word amask = tail_mask(n), bmask = tail_mask(k);
   word *rows       = reinterpret_cast<word *>(sb_smem);
   int32_t *perm    = reinterpret_cast<int32_t *>(sb_smem + (size_t)R * ldw * 8);
-  word *flags      = reinterpret_cast<word *>(sb_smem + (size_t)R * ldw * 8 + (((size_t)R * 4 + 15) & ~(size_t)15));
+  word *flags      = reinterpret_cast<word *>(sb_smem + (size_t)R * ldw * 8 + pad16((size_t)R * 4));
   word *pivcols    = flags + 2 * nfw;
 
   {
@@ -190,65 +180,27 @@ __global__ __launch_bounds__(SB_MAX_THREADS) void sb_block_kernel(const word *A,
   }
 
   int rank = 0;
-  int sw_r = -1, sw_p = -1, sw_R = 0, sw_P = 0;  // the previous column's pending swap of perm[rank] and perm[p]
+  PendingSwap sw;  // the previous column's pending swap of perm[rank] and perm[p]
   for (int c = 0; c < (INV ? 2 * n : n) && rank < m; ++c) {
     word *buf    = flags + (c & 1) * nfw;
     const int cw = c < n ? c >> 6 : wa + ((c - n) >> 6), cb = (c < n ? c : c - n) & 63;
-    // flag pass: each thread its own rows and their index entries
-    for (int base = t - lane; base < R; base += T) {
-      const int i = base + lane;
-      int bit     = 0;
-      if (i < R) {
-        int ph = (i == sw_r) ? sw_P : (i == sw_p) ? sw_R : perm[i];
-        if (i == sw_r || i == sw_p) perm[i] = ph;
-        bit = (int)((rows[ph * ldw + cw] >> cb) & 1);
-      }
-      const word bal = __ballot(bit);
-      if (lane == 0) buf[base >> 6] = bal;
-    }
-    sw_r = sw_p = -1;
+    flag_pass<true>(buf, rows, ldw, perm, sw, R, cw, cb, t, T);
     __syncthreads();
-    int p = -1;
-    for (int j = rank >> 6; j < rfw; ++j) {
-      word f = buf[j];
-      if (j == (rank >> 6)) f &= ~(word)0 << (rank & 63);
-      if (f) {
-        p = j * 64 + (int)__builtin_ctzll(f);
-        break;
-      }
-    }
+    const int p = find_pivot(buf, rank, rfw);
     if (p < 0) continue;  // no writes this column; the next flag pass uses the other buffer
     if (t == 0 && c < n) pivcols[c >> 6] |= (word)1 << (c & 63);
-    const int nw = W - cw;
     const int P  = perm[p];
     const word *prow = rows + P * ldw;
-    if (p != rank) {
-      sw_r = rank; sw_p = p; sw_P = P; sw_R = perm[rank];
-    }
+    sw.record(perm, rank, p, P);
     // the full update: every flagged row i != p (row `rank` is unflagged when p != rank), words cw .. W-1 (the pivot row has no
-    // bit left of column c).  Item q = (i, w) with q = i * nw + (w - cw), q = t, t + T, ...: advanced by (qi, qw) without a division.
-    {
-      const int qi = T / nw, qw = T - qi * nw;
-      int i = t / nw, w = cw + (t - (t / nw) * nw);
-      while (i < R) {
-        const int f = (int)((buf[i >> 6] >> (i & 63)) & 1);
-        if (f && i != p) rows[perm[i] * ldw + w] ^= prow[w];
-        i += qi;
-        w += qw;
-        if (w >= W) {
-          w -= nw;
-          ++i;
-        }
-      }
-    }
+    // bit left of column c).
+    for_each_item(0, R, cw, W, t, T, [&](int i, int w) {
+      if (flag_of(buf, i) && i != p) rows[perm[i] * ldw + w] ^= prow[w];
+    });
     ++rank;
     __syncthreads();
   }
-  if (sw_r >= 0) {  // the last column's swap (its owners only, as in the flag pass)
-    for (int i = t; i < R; i += T)
-      if (i == sw_r) perm[i] = sw_P;
-      else if (i == sw_p) perm[i] = sw_R;
-  }
+  sw.finish(perm, R, t, T);
   __syncthreads();
 
   if (OP == SB_KER) {
@@ -289,23 +241,14 @@ __global__ __launch_bounds__(SB_MAX_THREADS) void sb_block_kernel(const word *A,
       } else if (idx[i] < k && (idx[i] >> 6) == w) {
         x = (word)1 << (idx[i] & 63);
       }
-      word *dst = gb + (int64_t)i * b_stride + w;
-      if (w == wr - 1 && bmask != ~(word)0) x = (x & bmask) | (*dst & ~bmask);
-      *dst = x;
+      store_masked(gb + (int64_t)i * b_stride + w, x, w == wr - 1, bmask);
     }
     if (t == 0) rank_out[b] = rank;
     return;
   }
 
   if (INV) {
-    const int total = n * wb;
-    for (int q = t; q < total; q += T) {
-      const int i = q / wb, w = q - i * wb;
-      word x    = rows[perm[i] * ldw + wa + w];
-      word *dst = gb + (int64_t)i * b_stride + w;
-      if (w == wb - 1 && bmask != ~(word)0) x = (x & bmask) | (*dst & ~bmask);
-      *dst = x;
-    }
+    store_rows_out(gb, b_stride, rows + wa, ldw, perm, n, wb, bmask, t, T);  // the right half
     if (t == 0 && rank_out) {
       int r = 0;
       for (int j = 0; j < nfw; ++j) r += __builtin_popcountll(pivcols[j]);
@@ -344,9 +287,7 @@ __global__ __launch_bounds__(SB_MAX_THREADS) void sb_block_kernel(const word *A,
         const word pc = pivcols[i >> 6];
         if ((pc >> (i & 63)) & 1) x = rows[perm[below[i >> 6] + __builtin_popcountll(pc & (((word)1 << (i & 63)) - 1))] * ldw + wa + w];
       }
-      word *dst = gb + (int64_t)i * b_stride + w;
-      if (w == wb - 1 && bmask != ~(word)0) x = (x & bmask) | (*dst & ~bmask);
-      *dst = x;
+      store_masked(gb + (int64_t)i * b_stride + w, x, w == wb - 1, bmask);
     }
   }
   if (t == 0) {
@@ -355,71 +296,36 @@ __global__ __launch_bounds__(SB_MAX_THREADS) void sb_block_kernel(const word *A,
   }
 }
 
-int64_t lds_row_words(int64_t width) { return width + ((width & 1) ^ 1); }  // odd: the flag pass reads one word per row
-
 // path 1's LDS (sb_block_kernel): R rows of W words, the row index, flags and pivot columns over max(R, n), `tab` int32 entries
 int64_t lds_bytes_path1(int64_t R, int64_t W, int64_t n, int64_t tab) {
-  return R * lds_row_words(W) * 8 + ((R * 4 + 15) & ~(int64_t)15) + 3 * (((R > n ? R : n) + 63) / 64) * 8 + tab * 4;
+  return R * lds_row_words(W) * 8 + (int64_t)pad16((size_t)R * 4) + 3 * (((R > n ? R : n) + 63) / 64) * 8 + tab * 4;
 }
 
 // the kernel's path 1: m rows of words(n), the swap rule's arrangement and the index table (n entries each)
 int64_t lds_bytes_kernel(int64_t m, int64_t n) { return lds_bytes_path1(m, words_of(n), n, 2 * n); }
 
-int block_threads(int64_t R, int64_t W) { return R * W >= 8192 ? SB_MAX_THREADS : 256; }
-
 template <int OP>
 int launch(const word *A, int64_t a_stride, int64_t a_bs, word *B, int64_t b_stride, int64_t b_bs, int64_t m, int64_t n, int64_t k,
            int64_t batch, int path, int32_t *status, int32_t *rank, hipStream_t st) {
   if (path == 0) {
-    const int64_t per = SB_WAVE_THREADS / 64;
-    for (int64_t b0 = 0; b0 < batch; b0 += SB_CHUNK * per) {
-      const int64_t cnt = (batch - b0 < SB_CHUNK * per) ? batch - b0 : SB_CHUNK * per;
-      hipLaunchKernelGGL(sb_wave_kernel<OP>, dim3((unsigned)((cnt + per - 1) / per)), dim3(SB_WAVE_THREADS), 0, st, A, a_stride, a_bs, B, b_stride,
+    const int64_t per = BATCH_WAVE_THREADS / 64;
+    return launch_chunked(batch, BATCH_CHUNK * per, [&](int64_t b0, int64_t cnt) {
+      hipLaunchKernelGGL(sb_wave_kernel<OP>, dim3((unsigned)((cnt + per - 1) / per)), dim3(BATCH_WAVE_THREADS), 0, st, A, a_stride, a_bs, B, b_stride,
                          b_bs, (int)m, (int)n, (int)k, b0, batch, status, rank);
-      HIPTRY(hipGetLastError());
-    }
-    return 0;
+    });
   }
   static std::once_flag once;
   std::call_once(once, [] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(sb_block_kernel<OP>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SB_LDS_BUDGET);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(sb_block_kernel<OP>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)BATCH_LDS_BUDGET);
   });
   const bool ker    = OP == SB_KER;
   const int64_t R   = (ker || m > n) ? m : n, W = words_of(n) + (ker ? 0 : words_of(k));
   const int threads = block_threads(R, W);
   const size_t lds  = (size_t)(ker ? lds_bytes_kernel(m, n) : lds_bytes_path1(R, W, n, 0));
-  for (int64_t b0 = 0; b0 < batch; b0 += SB_CHUNK) {
-    const int64_t cnt = (batch - b0 < SB_CHUNK) ? batch - b0 : SB_CHUNK;
+  return launch_chunked(batch, BATCH_CHUNK, [&](int64_t b0, int64_t cnt) {
     hipLaunchKernelGGL(sb_block_kernel<OP>, dim3((unsigned)cnt), dim3(threads), lds, st, A, a_stride, a_bs, B, b_stride, b_bs, (int)m, (int)n,
                        (int)k, (int)lds_row_words(W), b0, status, rank);
-    HIPTRY(hipGetLastError());
-  }
-  return 0;
-}
-
-// path 2 helper: are rows r0 .. r1-1 of the k-column matrix at M (stride words) all zero?  Copies them to the host.  Blocking.
-int rows_zero(const word *M, int64_t stride, int64_t r0, int64_t r1, int64_t k, hipStream_t st, bool *zero) {
-  *zero = true;
-  const int64_t w = words_of(k);
-  if (r1 <= r0 || w == 0) return 0;
-  std::vector<word> h((size_t)((r1 - r0) * w));
-  HIPTRY(hipMemcpy2DAsync(h.data(), (size_t)w * 8, M + r0 * stride, (size_t)stride * 8, (size_t)w * 8, (size_t)(r1 - r0), hipMemcpyDeviceToHost, st));
-  HIPTRY(hipStreamSynchronize(st));
-  const word mask = (k & 63) ? (((word)1 << (k & 63)) - 1) : ~(word)0;
-  for (int64_t i = 0; i < r1 - r0; ++i)
-    for (int64_t j = 0; j < w; ++j)
-      if (h[(size_t)(i * w + j)] & (j == w - 1 ? mask : ~(word)0)) {
-        *zero = false;
-        return 0;
-      }
-  return 0;
-}
-
-// path 2: a clean copy (tail bits zero) of the m x n matrix at src into scratch
-int clean_copy(word *dst, int64_t dst_stride, const word *src, int64_t src_stride, int64_t m, int64_t n, hipStream_t st) {
-  HIPTRY(hipMemsetAsync(dst, 0, (size_t)(m * dst_stride) * 8, st));
-  HIPTRY(gf2_launch_copy_masked(st, dst, dst_stride, src, src_stride, m, n));
-  return 0;
+  });
 }
 
 // path 2 of the solve: per member, B's padding rows m .. R-1 checked first (all of them, see the header), then PLUQ of a copy of A_b
@@ -430,37 +336,32 @@ int run_path2_solve(const word *A, int64_t a_stride, int64_t a_bs, int64_t m, in
   const int64_t R = m > n ? m : n, wa = words_of(n), wb = words_of(k);
   std::vector<int32_t> hs((size_t)batch), hr((size_t)batch), P((size_t)(m > 0 ? m : 1)), Q((size_t)(n > 0 ? n : 1));
   word *sA = nullptr, *sB = nullptr;
-  auto run = [&]() -> int {
-    if (m > 0 && n > 0) HIPTRY(hipMalloc(reinterpret_cast<void **>(&sA), (size_t)(m * wa) * 8));
-    if (wb > 0) HIPTRY(hipMalloc(reinterpret_cast<void **>(&sB), (size_t)(R * wb) * 8));
-    for (int64_t b = 0; b < batch; ++b) {
-      const word *Ab = A + b * a_bs;
-      word *Bb       = B + b * b_bs;
-      int32_t r      = 0;
-      if (m > 0 && n > 0) {
-        if (int rc = clean_copy(sA, wa, Ab, a_stride, m, n, st)) return rc;
-        if (int rc = m4ri_amd_pluq_dev(sA, wa, m, n, P.data(), Q.data(), &r, M4RI_AMD_PLE_CUTOFF, st)) return rc;
-      }
-      hr[(size_t)b] = r;
-      bool zero     = true;
-      if (int rc = rows_zero(Bb, b_stride, (m > 0 && n > 0) ? m : 0, R, k, st, &zero)) return rc;  // A = 0: every row of B
-      int ret = zero ? 0 : -1;
-      if (ret == 0 && wb > 0 && m > 0 && n > 0) {
-        if (int rc = clean_copy(sB, wb, Bb, b_stride, R, k, st)) return rc;
-        if (int rc = m4ri_amd_pluq_solve_left_dev(sA, wa, m, n, r, P.data(), Q.data(), sB, wb, R, k, 0, 1, &ret, st)) return rc;
-        if (ret == 0) HIPTRY(gf2_launch_copy_masked(st, Bb, b_stride, sB, wb, R, k));
-      }
-      hs[(size_t)b] = ret;
+  Scratch scratch(st);
+  if (m > 0 && n > 0) HIPTRY(scratch.words(&sA, m * wa));
+  if (wb > 0) HIPTRY(scratch.words(&sB, R * wb));
+  for (int64_t b = 0; b < batch; ++b) {
+    const word *Ab = A + b * a_bs;
+    word *Bb       = B + b * b_bs;
+    int32_t r      = 0;
+    if (m > 0 && n > 0) {
+      HIPTRY(clean_copy(sA, wa, Ab, a_stride, m, n, st));
+      HIPTRY(m4ri_amd_pluq_dev(sA, wa, m, n, P.data(), Q.data(), &r, M4RI_AMD_PLE_CUTOFF, st));
     }
-    HIPTRY(hipMemcpyAsync(status, hs.data(), (size_t)batch * 4, hipMemcpyHostToDevice, st));
-    if (rank) HIPTRY(hipMemcpyAsync(rank, hr.data(), (size_t)batch * 4, hipMemcpyHostToDevice, st));
-    return (int)hipStreamSynchronize(st);
-  };
-  const int rc = run();
-  if (rc) (void)hipStreamSynchronize(st);
-  if (sA) (void)hipFree(sA);
-  if (sB) (void)hipFree(sB);
-  return rc;
+    hr[(size_t)b] = r;
+    bool zero     = true;
+    HIPTRY(rows_zero(Bb, b_stride, (m > 0 && n > 0) ? m : 0, R, k, st, &zero));  // A = 0: every row of B
+    int ret = zero ? 0 : -1;
+    if (ret == 0 && wb > 0 && m > 0 && n > 0) {
+      HIPTRY(clean_copy(sB, wb, Bb, b_stride, R, k, st));
+      HIPTRY(m4ri_amd_pluq_solve_left_dev(sA, wa, m, n, r, P.data(), Q.data(), sB, wb, R, k, 0, 1, &ret, st));
+      if (ret == 0) HIPTRY(gf2_launch_copy_masked(st, Bb, b_stride, sB, wb, R, k));
+    }
+    hs[(size_t)b] = ret;
+  }
+  HIPTRY(hipMemcpyAsync(status, hs.data(), (size_t)batch * 4, hipMemcpyHostToDevice, st));
+  if (rank) HIPTRY(hipMemcpyAsync(rank, hr.data(), (size_t)batch * 4, hipMemcpyHostToDevice, st));
+  HIPTRY(hipStreamSynchronize(st));
+  return scratch.done();
 }
 
 // path 2 of the inverse: per member, m4ri_amd_inv_dev on a clean copy of A_b into scratch, copied into Binv_b; the rank (when
@@ -470,25 +371,18 @@ int run_path2_inv(word *Binv, int64_t b_stride, int64_t b_bs, const word *A, int
   const int64_t wn = words_of(n);
   std::vector<int32_t> hr((size_t)batch);
   word *sA = nullptr, *sX = nullptr;
-  auto run = [&]() -> int {
-    HIPTRY(hipMalloc(reinterpret_cast<void **>(&sA), (size_t)(n * wn) * 8));
-    HIPTRY(hipMalloc(reinterpret_cast<void **>(&sX), (size_t)(n * wn) * 8));
-    for (int64_t b = 0; b < batch; ++b) {
-      if (int rc = clean_copy(sA, wn, A + b * a_bs, a_stride, n, n, st)) return rc;
-      if (int rc = m4ri_amd_inv_dev(sX, wn, sA, wn, n, st)) return rc;
-      HIPTRY(gf2_launch_copy_masked(st, Binv + b * b_bs, b_stride, sX, wn, n, n));
-      if (rank) {
-        if (int rc = m4ri_amd_echelonize_dev(sA, wn, n, n, 0, &hr[(size_t)b], st)) return rc;
-      }
-    }
-    if (rank) HIPTRY(hipMemcpyAsync(rank, hr.data(), (size_t)batch * 4, hipMemcpyHostToDevice, st));
-    return (int)hipStreamSynchronize(st);
-  };
-  const int rc = run();
-  if (rc) (void)hipStreamSynchronize(st);
-  if (sA) (void)hipFree(sA);
-  if (sX) (void)hipFree(sX);
-  return rc;
+  Scratch scratch(st);
+  HIPTRY(scratch.words(&sA, n * wn));
+  HIPTRY(scratch.words(&sX, n * wn));
+  for (int64_t b = 0; b < batch; ++b) {
+    HIPTRY(clean_copy(sA, wn, A + b * a_bs, a_stride, n, n, st));
+    HIPTRY(m4ri_amd_inv_dev(sX, wn, sA, wn, n, st));
+    HIPTRY(gf2_launch_copy_masked(st, Binv + b * b_bs, b_stride, sX, wn, n, n));
+    if (rank) HIPTRY(m4ri_amd_echelonize_dev(sA, wn, n, n, 0, &hr[(size_t)b], st));
+  }
+  if (rank) HIPTRY(hipMemcpyAsync(rank, hr.data(), (size_t)batch * 4, hipMemcpyHostToDevice, st));
+  HIPTRY(hipStreamSynchronize(st));
+  return scratch.done();
 }
 
 // path 2 of the kernel: per member, m4ri_amd_kernel_left_pluq_dev on a clean copy of A_b (m = 0: one zero row, the same basis)
@@ -498,27 +392,22 @@ int run_path2_kernel(const word *A, int64_t a_stride, int64_t a_bs, int64_t m, i
   const int64_t wn = words_of(n), rows = m > 0 ? m : 1;
   std::vector<int32_t> hr((size_t)batch);
   word *sA = nullptr, *sR = nullptr;
-  auto run = [&]() -> int {
-    HIPTRY(hipMalloc(reinterpret_cast<void **>(&sA), (size_t)(rows * wn) * 8));
-    HIPTRY(hipMalloc(reinterpret_cast<void **>(&sR), (size_t)(n * wn) * 8));
-    for (int64_t b = 0; b < batch; ++b) {
-      if (m > 0) {
-        if (int rc = clean_copy(sA, wn, A + b * a_bs, a_stride, m, n, st)) return rc;
-      } else {
-        HIPTRY(hipMemsetAsync(sA, 0, (size_t)wn * 8, st));
-      }
-      HIPTRY(hipMemsetAsync(sR, 0, (size_t)(n * wn) * 8, st));
-      if (int rc = m4ri_amd_kernel_left_pluq_dev(sA, wn, rows, n, sR, wn, 0, &hr[(size_t)b], st)) return rc;
-      if (kc > 0) HIPTRY(gf2_launch_copy_masked(st, R + b * r_bs, r_stride, sR, wn, n, kc));
+  Scratch scratch(st);
+  HIPTRY(scratch.words(&sA, rows * wn));
+  HIPTRY(scratch.words(&sR, n * wn));
+  for (int64_t b = 0; b < batch; ++b) {
+    if (m > 0) {
+      HIPTRY(clean_copy(sA, wn, A + b * a_bs, a_stride, m, n, st));
+    } else {
+      HIPTRY(hipMemsetAsync(sA, 0, (size_t)wn * 8, st));
     }
-    HIPTRY(hipMemcpyAsync(rank, hr.data(), (size_t)batch * 4, hipMemcpyHostToDevice, st));
-    return (int)hipStreamSynchronize(st);
-  };
-  const int rc = run();
-  if (rc) (void)hipStreamSynchronize(st);
-  if (sA) (void)hipFree(sA);
-  if (sR) (void)hipFree(sR);
-  return rc;
+    HIPTRY(hipMemsetAsync(sR, 0, (size_t)(n * wn) * 8, st));
+    HIPTRY(m4ri_amd_kernel_left_pluq_dev(sA, wn, rows, n, sR, wn, 0, &hr[(size_t)b], st));
+    if (kc > 0) HIPTRY(gf2_launch_copy_masked(st, R + b * r_bs, r_stride, sR, wn, n, kc));
+  }
+  HIPTRY(hipMemcpyAsync(rank, hr.data(), (size_t)batch * 4, hipMemcpyHostToDevice, st));
+  HIPTRY(hipStreamSynchronize(st));
+  return scratch.done();
 }
 
 }  // namespace
@@ -530,8 +419,8 @@ int m4ri_amd_plan_solve_batch(int64_t m, int64_t n, int64_t k) {
   const int64_t R = m > n ? m : n;
   if (R <= 64 && k <= 64) return 0;
   const int64_t W = words_of(n) + words_of(k);
-  if (R > SB_LDS_BUDGET / 8 || W > SB_LDS_BUDGET / 8) return 2;
-  return lds_bytes_path1(R, W, n, 0) <= SB_LDS_BUDGET ? 1 : 2;
+  if (R > BATCH_LDS_BUDGET / 8 || W > BATCH_LDS_BUDGET / 8) return 2;
+  return lds_bytes_path1(R, W, n, 0) <= BATCH_LDS_BUDGET ? 1 : 2;
 }
 
 int m4ri_amd_solve_left_batch_dev(const word *A, int64_t a_stride, int64_t a_bs, int64_t m, int64_t n, word *B, int64_t b_stride, int64_t b_bs,
@@ -557,13 +446,10 @@ int m4ri_amd_inv_batch_dev(word *Binv, int64_t b_stride, int64_t b_bs, const wor
   if (batch > 1 && n > 0 && b_bs < (n - 1) * b_stride + wn) return (int)hipErrorInvalidValue;
   if (batch > 0 && n > 0 && (!Binv || !A)) return (int)hipErrorInvalidValue;
   if (batch > 0 && n > 0) {  // in place with the same layout, or no overlap at all
-    const uintptr_t bi = (uintptr_t)Binv, ai = (uintptr_t)A;
-    if (bi == ai) {
+    if (Binv == A) {
       if (a_stride != b_stride || a_bs != b_bs) return (int)hipErrorInvalidValue;
-    } else {
-      const uintptr_t bend = bi + (uintptr_t)(((batch - 1) * b_bs + (n - 1) * b_stride + wn) * 8);
-      const uintptr_t aend = ai + (uintptr_t)(((batch - 1) * a_bs + (n - 1) * a_stride + wn) * 8);
-      if (bi < aend && ai < bend) return (int)hipErrorInvalidValue;
+    } else if (spans_meet(Binv, member_span_bytes(batch, b_bs, n, b_stride, wn), A, member_span_bytes(batch, a_bs, n, a_stride, wn))) {
+      return (int)hipErrorInvalidValue;
     }
   }
   if (batch == 0) return 0;
@@ -577,8 +463,8 @@ int m4ri_amd_inv_batch_dev(word *Binv, int64_t b_stride, int64_t b_bs, const wor
 int m4ri_amd_plan_kernel_batch(int64_t m, int64_t n) {
   if (m < 0 || n < 0) return -1;
   if (m <= 64 && n <= 64) return 0;
-  if (m > SB_LDS_BUDGET / 8 || n > SB_LDS_BUDGET / 8) return 2;
-  return lds_bytes_kernel(m, n) <= SB_LDS_BUDGET ? 1 : 2;
+  if (m > BATCH_LDS_BUDGET / 8 || n > BATCH_LDS_BUDGET / 8) return 2;
+  return lds_bytes_kernel(m, n) <= BATCH_LDS_BUDGET ? 1 : 2;
 }
 
 int m4ri_amd_kernel_left_batch_dev(const word *A, int64_t a_stride, int64_t a_bs, int64_t m, int64_t n, word *R, int64_t r_stride, int64_t r_bs,
@@ -590,12 +476,10 @@ int m4ri_amd_kernel_left_batch_dev(const word *A, int64_t a_stride, int64_t a_bs
   if (batch > 0 && !rank) return (int)hipErrorInvalidValue;
   const bool a_data = m > 0 && n > 0, r_data = kc > 0;  // kc <= n
   if (batch > 0 && ((a_data && !A) || (r_data && !R))) return (int)hipErrorInvalidValue;
-  if (batch > 0 && a_data && r_data) {  // R's span and A's span (first member's start to last member's end) must not meet
-    const uintptr_t ri = (uintptr_t)R, ai = (uintptr_t)A;
-    const uintptr_t rend = ri + (uintptr_t)(((batch - 1) * r_bs + (n - 1) * r_stride + wr) * 8);
-    const uintptr_t aend = ai + (uintptr_t)(((batch - 1) * a_bs + (m - 1) * a_stride + wa) * 8);
-    if (ri < aend && ai < rend) return (int)hipErrorInvalidValue;
-  }
+  // R's span and A's span (first member's start to last member's end) must not meet
+  if (batch > 0 && a_data && r_data &&
+      spans_meet(R, member_span_bytes(batch, r_bs, n, r_stride, wr), A, member_span_bytes(batch, a_bs, m, a_stride, wa)))
+    return (int)hipErrorInvalidValue;
   if (batch == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
   if (n == 0) return (int)hipMemsetAsync(rank, 0, (size_t)batch * 4, st);
