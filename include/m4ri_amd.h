@@ -320,6 +320,28 @@ int m4ri_amd_inv_dev(word *Binv, int64_t b_stride, const word *A, int64_t a_stri
  * m4ri_amd_trtri_upper_dev: U (n x n) <- U^-1, only the bits strictly above the diagonal are read and written;
  * asynchronous on `stream`, scratch grow-only per device. */
 int m4ri_amd_transpose_dev(word *D, int64_t d_stride, const word *A, int64_t a_stride, int64_t nrows, int64_t ncols, void *stream);
+/* `batch` transposes of SMALL matrices of one shape, D_b <- (A_b)^T (transpose_batch.hip): A_b nrows x ncols at A + b * a_bs words,
+ * rows a_stride words apart; D_b ncols x nrows at D + b * d_bs words, rows d_stride words apart.  The valid bits of D_b become the
+ * transpose; bits of A at columns >= ncols of a row's last word never influence a valid bit of D.  A is never written.  On paths 0
+ * and 1 of m4ri_amd_plan_transpose_batch, bits at columns >= nrows of a row's last word of D, the words from the width to d_stride
+ * of a row and the words between members are left as they were; on path 2 (m4ri_amd_transpose_dev's kernel and contract, the member
+ * a grid dimension) the last word of a row of D is written whole, the bits beyond column nrows zero, and padding words and gaps are
+ * left alone.  Every path is asynchronous on `stream`: plain launches (several for a batch beyond one grid), no allocation, no copy,
+ * no engine workspace, no engine lock; capturable.  nrows = 0, ncols = 0 or batch = 0 succeeds without touching anything.
+ * In place: D == A is allowed exactly when nrows == ncols <= 1024, d_stride == a_stride and d_bs == a_bs; such a call always runs
+ * in registers (a wave per member up to 64, a wave per pair of mirrored 64 x 64 blocks above), whatever the bound below or its
+ * override; D == A with members of any other shape is refused whatever the batch.  hipErrorInvalidValue, before any HIP call, for negative sizes, strides or batch strides, a_stride < words(ncols),
+ * d_stride < words(nrows), overlapping D members (batch > 1 and d_bs < (ncols - 1) * d_stride + words(nrows)), D overlapping A (the
+ * span from the first member's start to the last member's end of each) in any but the in-place case, or a NULL pointer with a
+ * non-empty member.  a_bs is otherwise free: A is only read, a_bs = 0 transposes one A into every D_b. */
+int m4ri_amd_transpose_batch_dev(word *D, int64_t d_stride, int64_t d_bs, const word *A, int64_t a_stride, int64_t a_bs, int64_t nrows,
+                                 int64_t ncols, int64_t batch, void *stream);
+/* which path an out-of-place m4ri_amd_transpose_batch_dev takes for this shape (pure host arithmetic; -1 for negative sizes): 0 one
+ * wave per member, registers only (nrows, ncols <= 64); 1 one wave per 64 x 64 block (max(nrows, ncols) <= the measured bound T1, a
+ * multiple of 64 in [64, 1024]; 64 = no such shape); 2 the tile kernel of m4ri_amd_transpose_dev.  The environment variable
+ * M4RI_AMD_TRANSPOSE_BATCH_PATH1_MAX (read per call, clamped to [64, 1024] in multiples of 64) replaces T1 in the routing of
+ * out-of-place calls; this function does not read it. */
+int m4ri_amd_plan_transpose_batch(int64_t nrows, int64_t ncols);
 int m4ri_amd_trtri_upper_dev(word *U, int64_t stride, int64_t n, void *stream);
 /* Device twins of mzd_echelonize* and mzd_apply_p_right{,_trans} (echelon.hip).  P: HOST array.  Blocking. */
 int m4ri_amd_echelonize_dev(word *A, int64_t stride, int64_t nrows, int64_t ncols, int full, int32_t *rank_out, void *stream);

@@ -168,6 +168,8 @@ SYMBOLS = {
     "mzd_trtri_upper": (MzdPtr, [MzdPtr]),
     "mzd_trtri_upper_russian": (MzdPtr, [MzdPtr, _I]),
     "m4ri_amd_transpose_dev": (_I, [_P, _I64, _P, _I64, _I64, _I64, _P]),
+    "m4ri_amd_transpose_batch_dev": (_I, [_P, _I64, _I64, _P, _I64, _I64, _I64, _I64, _I64, _P]),
+    "m4ri_amd_plan_transpose_batch": (_I, [_I64, _I64]),
     "m4ri_amd_m4rm_batch_dev": (_I, [_P, _I64, _I64, _P, _I64, _I64, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I, _P]),
     "m4ri_amd_mul_batch_dev": (_I, [_P, _I64, _I64, _P, _I64, _I64, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I, _I, _P]),
     "m4ri_amd_mul_small_batch_dev": (_I, [_P, _I64, _I64, _P, _I64, _I64, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I, _P]),
@@ -487,6 +489,19 @@ def mul_small_batch_dev(C: int, c_stride: int, c_bs: int, A: int, a_stride: int,
 def plan_mul_small_batch(m: int, l: int, n: int) -> int:
     """The path mul_small_batch_dev takes for (m, l, n) (0 wave per member, 1 wave per 64 x 64 block of C, 2 forwarded). Host arithmetic."""
     return int(lib().m4ri_amd_plan_mul_small_batch(m, l, n))
+
+
+def transpose_batch_dev(D: int, d_stride: int, d_bs: int, A: int, a_stride: int, a_bs: int, nrows: int, ncols: int, batch: int, stream: int = 0) -> None:
+    """`batch` transposes of small matrices, D_b = (A_b)^T with X_b = X + b * x_bs words (A_b nrows x ncols, D_b ncols x nrows); D == A
+    allowed for square members up to 1024 with equal strides.  Asynchronous, lock-free and capturable on every path of
+    plan_transpose_batch; paths 0-1 write only the valid bits of D, path 2 whole last words (m4ri_amd_transpose_dev's contract)."""
+    _check(lib().m4ri_amd_transpose_batch_dev(D, d_stride, d_bs, A, a_stride, a_bs, nrows, ncols, batch, stream), "m4ri_amd_transpose_batch_dev")
+
+
+def plan_transpose_batch(nrows: int, ncols: int) -> int:
+    """The path an out-of-place transpose_batch_dev takes for (nrows, ncols) (0 wave per member, 1 wave per 64 x 64 block, 2 the tile
+    kernel). Host arithmetic."""
+    return int(lib().m4ri_amd_plan_transpose_batch(nrows, ncols))
 
 
 def model_seconds_batch(m: int, l: int, n: int, levels: int = -1, batch: int = 1) -> float:

@@ -75,6 +75,12 @@ hipError_t gf2_launch_fill_splitmix(hipStream_t s, word *M, int64_t stride, int6
 hipError_t gf2_launch_fill_splitmix_rows(hipStream_t s, word *M, int64_t stride, int64_t row0, int64_t rows, int64_t ncols,
                                          uint64_t seed);
 
+// ---- transposes (transpose.hip) -------------------------------------------------------------------------------------------
+// the tile kernel on `batch` members (member b: nrows x ncols at A + b * a_bs -> ncols x nrows at D + b * d_bs); one member is
+// m4ri_amd_transpose_dev, many are path 2 of m4ri_amd_transpose_batch_dev (transpose_batch.hip)
+hipError_t gf2_launch_transpose_tiles(hipStream_t st, word *D, int64_t d_stride, int64_t d_bs, const word *A, int64_t a_stride, int64_t a_bs,
+                                      int64_t nrows, int64_t ncols, int64_t batch);
+
 // ---- host side ----------------------------------------------------------------------------------------------------------------
 double gf2_small_host_cost(int64_t m, int64_t l, int64_t n);  // small_host.cpp: word operations of the host product
 int gf2_multi_wanted(int64_t m, int64_t l, int64_t n);         // multi.hip: would mzd_mul_mp spread this product over devices?

@@ -9,7 +9,7 @@
 //     a group's 64 x 16 words are loaded along the rows (128 contiguous bytes per row, branch-free, TR_PREFETCH groups
 //     ahead in registers) and staged in LDS (double-buffered, one barrier per group);
 //   * wave w owns the word columns 2w, 2w+1: it takes its two 64 x 64 blocks of the group out of LDS (one ds_read_b128
-//     per lane) and transposes them in registers -- six exchange stages, none through LDS (transpose_block below);
+//     per lane) and transposes them in registers -- six exchange stages, none through LDS (transpose_block.h);
 //   * every 8 groups lane j of the wave holds 8 consecutive words (64 bytes) of row 64 (2w + k) + j of the result; they
 //     go through a wave-private LDS block so that a store instruction writes 16 x 64 contiguous bytes, the second half
 //     of each 128-byte line a few microseconds after the first from the same CU.
@@ -26,7 +26,8 @@
 //             is left is what HBM gives 128-byte reads at an 8 KB stride against 64-byte writes (the same box copies
 //             at 4.7 .. 5.2 TB/s); 16384^2 and 32768^2, which the caches help, run at 4.2 and 5.5 TB/s.
 #include <hip/hip_runtime.h>
-#include "gf2_common.h"
+#include "gf2_internal.h"
+#include "transpose_block.h"
 
 #ifdef TR_TIMING  // tools/transpose_probe.hip: a block's timeline in 100 MHz ticks
 __device__ unsigned long long tr_times[8192][6];
@@ -50,67 +51,18 @@ constexpr int TR_GROUPS  = 16;   // 64-row groups per tile: 128 bytes per row of
 #endif
 constexpr int TR_PITCH   = TR_WORDS + 2;  // LDS row pitch in words: 16-byte aligned, 36 (68) banks apart (b128 reads conflict-free)
 
-// lane i holds row i of a 64 x 64 bit block in (lo, hi); on return lane j holds column j.  Six exchange stages (lane
-// distance = bit distance = 32, 16, ..., 1), none of them through LDS -- with ds_bpermute the six dependent LDS round
-// trips per block were what the kernel waited for:
-//   32: lanes >= 32 of lo <-> lanes < 32 of hi: one v_permlane32_swap;
-//   16: the low halves of both dwords in one register, the high halves in another (v_perm), v_permlane16_swap;
-//   8: the same with bytes, two v_perm from the previous form, the exchange a DPP row_ror:8 and three selects, two v_perm back;
-//   4, 2, 1: a lane keeps the bits K of its dwords (M for the lower lane of a pair, ~M for the upper one) and hands
-//       the others to its partner, both dwords' worth packed into one dword that moves by DPP (row_half_mirror
-//       + quad_perm[3,2,1,0] = xor 4; quad_perm for 2 and 1); branch-free, the two roles differ in K and two shift counts.
-__device__ __forceinline__ uint32_t dpp_xor8(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x128, 0xf, 0xf, true); }
-__device__ __forceinline__ uint32_t dpp_xor4(uint32_t v) {
-  const int t = __builtin_amdgcn_update_dpp(0, (int)v, 0x141, 0xf, 0xf, true);  // row_half_mirror: i -> i ^ 7
-  return (uint32_t)__builtin_amdgcn_update_dpp(0, t, 0x1B, 0xf, 0xf, true);     // quad_perm [3,2,1,0]: i -> i ^ 3
-}
-__device__ __forceinline__ uint32_t dpp_xor2(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xf, 0xf, true); }
-__device__ __forceinline__ uint32_t dpp_xor1(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xf, 0xf, true); }
-
-__device__ __forceinline__ void transpose_block(uint32_t &lo, uint32_t &hi, int lane) {
-  {
-    const auto r = __builtin_amdgcn_permlane32_swap(lo, hi, false, false);
-    lo = r[0]; hi = r[1];
-  }
-  {
-    // distance 16: y = the low halves of (lo, hi), x = the high halves; the lower lane of a pair keeps y and gets its
-    // partner's y as its new x, the upper lane keeps x and gets its partner's x as its new y
-    uint32_t y = __builtin_amdgcn_perm(hi, lo, 0x05040100u);
-    uint32_t x = __builtin_amdgcn_perm(hi, lo, 0x07060302u);
-    const auto r = __builtin_amdgcn_permlane16_swap(y, x, false, false);  // odd rows of y <-> even rows of x
-    y = r[0]; x = r[1];
-    // distance 8, straight from that form: y8 = the even bytes of the (lo, hi) that (y, x) stand for, x8 = the odd ones
-    const uint32_t y8 = __builtin_amdgcn_perm(x, y, 0x06020400u), x8 = __builtin_amdgcn_perm(x, y, 0x07030501u);
-    const bool up = (lane & 8) != 0;
-    const uint32_t got = dpp_xor8(up ? y8 : x8);
-    const uint32_t ny = up ? got : y8, nx = up ? x8 : got;
-    lo = __builtin_amdgcn_perm(nx, ny, 0x05010400u);
-    hi = __builtin_amdgcn_perm(nx, ny, 0x07030602u);
-  }
-#define TR_STAGE(D, M, XCHG)                                                           \
-  {                                                                                    \
-    const uint32_t up = (uint32_t)lane & (D), K = up ? ~(M) : (M);                     \
-    const uint32_t shr = (D) - up, shl = up; /* (D, 0) for the lower lane, (0, D) for the upper */ \
-    const uint32_t s  = ((lo & ~K) >> shr) | ((hi & ~K) << shl);                       \
-    const uint32_t r  = XCHG(s);                                                       \
-    lo = (lo & K) | ((r & (M)) << shr);                                                \
-    hi = (hi & K) | ((r & ~(M)) >> shl);                                               \
-  }
-  TR_STAGE(4, 0x0f0f0f0fu, dpp_xor4)
-  TR_STAGE(2, 0x33333333u, dpp_xor2)
-  TR_STAGE(1, 0x55555555u, dpp_xor1)
-#undef TR_STAGE
-}
-
 // VEC / AVEC: the rows of D / of A are 16-byte aligned (even stride, aligned base) -> 16-byte stores / loads.
 // The loads are branch-free and unmasked: addresses are clamped into the matrix (a load behind a branch would be waited
 // for on the spot, and the kernel lives on having many in flight), and what a clamped or ragged load brings in beyond
 // A's rows and columns ends up either in rows of D that do not exist (never stored) or in the bits of D's last word
-// beyond column nrows (masked at the store).
+// beyond column nrows (masked at the store).  The grid's second dimension is the member of a batch: member blockIdx.y of the launch
+// is the matrix at A0 + blockIdx.y * a_bs and goes to D0 + blockIdx.y * d_bs (one member: both strides unused).
 template <bool VEC, bool AVEC>
-__global__ __launch_bounds__(TR_THREADS) __attribute__((amdgpu_waves_per_eu(TR_WAVES_PER_EU))) void transpose_kernel(word *__restrict__ D, int64_t d_stride, const word *__restrict__ A,
-                                                               int64_t a_stride, int64_t nrows, int64_t ncols, int64_t tiles_r,
-                                                               int64_t ntiles) {
+__global__ __launch_bounds__(TR_THREADS) __attribute__((amdgpu_waves_per_eu(TR_WAVES_PER_EU))) void transpose_kernel(word *__restrict__ D0, int64_t d_stride, int64_t d_bs,
+                                                               const word *__restrict__ A0, int64_t a_stride, int64_t a_bs, int64_t nrows,
+                                                               int64_t ncols, int64_t tiles_r, int64_t ntiles) {
+  word *__restrict__ D       = D0 + (int64_t)blockIdx.y * d_bs;
+  const word *__restrict__ A = A0 + (int64_t)blockIdx.y * a_bs;
   __shared__ __attribute__((aligned(16))) word stage[2][64][TR_PITCH];
   __shared__ __attribute__((aligned(16))) word ostage[TR_THREADS / 64][64][TR_GROUPS / 2];
   const int64_t wa = (ncols + 63) >> 6, wd = (nrows + 63) >> 6;
@@ -222,22 +174,39 @@ __global__ __launch_bounds__(TR_THREADS) __attribute__((amdgpu_waves_per_eu(TR_W
 
 }  // namespace
 
+// `batch` members in launches of at most TR_MEMBERS each: member b is the nrows x ncols matrix at A + b * a_bs and goes to D + b * d_bs.
+// The 16-byte paths need every member's rows aligned: an even stride, an aligned base and (beyond one member) an even batch stride.
+constexpr int64_t TR_MEMBERS = 65535;  // the grid's second dimension
+
+extern "C" hipError_t gf2_launch_transpose_tiles(hipStream_t st, word *D, int64_t d_stride, int64_t d_bs, const word *A, int64_t a_stride, int64_t a_bs,
+                                                 int64_t nrows, int64_t ncols, int64_t batch) {
+  if (nrows <= 0 || ncols <= 0 || batch <= 0) return hipSuccess;
+  const int64_t tiles_r = (nrows + 64 * TR_GROUPS - 1) / (64 * TR_GROUPS), tiles_c = (((ncols + 63) >> 6) + TR_WORDS - 1) / TR_WORDS;
+  if (tiles_r * tiles_c > 0x7fffffffLL) return hipErrorInvalidValue;
+  const bool vec  = (d_stride % 2 == 0) && (reinterpret_cast<uintptr_t>(D) % 16 == 0) && (batch == 1 || d_bs % 2 == 0);
+  const bool avec = (a_stride % 2 == 0) && (reinterpret_cast<uintptr_t>(A) % 16 == 0) && (batch == 1 || a_bs % 2 == 0);
+  const int64_t ntiles = tiles_r * tiles_c;
+  const dim3 block(TR_THREADS);
+  for (int64_t b0 = 0; b0 < batch; b0 += TR_MEMBERS) {
+    const int64_t nb = batch - b0 < TR_MEMBERS ? batch - b0 : TR_MEMBERS;
+    const dim3 grid((unsigned)ntiles, (unsigned)nb);
+    word *d = D + b0 * d_bs;
+    const word *a = A + b0 * a_bs;
+    if (vec && avec)  hipLaunchKernelGGL((transpose_kernel<true, true>), grid, block, 0, st, d, d_stride, d_bs, a, a_stride, a_bs, nrows, ncols, tiles_r, ntiles);
+    else if (vec)     hipLaunchKernelGGL((transpose_kernel<true, false>), grid, block, 0, st, d, d_stride, d_bs, a, a_stride, a_bs, nrows, ncols, tiles_r, ntiles);
+    else if (avec)    hipLaunchKernelGGL((transpose_kernel<false, true>), grid, block, 0, st, d, d_stride, d_bs, a, a_stride, a_bs, nrows, ncols, tiles_r, ntiles);
+    else              hipLaunchKernelGGL((transpose_kernel<false, false>), grid, block, 0, st, d, d_stride, d_bs, a, a_stride, a_bs, nrows, ncols, tiles_r, ntiles);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
 // D (ncols x nrows bits, d_stride words per row) <- A^T, A nrows x ncols.  D must not overlap A.  Bits of A's last word
-// beyond ncols are ignored; D's bits beyond column nrows come out zero.  Asynchronous on `stream`.
+// beyond ncols are ignored; D's bits beyond column nrows come out zero.  Asynchronous on `stream`.  The batch = 1 case of the
+// launcher above.
 extern "C" int m4ri_amd_transpose_dev(word *D, int64_t d_stride, const word *A, int64_t a_stride, int64_t nrows, int64_t ncols,
                                       void *stream) {
   if (nrows < 0 || ncols < 0) return (int)hipErrorInvalidValue;
-  if (nrows == 0 || ncols == 0) return 0;
-  const int64_t tiles_r = (nrows + 64 * TR_GROUPS - 1) / (64 * TR_GROUPS), tiles_c = (((ncols + 63) >> 6) + TR_WORDS - 1) / TR_WORDS;
-  if (tiles_r * tiles_c > 0x7fffffffLL) return (int)hipErrorInvalidValue;
-  const bool vec  = (d_stride % 2 == 0) && (reinterpret_cast<uintptr_t>(D) % 16 == 0);
-  const bool avec = (a_stride % 2 == 0) && (reinterpret_cast<uintptr_t>(A) % 16 == 0);
-  const int64_t ntiles = tiles_r * tiles_c;
-  const dim3 grid((unsigned)ntiles), block(TR_THREADS);
-  hipStream_t st = (hipStream_t)stream;
-  if (vec && avec)  hipLaunchKernelGGL((transpose_kernel<true, true>), grid, block, 0, st, D, d_stride, A, a_stride, nrows, ncols, tiles_r, ntiles);
-  else if (vec)     hipLaunchKernelGGL((transpose_kernel<true, false>), grid, block, 0, st, D, d_stride, A, a_stride, nrows, ncols, tiles_r, ntiles);
-  else if (avec)    hipLaunchKernelGGL((transpose_kernel<false, true>), grid, block, 0, st, D, d_stride, A, a_stride, nrows, ncols, tiles_r, ntiles);
-  else              hipLaunchKernelGGL((transpose_kernel<false, false>), grid, block, 0, st, D, d_stride, A, a_stride, nrows, ncols, tiles_r, ntiles);
-  return (int)hipGetLastError();
+  return (int)gf2_launch_transpose_tiles((hipStream_t)stream, D, d_stride, 0, A, a_stride, 0, nrows, ncols, 1);
 }
