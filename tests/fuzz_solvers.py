@@ -14,12 +14,13 @@ import numpy as np  # noqa: E402
 import m4ri_amd  # noqa: E402
 from m4ri_amd.mzd import Mzd  # noqa: E402
 import cpu_libs  # noqa: E402
+from ple_paths import clear  # noqa: E402
 
 
 def structured(rng, m, n):
     A = Mzd.random(m, n, int(rng.integers(1, 1 << 30)))
     w = A.valid_words()
-    kind = rng.integers(0, 6)
+    kind = rng.integers(0, 7)
     if kind == 1:    # zero word columns
         for _ in range(rng.integers(1, 4)):
             w[:, rng.integers(0, w.shape[1])] = 0
@@ -38,6 +39,10 @@ def structured(rng, m, n):
             c = int(c)
             bit = (w[:, (c - 1) // 64] >> np.uint64((c - 1) % 64)) & np.uint64(1)
             w[:, c // 64] = (w[:, c // 64] & ~(np.uint64(1) << np.uint64(c % 64))) | (bit << np.uint64(c % 64))
+    elif kind == 6:  # shelf: the top D rows empty in a run of columns, so the pivots there lie D rows below the rank position (ple_paths.py)
+        D = min(int(rng.choice([70, 130, 1000, 1030, 1100, 2100])), m)
+        c0 = int(rng.integers(0, n))
+        clear(w, D, c0, int(rng.integers(c0, n)) + 1)
     return A, int(kind)
 
 
