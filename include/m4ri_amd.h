@@ -275,23 +275,50 @@ double m4ri_amd_model_seconds_batch(int64_t m, int64_t l, int64_t n, int levels,
 int m4ri_amd_xor_dev(word *C, int64_t c_stride, const word *A, int64_t a_stride, const word *B,
                      int64_t b_stride, int64_t rows, int64_t ncols, void *stream);
 /* B (mb x nb, device) <- L^-1 B / U^-1 B in place, T (mb x mb, device) unit triangular -- the device twins of
- * _mzd_trsm_lower_left / _mzd_trsm_upper_left: halves recursion down to 64-row blocks, every update one
- * m4ri_amd_mul_dev on views.  Bits of B at column >= nb: zero in, zero out. */
+ * _mzd_trsm_lower_left / _mzd_trsm_upper_left: halves recursion down to 512-row blocks solved through their inverses (64 rows
+ * or fewer: one substitution kernel), every update one m4ri_amd_mul_dev on views; `cutoff` is handed to each of them and is a
+ * hint (every value >= 0 gives the same bits).
+ * Memory: of T only the bits strictly inside its triangle are read (diagonal, other triangle and the words from words(mb) to
+ * t_stride never); T is never written.  Above 64 rows the caller keeps T's bits at column >= mb zero (its blocks go to the
+ * multiply engine as operands); up to 64 rows they are not read.  Of B the rows 0 .. mb-1, words 0 .. words(nb)-1 are read and
+ * written.  Bits of B at column >= nb: above 64 rows zero in, zero out (the last word is written whole); up to 64 rows they are
+ * kept, whatever they are.  The words from words(nb) to b_stride of a row and the rows before and after B are never written.
+ * T and B must not overlap.  Any word alignment and any stride >= the width, odd ones included.
+ * Asynchronous on `stream`; above 64 rows the calls share grow-only scratch per device (growing it synchronises the device)
+ * and a solve on another stream than the previous one first waits, on the device, for that one.  hipErrorInvalidValue, before
+ * any HIP call, for mb < 0, nb < 0 or cutoff < 0. */
 int m4ri_amd_trsm_lower_left_dev(const word *L, int64_t t_stride, word *B, int64_t b_stride, int64_t mb, int64_t nb, int cutoff,
                                  void *stream);
 int m4ri_amd_trsm_upper_left_dev(const word *U, int64_t t_stride, word *B, int64_t b_stride, int64_t mb, int64_t nb, int cutoff,
                                  void *stream);
-/* B (mb x nb) <- B U^-1 / B L^-1, T (nb x nb, device) unit triangular: the right-hand twins. */
+/* B (mb x nb) <- B U^-1 / B L^-1, T (nb x nb, device) unit triangular: the right-hand twins (64 columns or fewer: one kernel,
+ * a thread per row of B).  The same memory rules with T nb x nb and the threshold at 64 columns: T's proper triangle only is
+ * read, never written, its bits at column >= nb zero above 64 columns and not read up to 64; rows 0 .. mb-1, words 0 ..
+ * words(nb)-1 of B read and written, bits of B at column >= nb zero in, zero out above 64 columns and kept whatever they are up
+ * to 64; padding words and neighbouring rows never written; asynchronous on `stream` with the same shared scratch above 64
+ * columns; hipErrorInvalidValue, before any HIP call, for mb < 0, nb < 0 or cutoff < 0. */
 int m4ri_amd_trsm_upper_right_dev(const word *U, int64_t t_stride, word *B, int64_t b_stride, int64_t mb, int64_t nb, int cutoff,
                                   void *stream);
 int m4ri_amd_trsm_lower_right_dev(const word *L, int64_t t_stride, word *B, int64_t b_stride, int64_t mb, int64_t nb, int cutoff,
                                   void *stream);
-/* Device twins of mzd_process_rowsN / mzd_make_table (elim.hip): streaming, HBM-bound.  kbits[t]: bits of group
- * t (lowest first); L[t]: 2^kbits[t] table row numbers; idx_scratch: 6 * (stoprow - startrow) int32; jstar: see
- * elim.hip (all zeros when rows r .. r+k-1 exist).  Asynchronous on `stream`. */
+/* Device twin of mzd_process_rowsN (elim.hip): streaming, HBM-bound.  kbits[t]: bits of group t (lowest first); L[t]:
+ * 2^kbits[t] table row numbers; idx_scratch: 6 * (stoprow - startrow) int32.  kbits, T, t_stride and L are HOST arrays of
+ * `ntables` entries (T[t], L[t] and idx_scratch device pointers).  Reads the strip of every row of [startrow, stoprow) and the
+ * words startcol/64 .. width-1 of the table rows it selects; XORs whole words onto the words startcol/64 .. width-1 of those
+ * rows of M (the last word included: a table row with a clean tail leaves M's tail as it was) and writes nothing else -- not
+ * the words before startcol/64, not the words from `width` to `stride`, no other row, no table.  16-byte accesses are used when
+ * M and every table allow them (16-byte aligned bases, even strides, startcol/64 and width - startcol/64 even), single words
+ * otherwise: any alignment is legal.  Asynchronous on `stream`.  hipErrorInvalidValue, before any HIP call, for ntables
+ * outside 1 .. 6, startrow < 0, stoprow < startrow or startcol < 0. */
 int m4ri_amd_process_rows_dev(word *M, int64_t stride, int64_t width, int64_t startrow, int64_t stoprow, int64_t startcol, int ntables,
                               const int32_t *kbits, const word *const *T, const int64_t *t_stride, const int32_t *const *L,
                               int32_t *idx_scratch, void *stream);
+/* Device twin of mzd_make_table (elim.hip).  jstar: 2^k int32 on the device, see elim.hip (all zeros when rows r .. r+k-1
+ * exist).  Reads rows r .. r+k-1 of M below m_rows (never written) and Tin; writes rows 1 .. 2^k - 1 of Tout, words c/64 ..
+ * words(ncols)-1: the first of them masked below column c, the last to ncols columns (tail written zero); a row whose source
+ * row does not exist is copied from Tin, tail included (Tin == Tout: it stays).  Tin and Tout have the stride t_stride; Tin is
+ * not written unless it is Tout.  Row 0, the words before c/64 and the words from words(ncols) to t_stride of Tout are never
+ * written.  Asynchronous on `stream`.  hipErrorInvalidValue, before any HIP call, for k outside 1 .. 16 or ncols <= 0. */
 int m4ri_amd_make_table_dev(const word *M, int64_t m_stride, int64_t m_rows, int64_t ncols, int64_t r, int64_t c, int k, const word *Tin,
                             word *Tout, int64_t t_stride, const int32_t *jstar, void *stream);
 /* PLE of a device matrix in place (bits at column >= ncols zero in, zero out).  P (nrows entries) and Q (ncols
@@ -306,19 +333,35 @@ int m4ri_amd_ple_dev(word *A, int64_t stride, int64_t nrows, int64_t ncols, int3
 /* PLUQ in place (m4ri/ple.c:50-60): the PLE, then the column step below on the first `rank` rows.  Blocking. */
 int m4ri_amd_pluq_dev(word *A, int64_t stride, int64_t nrows, int64_t ncols, int32_t *P, int32_t *Q, int32_t *rank_out,
                       int64_t recursion_cutoff, void *stream);
-/* Device twins of the drivers over PLUQ (solve.hip); P, Q: HOST arrays; *retval: 0 / -1 as mzd_solve_left.  Blocking. */
+/* Device twins of the drivers over PLUQ (solve.hip); P, Q: HOST arrays; *retval: 0 / -1 as mzd_solve_left.  Blocking: on
+ * return the work is complete and `stream` idle.  Memory rules common to the five functions below: every matrix keeps the Part
+ * 2 invariant (bits beyond its last column zero in, zero out); of a matrix that is written, only its own rows and the words
+ * below its width are -- the words from the width to the stride of a row and the rows before and after it never; any word
+ * alignment, any stride >= width. */
+/* The row transpositions (i, P[i]), i < min(length, nrows), ascending (trans == 0) or descending: whole rows of words(ncols)
+ * words move, each with its own tail bits.  hipErrorInvalidValue, before any HIP call, for negative sizes, P == NULL or an
+ * entry of P outside the rows. */
 int m4ri_amd_apply_p_left_dev(word *A, int64_t stride, int64_t nrows, int64_t ncols, const int32_t *P, int64_t length, int trans, void *stream);
+/* A (m x n, its PLUQ), rank, P, Q are read only; B (b_rows x b_cols, b_rows >= max(m, n)) <- the solution, as
+ * _mzd_pluq_solve_left leaves it: also on *retval == -1 (inconsistency_check != 0 and no solution), where B holds the
+ * reference's state at that point (solve.c:81-121), not its input.  hipErrorInvalidValue, before any HIP call, for negative
+ * sizes, a NULL P, Q or retval, rank > min(m, n), b_rows < max(m, n) or cutoff < 0. */
 int m4ri_amd_pluq_solve_left_dev(const word *A, int64_t a_stride, int64_t m, int64_t n, int32_t rank, const int32_t *P, const int32_t *Q, word *B,
                                  int64_t b_stride, int64_t b_rows, int64_t b_cols, int cutoff, int inconsistency_check, int *retval, void *stream);
+/* A <- its PLUQ, then the above.  With inconsistency_check != 0 and b_rows > m, a set bit in the rows m+1 .. b_rows-1 of B
+ * gives *retval = -1 before anything is computed: A and B are then untouched, byte for byte.  hipErrorInvalidValue, before any
+ * HIP call, for negative sizes, retval == NULL, b_rows < max(m, n) or cutoff < 0. */
 int m4ri_amd_solve_left_dev(word *A, int64_t a_stride, int64_t m, int64_t n, word *B, int64_t b_stride, int64_t b_rows, int64_t b_cols, int cutoff,
                             int inconsistency_check, int *retval, void *stream);
+/* A <- its PLUQ; R (n x (n - rank), its valid words ZERO on entry) <- the basis, whole words of its rows written; rank == n: R
+ * is not touched.  hipErrorInvalidValue, before any HIP call, for negative sizes, rank_out == NULL or cutoff < 0. */
 int m4ri_amd_kernel_left_pluq_dev(word *A, int64_t a_stride, int64_t m, int64_t n, word *R, int64_t r_stride, int cutoff, int32_t *rank_out,
                                   void *stream);
+/* A is read only (bits beyond column n zero); the n x words(n) words of Binv are written whole, whatever they held, the bits
+ * beyond column n zero.  Binv must not overlap A.  hipErrorInvalidValue, before any HIP call, for n < 0. */
 int m4ri_amd_inv_dev(word *Binv, int64_t b_stride, const word *A, int64_t a_stride, int64_t n, void *stream);
-/* Device twins of mzd_transpose and mzd_trtri_upper.  m4ri_amd_transpose_dev: D (ncols x nrows) <- A^T, D must not
- * overlap A; one HBM-bound launch (A read once, D written once, whole 128-byte lines on both sides); asynchronous.
- * m4ri_amd_trtri_upper_dev: U (n x n) <- U^-1, only the bits strictly above the diagonal are read and written;
- * asynchronous on `stream`, scratch grow-only per device. */
+/* Device twin of mzd_transpose: D (ncols x nrows) <- A^T, D must not overlap A; one HBM-bound launch (A read once, D written
+ * once, whole 128-byte lines on both sides); asynchronous. */
 int m4ri_amd_transpose_dev(word *D, int64_t d_stride, const word *A, int64_t a_stride, int64_t nrows, int64_t ncols, void *stream);
 /* `batch` transposes of SMALL matrices of one shape, D_b <- (A_b)^T (transpose_batch.hip): A_b nrows x ncols at A + b * a_bs words,
  * rows a_stride words apart; D_b ncols x nrows at D + b * d_bs words, rows d_stride words apart.  The valid bits of D_b become the
@@ -342,8 +385,18 @@ int m4ri_amd_transpose_batch_dev(word *D, int64_t d_stride, int64_t d_bs, const 
  * M4RI_AMD_TRANSPOSE_BATCH_PATH1_MAX (read per call, clamped to [64, 1024] in multiples of 64) replaces T1 in the routing of
  * out-of-place calls; this function does not read it. */
 int m4ri_amd_plan_transpose_batch(int64_t nrows, int64_t ncols);
+/* Device twin of mzd_trtri_upper: U (n x n) <- U^-1.  Only the bits strictly above the diagonal (and below column n) are read
+ * and written: the diagonal, the lower triangle, the bits beyond column n of a row's last word (whatever they are), the words
+ * from words(n) to `stride` and the rows around U come back untouched.  Any word alignment, any stride >= words(n).
+ * Asynchronous on `stream`; scratch grow-only per device (growing it synchronises the device), one call at a time per device:
+ * two calls in flight on different streams are NOT ordered against each other.  hipErrorInvalidValue, before any HIP call, for
+ * n < 0. */
 int m4ri_amd_trtri_upper_dev(word *U, int64_t stride, int64_t n, void *stream);
-/* Device twins of mzd_echelonize* and mzd_apply_p_right{,_trans} (echelon.hip).  P: HOST array.  Blocking. */
+/* Device twin of mzd_echelonize* (echelon.hip): A (nrows x ncols) <- its (reduced, full != 0) row echelon form, *rank_out the
+ * rank.  Blocking.  Bits at column >= ncols: zero in, zero out (rows are written in whole words, last word included).  Only rows
+ * 0 .. nrows-1, words 0 .. words(ncols)-1 are written: never the words from the width to `stride`, never a row before or after
+ * A.  Any word alignment, any stride >= width.  hipErrorInvalidValue, before any HIP call, for negative sizes or rank_out ==
+ * NULL. */
 int m4ri_amd_echelonize_dev(word *A, int64_t stride, int64_t nrows, int64_t ncols, int full, int32_t *rank_out, void *stream);
 /* `batch` independent (reduced) row echelon forms in place (echelon_batch.hip).  Member b is the nrows x ncols matrix at
  * A + b * a_bs (words), rows `stride` words apart; each comes out bit-identical to m4ri_amd_echelonize_dev (mzd_echelonize) with
@@ -449,13 +502,24 @@ int m4ri_amd_pluq_solve_left_batch_dev(const word *A, int64_t a_stride, int64_t 
  * row of A, within 160 KiB -- only B is staged, so the boundary lies above m4ri_amd_plan_solve_batch's); 2 members one by one through
  * m4ri_amd_pluq_solve_left_dev on scratch copies (blocking) */
 int m4ri_amd_plan_pluq_solve_batch(int64_t m, int64_t n, int64_t k);
+/* Device twin of mzd_apply_p_right{,_trans} (echelon.hip): the column transpositions (i, P[i]), i < min(length, ncols),
+ * descending (trans == 0, A * P) or ascending (A * P^T), on every row.  P: HOST array.  Blocking.  Whole words from the first to
+ * the last word that holds a moved column are rewritten: bits at column >= ncols zero in, zero out; the words from the width to
+ * `stride` and other rows never written.  Rows up to 64 KiB wide are staged in LDS, wider ones gathered from a copy in global
+ * memory, 4096 rows at a time.  hipErrorInvalidValue, before any HIP call, for negative sizes, P == NULL or an entry of P outside
+ * the columns. */
 int m4ri_amd_apply_p_right_dev(word *A, int64_t stride, int64_t nrows, int64_t ncols, const int32_t *P, int64_t length, int trans, void *stream);
 /* Row r <- its columns under the transpositions (i, Q[i]), i = r+1 .. ncols-1 ascending (mzd_apply_p_right_trans_tri,
- * m4ri/mzp.c:279-293).  Q: HOST array, ncols entries, Q[i] >= i.  Blocking. */
+ * m4ri/mzp.c:279-293).  Q: HOST array, ncols entries, Q[i] >= i.  Blocking.  Whole words of the rows 0 .. nrows-1 are
+ * rewritten, from the row's diagonal word to the last word that holds a moved column: bits at column >= ncols zero in, zero
+ * out; the words from the width to `stride` and other rows are never written.  hipErrorInvalidValue, before any HIP call, for
+ * negative sizes, Q == NULL or an entry Q[i] outside i .. ncols-1. */
 int m4ri_amd_apply_p_right_trans_tri_dev(word *A, int64_t stride, int64_t nrows, int64_t ncols, const int32_t *Q, void *stream);
 /* Deterministic fill: word (r, j) = splitmix64 stream `seed`, output number r*width + j, last word
  * masked -- the order mzd_randomize_custom fills a matrix in (mzd.c:1282-1292). */
 int m4ri_amd_fill_dev(word *M, int64_t stride, int64_t rows, int64_t ncols, uint64_t seed, void *stream);
+/* Clears the bits at column >= ncols of word words(ncols)-1 of each of the `rows` rows and writes nothing else (ncols a multiple
+ * of 64: nothing at all).  Asynchronous on `stream`. */
 int m4ri_amd_mask_tail_dev(word *M, int64_t stride, int64_t rows, int64_t ncols, void *stream);
 
 /* Schedule statistics of the most recent m4ri_amd_mul_dev / m4ri_amd_m4rm_dev on this thread's

@@ -177,7 +177,7 @@ int m4ri_amd_pluq_solve_left_dev(const word *A, int64_t a_stride, int64_t m, int
 // included), B <- a solution X of A X = B with the undefined rows zero; *retval = -1 when the check finds none.
 int m4ri_amd_solve_left_dev(word *A, int64_t a_stride, int64_t m, int64_t n, word *B, int64_t b_stride, int64_t b_rows, int64_t b_cols, int cutoff,
                             int inconsistency_check, int *retval, void *stream) {
-  if (!retval || m < 0 || n < 0 || b_rows < m || b_rows < n) return (int)hipErrorInvalidValue;
+  if (!retval || m < 0 || n < 0 || b_rows < m || b_rows < n || b_cols < 0 || cutoff < 0) return (int)hipErrorInvalidValue;
   hipStream_t st = (hipStream_t)stream;
   *retval = 0;
   if (inconsistency_check && b_rows > m) {  // :124-128 -- the window starts one row late in the reference, so does this
@@ -196,7 +196,7 @@ int m4ri_amd_solve_left_dev(word *A, int64_t a_stride, int64_t m, int64_t n, wor
 // *rank_out = the rank; R is untouched when the rank is n.
 int m4ri_amd_kernel_left_pluq_dev(word *A, int64_t a_stride, int64_t m, int64_t n, word *R, int64_t r_stride, int cutoff, int32_t *rank_out,
                                   void *stream) {
-  if (!rank_out || m < 0 || n < 0) return (int)hipErrorInvalidValue;
+  if (!rank_out || m < 0 || n < 0 || cutoff < 0) return (int)hipErrorInvalidValue;
   hipStream_t st = (hipStream_t)stream;
   std::vector<int32_t> P((size_t)(m > 0 ? m : 1)), Q((size_t)(n > 0 ? n : 1));
   int32_t r = 0;

@@ -17,7 +17,8 @@ def _gpu():
 
 
 SHAPES = [(1, 1), (2, 65), (57, 10), (64, 64), (65, 1), (100, 300), (128, 64), (200, 513), (511, 129), (1000, 70), (2049, 200),
-          (2500, 131), (4096, 4096), (3000, 10000)]
+          (2500, 131), (4096, 4096), (3000, 10000),
+          (64, 4097)]  # the 64-row base kernel across two workgroups of 64 word columns, the second partial
 
 
 @pytest.mark.parametrize("mb,nb", SHAPES)
@@ -102,7 +103,8 @@ def test_large_solve_is_an_inverse(oracle):
 
 
 RIGHT_SHAPES = [(1, 1), (65, 2), (10, 57), (64, 64), (1, 65), (300, 100), (64, 128), (513, 200), (129, 511), (70, 1000), (200, 2049),
-                (131, 2500), (400, 4096)]
+                (131, 2500), (400, 4096),
+                (257, 64)]  # the 64-column base kernel across two workgroups of 256 rows
 
 
 def _unit_diag(T):
