@@ -385,6 +385,41 @@ int m4ri_amd_transpose_batch_dev(word *D, int64_t d_stride, int64_t d_bs, const 
  * M4RI_AMD_TRANSPOSE_BATCH_PATH1_MAX (read per call, clamped to [64, 1024] in multiples of 64) replaces T1 in the routing of
  * out-of-place calls; this function does not read it. */
 int m4ri_amd_plan_transpose_batch(int64_t nrows, int64_t ncols);
+/* The read side of the batched calls (reduce_batch.hip): what a caller wants to know about `batch` matrices of one shape without
+ * downloading them.  Conventions of the three calls below: member b of X is the nrows x ncols matrix at X + b * x_bs words, rows
+ * x_stride words apart; x_bs = 0 is one operand shared by all members.  Only the valid bits count: bits at columns >= ncols of a
+ * row's last word, the words from the width to the stride and the words between members are never looked at.  The operands are
+ * READ ONLY; every result array is DEVICE memory and is written whole, whatever it held.  Asynchronous on `stream` on every path of
+ * m4ri_amd_plan_reduce_batch: plain launches (on path 2 an initialisation of the outputs goes first, on the same stream), no
+ * allocation, no copy to the host, no synchronisation, no engine workspace, no engine lock; capturable.  All results are integer
+ * sums, minima and maxima: they do not depend on the order the hardware takes the rows in.
+ * hipErrorInvalidValue, before any HIP call, for negative sizes, strides or batch strides, nrows or ncols > INT32_MAX, a stride below
+ * words(ncols) or a NULL operand with non-empty members (the latter with batch > 0), no output at all, or an output array whose
+ * bytes meet the span (first member's start to last member's end) of an operand.  batch = 0 succeeds without touching anything.
+ * Empty members (nrows = 0 or ncols = 0) need no operand pointers; their results are still written: weights 0, lightest -1
+ * (nrows = 0) or 0 (ncols = 0 < nrows), first_row -1, first_nonzero = nrows, end_nonzero = 0. */
+/* Hamming weights of A_b (B == NULL; b_stride, b_bs ignored but not negative) or of A_b ^ B_b, the distance, which is never
+ * written anywhere.  total[b] (int64, batch entries): the member's weight.  row_weight[b * nrows + i] (int32): the weight of row i.
+ * lightest[b] (int64): (the smallest row weight << 32) | the index of the first row that has it; -1 for nrows = 0.  Each of the three
+ * may be NULL, not all.  A == B is allowed (zeros). */
+int m4ri_amd_weight_batch_dev(const word *A, int64_t a_stride, int64_t a_bs, const word *B, int64_t b_stride, int64_t b_bs, int64_t nrows,
+                              int64_t ncols, int64_t batch, int64_t *total, int32_t *row_weight, int64_t *lightest, void *stream);
+/* first_row[b] (int32, batch entries, required): the smallest i at which rows i of A_b and B_b differ in a valid bit, -1 if there
+ * is none: -1 <=> mzd_equal (m4ri/mzd.c:1314).  Both operands are required. */
+int m4ri_amd_mismatch_batch_dev(const word *A, int64_t a_stride, int64_t a_bs, const word *B, int64_t b_stride, int64_t b_bs, int64_t nrows,
+                                int64_t ncols, int64_t batch, int32_t *first_row, void *stream);
+/* first_nonzero[b] (int32): the first row of A_b with a set bit, nrows if there is none.  end_nonzero[b] (int32): one past the last
+ * such row, which is mzd_first_zero_row (m4ri/mzd.c:1826); 0 <=> mzd_is_zero (:1629).  Either may be NULL, not both. */
+int m4ri_amd_row_span_batch_dev(const word *A, int64_t a_stride, int64_t a_bs, int64_t nrows, int64_t ncols, int64_t batch,
+                                int32_t *first_nonzero, int32_t *end_nonzero, void *stream);
+/* which path the three calls above take for members of this shape (pure host arithmetic; -1 for negative sizes): 0 one wave per
+ * member, a row per lane, registers only (nrows <= 64 and at most W0 words per row; empty members count here); 1 one workgroup
+ * per member, reduced through LDS (nrows * words(ncols) <= T1); 2 a member's rows cut into chunks, a workgroup per chunk, the
+ * per-member results combined with global atomics.  W0 and T1 are measured bounds.  The environment variables
+ * M4RI_AMD_REDUCE_BATCH_PATH0_MAX (words per row, clamped to [0, 16]; 0 = no path 0) and M4RI_AMD_REDUCE_BATCH_PATH1_MAX (words per
+ * member, clamped to [0, 2^30]; 0 = no path 1) replace them in the routing of a call, read per call; this function does not read
+ * them. */
+int m4ri_amd_plan_reduce_batch(int64_t nrows, int64_t ncols);
 /* Device twin of mzd_trtri_upper: U (n x n) <- U^-1.  Only the bits strictly above the diagonal (and below column n) are read
  * and written: the diagonal, the lower triangle, the bits beyond column n of a row's last word (whatever they are), the words
  * from words(n) to `stride` and the rows around U come back untouched.  Any word alignment, any stride >= words(n).

@@ -170,6 +170,10 @@ SYMBOLS = {
     "m4ri_amd_transpose_dev": (_I, [_P, _I64, _P, _I64, _I64, _I64, _P]),
     "m4ri_amd_transpose_batch_dev": (_I, [_P, _I64, _I64, _P, _I64, _I64, _I64, _I64, _I64, _P]),
     "m4ri_amd_plan_transpose_batch": (_I, [_I64, _I64]),
+    "m4ri_amd_weight_batch_dev": (_I, [_P, _I64, _I64, _P, _I64, _I64, _I64, _I64, _I64, _P, _P, _P, _P]),
+    "m4ri_amd_mismatch_batch_dev": (_I, [_P, _I64, _I64, _P, _I64, _I64, _I64, _I64, _I64, _P, _P]),
+    "m4ri_amd_row_span_batch_dev": (_I, [_P, _I64, _I64, _I64, _I64, _I64, _P, _P, _P]),
+    "m4ri_amd_plan_reduce_batch": (_I, [_I64, _I64]),
     "m4ri_amd_m4rm_batch_dev": (_I, [_P, _I64, _I64, _P, _I64, _I64, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I, _P]),
     "m4ri_amd_mul_batch_dev": (_I, [_P, _I64, _I64, _P, _I64, _I64, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I, _I, _P]),
     "m4ri_amd_mul_small_batch_dev": (_I, [_P, _I64, _I64, _P, _I64, _I64, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I, _P]),
@@ -502,6 +506,39 @@ def plan_transpose_batch(nrows: int, ncols: int) -> int:
     """The path an out-of-place transpose_batch_dev takes for (nrows, ncols) (0 wave per member, 1 wave per 64 x 64 block, 2 the tile
     kernel). Host arithmetic."""
     return int(lib().m4ri_amd_plan_transpose_batch(nrows, ncols))
+
+
+def weight_batch_dev(A: int, a_stride: int, a_bs: int, B: int, b_stride: int, b_bs: int, nrows: int, ncols: int, batch: int, total: int = 0,
+                     row_weight: int = 0, lightest: int = 0, stream: int = 0) -> None:
+    """Hamming weights of `batch` matrices A_b (B = 0) or distances of A_b ^ B_b, X_b = X + b * x_bs words (x_bs = 0: one shared
+    operand), valid bits only, operands read only.  DEVICE outputs, each 0 = not wanted, not all: total (int64 per member), row_weight
+    (int32, batch * nrows), lightest (int64 per member: (smallest row weight << 32) | its first row).  Asynchronous, lock-free and
+    capturable on every path of plan_reduce_batch."""
+    _check(lib().m4ri_amd_weight_batch_dev(A, a_stride, a_bs, B or None, b_stride, b_bs, nrows, ncols, batch, total or None, row_weight or None,
+                                           lightest or None, stream), "m4ri_amd_weight_batch_dev")
+
+
+def mismatch_batch_dev(A: int, a_stride: int, a_bs: int, B: int, b_stride: int, b_bs: int, nrows: int, ncols: int, batch: int, first_row: int,
+                       stream: int = 0) -> None:
+    """first_row[b] (DEVICE int32 per member) = the first row at which A_b and B_b differ in a valid bit, -1 if none (mzd_equal).
+    Asynchronous, lock-free and capturable on every path of plan_reduce_batch."""
+    _check(lib().m4ri_amd_mismatch_batch_dev(A, a_stride, a_bs, B, b_stride, b_bs, nrows, ncols, batch, first_row or None, stream),
+           "m4ri_amd_mismatch_batch_dev")
+
+
+def row_span_batch_dev(A: int, a_stride: int, a_bs: int, nrows: int, ncols: int, batch: int, first_nonzero: int = 0, end_nonzero: int = 0,
+                       stream: int = 0) -> None:
+    """DEVICE int32 outputs per member, each 0 = not wanted, not both: first_nonzero[b] = the first non-zero row of A_b (nrows if none),
+    end_nonzero[b] = one past the last (mzd_first_zero_row; 0 = mzd_is_zero).  Asynchronous, lock-free and capturable on every path of
+    plan_reduce_batch."""
+    _check(lib().m4ri_amd_row_span_batch_dev(A, a_stride, a_bs, nrows, ncols, batch, first_nonzero or None, end_nonzero or None, stream),
+           "m4ri_amd_row_span_batch_dev")
+
+
+def plan_reduce_batch(nrows: int, ncols: int) -> int:
+    """The path weight_batch_dev, mismatch_batch_dev and row_span_batch_dev take for (nrows, ncols) (0 wave per member, 1 workgroup per
+    member, 2 chunks of rows and atomics). Host arithmetic."""
+    return int(lib().m4ri_amd_plan_reduce_batch(nrows, ncols))
 
 
 def model_seconds_batch(m: int, l: int, n: int, levels: int = -1, batch: int = 1) -> float:
