@@ -420,6 +420,63 @@ int m4ri_amd_row_span_batch_dev(const word *A, int64_t a_stride, int64_t a_bs, i
  * member, clamped to [0, 2^30]; 0 = no path 1) replace them in the routing of a call, read per call; this function does not read
  * them. */
 int m4ri_amd_plan_reduce_batch(int64_t nrows, int64_t ncols);
+/* Assembling, cutting and permuting the members of a batch where they are (assemble_batch.hip).  Conventions of the calls below, as
+ * of the other batched calls: member b of X is at X + b * x_bs words, its rows x_stride words apart; a batch stride of 0 on a
+ * READ-ONLY operand is one operand shared by all members.  Every call is asynchronous on `stream`: plain launches (several for a
+ * batch beyond one grid), no allocation, no copy to or from the host, no synchronisation, no engine workspace, no engine lock;
+ * capturable -- path 2 of the permutations alone allocates and BLOCKS.  Only the bits a call names as written are written: never
+ * a row's other bits in a partly covered word, the words from the width to the stride, the words between members or a read-only
+ * operand.  batch = 0 or an empty block succeeds without touching anything.  hipErrorInvalidValue, before any HIP call, for negative
+ * sizes, offsets, strides or batch strides, a stride that does not reach the last addressed column, written members that overlap
+ * each other, a written operand whose span (from the first member's first addressed word to the last member's last) meets a
+ * read-only operand's, or a NULL pointer with non-empty members. */
+/* For every member, bit (d_row + i, d_col + j) of D_b <- bit (a_row + i, a_col + j) of A_b, i < rows, j < cols; both column offsets
+ * may be any bit position (a 64-bit funnel shift per destination word; the first and the last word of a destination row are written
+ * under a mask).  Nothing else in D changes.  Of A only words that hold a bit of the block are read: when the last destination word
+ * of a row takes all its bits from one source word, the word after that source word is NOT read, so a block may end in the last word
+ * of an allocation.  16-byte accesses where both column offsets are multiples of 64, both first words 16-byte aligned and all four
+ * strides even.  mzd_submatrix is d_row = d_col = 0; mzd_concat and mzd_stack are two calls; mzd_copy is all four offsets 0;
+ * a_bs = 0 broadcasts one block into every member.  D must not meet A (no copy in place).  Also refused: cols above 2^36 - 64.
+ * Overlapping D members: batch > 1 and d_bs < (rows - 1) * d_stride + the words a destination row's block touches. */
+int m4ri_amd_copy_block_batch_dev(word *D, int64_t d_stride, int64_t d_bs, int64_t d_row, int64_t d_col, const word *A, int64_t a_stride,
+                                  int64_t a_bs, int64_t a_row, int64_t a_col, int64_t rows, int64_t cols, int64_t batch, void *stream);
+/* The triangles of A_b (nrows x ncols), k = min(nrows, ncols) (mzd_extract_u / mzd_extract_l, m4ri/mzd.h; the block copy's kernel
+ * with a mask per row).  upper != 0: D_b is k x ncols, bit (i, j) = A_b(i, j) for j > i and 0 for j < i.  upper == 0: D_b is
+ * nrows x k, bit (i, j) = A_b(i, j) for i > j and 0 for i < j.  The diagonal is 0 (diag == 0), 1 (diag == 1) or A_b(i, i)
+ * (diag == 2); any other diag is refused.  rank: a DEVICE int32 array of batch entries, or NULL; an entry outside 0 ... k is
+ * clamped.  With it, the upper form's rows i >= rank[b] are written zero, diagonal included, and the lower form's columns
+ * j >= rank[b] take nothing from A: they hold the diagonal rule's bit and zeros.  ALL valid bits of D_b are written, whatever they
+ * held; A's bits beyond column ncols are never looked at.  rank == NULL, diag == 2, square members: mzd_extract_u / mzd_extract_l
+ * bit for bit.  On what m4ri_amd_ple_batch_dev(pluq = 1) left, (upper = 0, diag = 1, rank) is L as nrows x k with identity columns
+ * behind the rank and (upper = 1, diag = 2, rank) is U as k x ncols with zero rows behind the rank, so L_b * U_b = P^T A Q^T is
+ * defined whatever the rank.  L of a plain PLE (pluq = 0: the columns under the pivots, not compressed) is out of scope.
+ * Also refused: nrows or ncols > INT32_MAX, D meeting rank. */
+int m4ri_amd_extract_tri_batch_dev(word *D, int64_t d_stride, int64_t d_bs, const word *A, int64_t a_stride, int64_t a_bs, int64_t nrows,
+                                   int64_t ncols, int64_t batch, int upper, int diag, const int32_t *rank, void *stream);
+/* mzd_apply_p_left{,_trans} on every member, in place, P in DEVICE memory: member b's transpositions are at P + b * p_bs entries
+ * (p_bs = 0: one permutation for all members) -- the arrays m4ri_amd_ple_batch_dev writes, with p_bs = nrows.  The row
+ * transpositions (i, P[i]), i < min(length, nrows), ascending (trans == 0) or descending.  Only the valid bits of a row move: the
+ * bits beyond column ncols stay at their row's position.  Entries P[i] < i are legal (the result is that of the sequence of swaps).
+ * An entry outside 0 ... nrows - 1 cannot be checked on the host: such a member is left untouched and status[b] = -1, else
+ * status[b] = 0 (status: DEVICE int32, batch entries, or NULL); no entry ever leads to an access outside the member.  With
+ * non-empty members and min(length, nrows) = 0 only status is written.  Also refused: A meeting P, status meeting A or P.
+ * Asynchronous on paths 0 and 1 of m4ri_amd_plan_perm_batch; path 2 downloads P, checks it on the host the same way, allocates and
+ * BLOCKS. */
+int m4ri_amd_apply_p_left_batch_dev(word *A, int64_t stride, int64_t a_bs, int64_t nrows, int64_t ncols, int64_t batch, const int32_t *P,
+                                    int64_t p_bs, int64_t length, int trans, int32_t *status, void *stream);
+/* mzd_apply_p_right{,_trans} the same way (m4ri_amd_ple_batch_dev's Q with p_bs = ncols): the column transpositions (i, P[i]),
+ * i < min(length, ncols), descending (trans == 0, A * P) or ascending (A * P^T), the order of m4ri_amd_apply_p_right_dev; an entry
+ * outside 0 ... ncols - 1 makes the member's status -1. */
+int m4ri_amd_apply_p_right_batch_dev(word *A, int64_t stride, int64_t a_bs, int64_t nrows, int64_t ncols, int64_t batch, const int32_t *P,
+                                     int64_t p_bs, int64_t length, int trans, int32_t *status, void *stream);
+/* which path the two calls above take (right != 0: m4ri_amd_apply_p_right_batch_dev; pure host arithmetic; -1 for negative sizes):
+ * 0 one wave per member, a row per lane, the index in registers, rows moved by ds_bpermute and columns between two register
+ * transposes (nrows, ncols <= 64); 1 one workgroup per member, the member's nrows * words(ncols) words plus 8 bytes per row (right:
+ * per column) of P and index and 8 bytes of flags in LDS within 160 KiB; 2 members one by one through m4ri_amd_apply_p_left_dev /
+ * m4ri_amd_apply_p_right_dev (blocking).  The environment variables M4RI_AMD_PERM_BATCH_PATH0_MAX (the largest side of path 0,
+ * clamped to [0, 64]; 0 = no path 0) and M4RI_AMD_PERM_BATCH_PATH1_MAX (the LDS bytes of path 1, clamped to [0, 163840]; 0 = no
+ * path 1) replace the bounds in the routing of a call, read per call; this function does not read them. */
+int m4ri_amd_plan_perm_batch(int64_t nrows, int64_t ncols, int right);
 /* Device twin of mzd_trtri_upper: U (n x n) <- U^-1.  Only the bits strictly above the diagonal (and below column n) are read
  * and written: the diagonal, the lower triangle, the bits beyond column n of a row's last word (whatever they are), the words
  * from words(n) to `stride` and the rows around U come back untouched.  Any word alignment, any stride >= words(n).
@@ -505,7 +562,10 @@ int m4ri_amd_plan_kernel_batch(int64_t m, int64_t n);
  * overlapping members (batch > 1 and a_bs < (nrows - 1) * stride + words(ncols)), a NULL A with a non-empty member, rank == NULL with
  * batch > 0, P == NULL with batch * nrows > 0 or Q == NULL with batch * ncols > 0.  batch = 0 succeeds without touching anything;
  * nrows = 0 or ncols = 0 writes rank 0 and the identity to P and Q and no matrix word.  Asynchronous on `stream` (one launch, no
- * allocation, no copy, no host synchronisation) on paths 0-2 of m4ri_amd_plan_ple_batch; path 3 allocates and BLOCKS. */
+ * allocation, no copy, no host synchronisation) on paths 0-2 of m4ri_amd_plan_ple_batch; path 3 allocates and BLOCKS.
+ * To use P, Q and the factors without a download: m4ri_amd_extract_tri_batch_dev gives L and U of every member,
+ * m4ri_amd_apply_p_left_batch_dev / m4ri_amd_apply_p_right_batch_dev take P and Q as they lie here (p_bs = nrows / ncols), and
+ * m4ri_amd_pluq_solve_left_batch_dev solves from them. */
 int m4ri_amd_ple_batch_dev(word *A, int64_t stride, int64_t a_bs, int64_t nrows, int64_t ncols, int64_t batch, int pluq, int32_t *P, int32_t *Q,
                            int32_t *rank, void *stream);
 /* which path m4ri_amd_ple_batch_dev takes for members of this shape (pure host arithmetic; -1 for negative sizes): 0 one wave per

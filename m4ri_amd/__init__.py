@@ -174,6 +174,11 @@ SYMBOLS = {
     "m4ri_amd_mismatch_batch_dev": (_I, [_P, _I64, _I64, _P, _I64, _I64, _I64, _I64, _I64, _P, _P]),
     "m4ri_amd_row_span_batch_dev": (_I, [_P, _I64, _I64, _I64, _I64, _I64, _P, _P, _P]),
     "m4ri_amd_plan_reduce_batch": (_I, [_I64, _I64]),
+    "m4ri_amd_copy_block_batch_dev": (_I, [_P, _I64, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _P]),
+    "m4ri_amd_extract_tri_batch_dev": (_I, [_P, _I64, _I64, _P, _I64, _I64, _I64, _I64, _I64, _I, _I, _P, _P]),
+    "m4ri_amd_apply_p_left_batch_dev": (_I, [_P, _I64, _I64, _I64, _I64, _I64, _P, _I64, _I64, _I, _P, _P]),
+    "m4ri_amd_apply_p_right_batch_dev": (_I, [_P, _I64, _I64, _I64, _I64, _I64, _P, _I64, _I64, _I, _P, _P]),
+    "m4ri_amd_plan_perm_batch": (_I, [_I64, _I64, _I]),
     "m4ri_amd_m4rm_batch_dev": (_I, [_P, _I64, _I64, _P, _I64, _I64, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I, _P]),
     "m4ri_amd_mul_batch_dev": (_I, [_P, _I64, _I64, _P, _I64, _I64, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I, _I, _P]),
     "m4ri_amd_mul_small_batch_dev": (_I, [_P, _I64, _I64, _P, _I64, _I64, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I, _P]),
@@ -539,6 +544,66 @@ def plan_reduce_batch(nrows: int, ncols: int) -> int:
     """The path weight_batch_dev, mismatch_batch_dev and row_span_batch_dev take for (nrows, ncols) (0 wave per member, 1 workgroup per
     member, 2 chunks of rows and atomics). Host arithmetic."""
     return int(lib().m4ri_amd_plan_reduce_batch(nrows, ncols))
+
+
+def copy_block_batch_dev(D: int, d_stride: int, d_bs: int, d_row: int, d_col: int, A: int, a_stride: int, a_bs: int, a_row: int, a_col: int,
+                         rows: int, cols: int, batch: int, stream: int = 0) -> None:
+    """Bits (d_row + i, d_col + j) of every D_b <- bits (a_row + i, a_col + j) of A_b, i < rows, j < cols, X_b = X + b * x_bs words; any
+    bit offsets, nothing else of D written, a_bs = 0 broadcasts one block.  Asynchronous, lock-free and capturable."""
+    _check(lib().m4ri_amd_copy_block_batch_dev(D, d_stride, d_bs, d_row, d_col, A, a_stride, a_bs, a_row, a_col, rows, cols, batch, stream),
+           "m4ri_amd_copy_block_batch_dev")
+
+
+def submatrix_batch_dev(S: int, s_stride: int, s_bs: int, A: int, a_stride: int, a_bs: int, lowr: int, lowc: int, highr: int, highc: int,
+                        batch: int, stream: int = 0) -> None:
+    """mzd_submatrix for a batch: S_b ((highr - lowr) x (highc - lowc)) <- rows lowr .. highr-1, columns lowc .. highc-1 of A_b; lowc
+    may be any column."""
+    copy_block_batch_dev(S, s_stride, s_bs, 0, 0, A, a_stride, a_bs, lowr, lowc, highr - lowr, highc - lowc, batch, stream)
+
+
+def concat_batch_dev(C: int, c_stride: int, c_bs: int, A: int, a_stride: int, a_bs: int, a_cols: int, B: int, b_stride: int, b_bs: int, b_cols: int,
+                     nrows: int, batch: int, stream: int = 0) -> None:
+    """mzd_concat for a batch: C_b (nrows x (a_cols + b_cols)) <- [A_b | B_b]."""
+    copy_block_batch_dev(C, c_stride, c_bs, 0, 0, A, a_stride, a_bs, 0, 0, nrows, a_cols, batch, stream)
+    copy_block_batch_dev(C, c_stride, c_bs, 0, a_cols, B, b_stride, b_bs, 0, 0, nrows, b_cols, batch, stream)
+
+
+def stack_batch_dev(C: int, c_stride: int, c_bs: int, A: int, a_stride: int, a_bs: int, a_rows: int, B: int, b_stride: int, b_bs: int, b_rows: int,
+                    ncols: int, batch: int, stream: int = 0) -> None:
+    """mzd_stack for a batch: C_b ((a_rows + b_rows) x ncols) <- A_b on top of B_b."""
+    copy_block_batch_dev(C, c_stride, c_bs, 0, 0, A, a_stride, a_bs, 0, 0, a_rows, ncols, batch, stream)
+    copy_block_batch_dev(C, c_stride, c_bs, a_rows, 0, B, b_stride, b_bs, 0, 0, b_rows, ncols, batch, stream)
+
+
+def extract_tri_batch_dev(D: int, d_stride: int, d_bs: int, A: int, a_stride: int, a_bs: int, nrows: int, ncols: int, batch: int, upper: bool,
+                          diag: int = 2, rank: int = 0, stream: int = 0) -> None:
+    """The upper (D_b k x ncols) or lower (D_b nrows x k) triangle of every A_b, k = min(nrows, ncols); diag 0 / 1 / 2 = the diagonal
+    zero / one / A's; rank (DEVICE int32 per member, 0 = none) cuts U's rows and L's columns behind it.  On ple_batch_dev(pluq=1)'s
+    output (upper=False, diag=1, rank) is L and (upper=True, diag=2, rank) is U.  Asynchronous, lock-free and capturable."""
+    _check(lib().m4ri_amd_extract_tri_batch_dev(D, d_stride, d_bs, A, a_stride, a_bs, nrows, ncols, batch, int(bool(upper)), diag, rank or None, stream),
+           "m4ri_amd_extract_tri_batch_dev")
+
+
+def apply_p_left_batch_dev(A: int, stride: int, a_bs: int, nrows: int, ncols: int, batch: int, P: int, p_bs: int, length: int, trans: bool = False,
+                           status: int = 0, stream: int = 0) -> None:
+    """mzd_apply_p_left (trans: _trans) on every member, P a DEVICE int32 array, member b's at P + b * p_bs entries (0: shared);
+    status (DEVICE int32 per member, 0 = not wanted): -1 and the member untouched where an entry is out of range.  Asynchronous on
+    paths 0-1 of plan_perm_batch, blocking on path 2."""
+    _check(lib().m4ri_amd_apply_p_left_batch_dev(A, stride, a_bs, nrows, ncols, batch, P or None, p_bs, length, int(bool(trans)), status or None, stream),
+           "m4ri_amd_apply_p_left_batch_dev")
+
+
+def apply_p_right_batch_dev(A: int, stride: int, a_bs: int, nrows: int, ncols: int, batch: int, P: int, p_bs: int, length: int, trans: bool = False,
+                            status: int = 0, stream: int = 0) -> None:
+    """mzd_apply_p_right (trans: _trans) on every member; arguments as apply_p_left_batch_dev, the entries are columns."""
+    _check(lib().m4ri_amd_apply_p_right_batch_dev(A, stride, a_bs, nrows, ncols, batch, P or None, p_bs, length, int(bool(trans)), status or None, stream),
+           "m4ri_amd_apply_p_right_batch_dev")
+
+
+def plan_perm_batch(nrows: int, ncols: int, right: bool) -> int:
+    """The path apply_p_left_batch_dev (right False) / apply_p_right_batch_dev takes for members of this shape (0 wave, 1 LDS, 2 one by
+    one). Host arithmetic."""
+    return int(lib().m4ri_amd_plan_perm_batch(nrows, ncols, int(bool(right))))
 
 
 def model_seconds_batch(m: int, l: int, n: int, levels: int = -1, batch: int = 1) -> float:
