@@ -267,6 +267,32 @@ int m4ri_amd_mul_small_batch_dev(word *C, int64_t c_stride, int64_t c_bs, const 
  * M4RI_AMD_MUL_SMALL_BATCH_PATH1_MAX (read per call, clamped to [64, 256] in multiples of 64) replaces D1 in the routing of
  * m4ri_amd_mul_small_batch_dev; this function does not read it. */
 int m4ri_amd_plan_mul_small_batch(int64_t m, int64_t l, int64_t n);
+/* The same product with transposed operands, C_b (m x n) (+)= op(A_b) * op(B_b), op(A_b) m x l and op(B_b) l x n, in the same one
+ * launch and without a scratch buffer: A A^T, A^T A, E H^T.  trans_a != 0: A_b is STORED l x m (a_stride >= words(m)) and
+ * op(A_b) = A_b^T; trans_b != 0: B_b is STORED n x l (b_stride >= words(l)) and op(B_b) = B_b^T.  The kernels transpose each 64 x 64
+ * block of a stored operand in registers on its way into the product.  Everything else is m4ri_amd_mul_small_batch_dev's: the
+ * member addressing, a_bs = 0 / b_bs = 0 for one shared operand, A and B overlapping or the same pointer (A A^T with B == A and
+ * trans_b, A^T A with trans_a), l = 0, m = 0, n = 0 and batch = 0.  Memory: only the valid bits of C are written -- bits at columns >= n
+ * of a row's last word, the words from the width to c_stride of a row, the words between members, A and B never; bits of a STORED
+ * operand beyond its own last column (m for a transposed A, l for a transposed B) never influence a valid bit of C; no word of a
+ * stored operand outside its rows' widths is loaded.  Asynchronous on `stream`: one launch (several for a batch beyond one grid), no
+ * allocation, no copy, no engine workspace, no engine lock; capturable.  hipErrorInvalidValue, before any HIP call, for the
+ * conditions of m4ri_amd_mul_small_batch_dev with the widths and the row counts of the operands AS STORED: a_stride < words(m)
+ * under trans_a, b_stride < words(l) under trans_b, C's span meeting the span of the l rows of a transposed A or of the n rows of a
+ * transposed B.  With trans_a == trans_b == 0 the call IS m4ri_amd_mul_small_batch_dev, path 2 included.  With a transposed operand
+ * there is no path 2: where m4ri_amd_plan_mul_small_batch_op says 2 (or the override of the routing makes it so) the call returns
+ * hipErrorNotSupported before any HIP call and touches nothing.  Such a product is composed by the caller, who owns the scratch:
+ * m4ri_amd_transpose_batch_dev of every transposed operand into a buffer of its own (D_b = A_b^T: l x m -> m x l; n x l -> l x n),
+ * then m4ri_amd_m4rm_batch_dev (or m4ri_amd_mul_small_batch_dev) on the transposes, on the same stream. */
+int m4ri_amd_mul_small_batch_op_dev(word *C, int64_t c_stride, int64_t c_bs, const word *A, int64_t a_stride, int64_t a_bs, const word *B,
+                                    int64_t b_stride, int64_t b_bs, int64_t m, int64_t l, int64_t n, int64_t batch, int trans_a, int trans_b,
+                                    int add, void *stream);
+/* which path m4ri_amd_mul_small_batch_op_dev takes (pure host arithmetic; -1 for negative sizes).  trans_a == trans_b == 0:
+ * m4ri_amd_plan_mul_small_batch's answer.  Otherwise 0 for m, l, n <= 64; 1 for max(m, l, n) <= D1op, the measured bound up to which
+ * the fused call is not slower than transposing into scratch and multiplying (a multiple of 64 in [64, 256]; 64 = no such shape);
+ * 2 = not supported.  M4RI_AMD_MUL_SMALL_BATCH_PATH1_MAX replaces D1op in the routing of the call as it replaces D1; this function
+ * does not read it. */
+int m4ri_amd_plan_mul_small_batch_op(int64_t m, int64_t l, int64_t n, int trans_a, int trans_b);
 /* the time model's estimate for `batch` products m x l x n scheduled as one at `levels` levels (pure host arithmetic) */
 double m4ri_amd_model_seconds_batch(int64_t m, int64_t l, int64_t n, int levels, int64_t batch);
 /* C = A ^ B on rows x ncols bits: the device twin of _mzd_add (mzd.c:1471-1583).  In-place allowed,

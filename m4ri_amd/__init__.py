@@ -183,6 +183,8 @@ SYMBOLS = {
     "m4ri_amd_mul_batch_dev": (_I, [_P, _I64, _I64, _P, _I64, _I64, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I, _I, _P]),
     "m4ri_amd_mul_small_batch_dev": (_I, [_P, _I64, _I64, _P, _I64, _I64, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I, _P]),
     "m4ri_amd_plan_mul_small_batch": (_I, [_I64, _I64, _I64]),
+    "m4ri_amd_mul_small_batch_op_dev": (_I, [_P, _I64, _I64, _P, _I64, _I64, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I, _I, _I, _P]),
+    "m4ri_amd_plan_mul_small_batch_op": (_I, [_I64, _I64, _I64, _I, _I]),
     "m4ri_amd_model_seconds_batch": (ctypes.c_double, [_I64, _I64, _I64, _I, _I64]),
     "m4ri_amd_trtri_upper_dev": (_I, [_P, _I64, _I64, _P]),
     "m4ri_amd_echelonize_dev": (_I, [_P, _I64, _I64, _I64, _I, _P, _P]),
@@ -498,6 +500,21 @@ def mul_small_batch_dev(C: int, c_stride: int, c_bs: int, A: int, a_stride: int,
 def plan_mul_small_batch(m: int, l: int, n: int) -> int:
     """The path mul_small_batch_dev takes for (m, l, n) (0 wave per member, 1 wave per 64 x 64 block of C, 2 forwarded). Host arithmetic."""
     return int(lib().m4ri_amd_plan_mul_small_batch(m, l, n))
+
+
+def mul_small_batch_op_dev(C: int, c_stride: int, c_bs: int, A: int, a_stride: int, a_bs: int, B: int, b_stride: int, b_bs: int, m: int, l: int,
+                           n: int, batch: int, trans_a: bool = False, trans_b: bool = False, add: bool = False, stream: int = 0) -> None:
+    """mul_small_batch_dev with transposed operands, C_b (m x n) (+)= op(A_b) * op(B_b): trans_a: A_b is stored l x m, trans_b: B_b is
+    stored n x l (B == A allowed: A A^T, A^T A).  One launch, no scratch, only the valid bits of C written.  With a transposed operand
+    there is no path 2: beyond plan_mul_small_batch_op's bound the call raises (hipErrorNotSupported, 801) and touches nothing."""
+    _check(lib().m4ri_amd_mul_small_batch_op_dev(C, c_stride, c_bs, A, a_stride, a_bs, B, b_stride, b_bs, m, l, n, batch, int(bool(trans_a)),
+                                                 int(bool(trans_b)), int(bool(add)), stream), "m4ri_amd_mul_small_batch_op_dev")
+
+
+def plan_mul_small_batch_op(m: int, l: int, n: int, trans_a: bool = False, trans_b: bool = False) -> int:
+    """The path mul_small_batch_op_dev takes (0 wave per member, 1 wave per 64 x 64 block of C, 2 forwarded -- with a transposed operand:
+    not supported). Host arithmetic."""
+    return int(lib().m4ri_amd_plan_mul_small_batch_op(m, l, n, int(bool(trans_a)), int(bool(trans_b))))
 
 
 def transpose_batch_dev(D: int, d_stride: int, d_bs: int, A: int, a_stride: int, a_bs: int, nrows: int, ncols: int, batch: int, stream: int = 0) -> None:
