@@ -1,18 +1,29 @@
-// mzd_api.hip -- the drop-in boundary (include/m4ri_amd.h, part 1): M4RI's own entry points for the
-// multiply path, taking and returning host mzd_t matrices, implemented on the device engine.
+// mzd_api.hip -- the drop-in boundary (include/m4ri_amd.h, parts 1 and 3): M4RI's own entry points, taking and returning host
+// mzd_t matrices, implemented on the device engine.  Same names, argument meaning and fatal-error behaviour as the reference
+// (each entry point names its place there).  There is NO CPU fallback: a HIP failure is fatal, like every other error on this
+// path (misc.c:36-42).
 //
-// Reference interfaces replaced (same names, argument meaning and fatal-error behaviour):
-//   mzd_mul, mzd_addmul, _mzd_mul_even, _mzd_addmul_even, _mzd_addmul   m4ri/strassen.h:52-126
-//   _mzd_sqr_even, _mzd_addsqr_even                                      m4ri/strassen.c:210,528
-//   mzd_mul_m4rm, mzd_addmul_m4rm, _mzd_mul_m4rm                         m4ri/brilliantrussian.h:274-317
-//   mzd_mul_mp, mzd_addmul_mp                                            m4ri/mp.h:47,62
+// In this order:
+//   allocator         m4ri_amd_mzd_init / _free, the cache of large blocks, results allocated beside the upload (LateC)
+//   staging           one grow-only device arena per device, re-carved on every call; upload / download; the pinned host buffer
+//   residency         the table of pinned matrices (its entry points, m4ri_amd_pin and friends, are at the end of the file)
+//   HostCall          one host entry point running on the current device, and the placement of its operands
+//   products          mzd_mul, mzd_addmul, _mzd_mul_even ... _mzd_addsqr_even, mzd_mul_m4rm ..., mzd_mul_mp: run(), run_pipelined()
+//   solver family     TRSM, PLE / PLUQ, echelon forms, permutations, systems, kernels, inverses, transposes, triangular inverses
+//   table primitives  mzd_make_table, mzd_process_rows{,2..6}
 //
-// Each call: upload A and B (hipMemcpy2D straight out of the caller's rows, so windows cost
-// nothing extra) into a grow-only staging arena, zero the excess bits on the device, run the engine,
-// and copy C back touching only the words and bits the reference would touch (mzd.h:117-123).
-// Matrices pinned with m4ri_amd_pin (part 3 of the header) are not moved at all: operands are read
-// from, and results left in, their device copy -- windows into a pinned parent included.  There is NO CPU fallback: a HIP
-// failure is fatal, like every other error on this path (misc.c:36-42).
+// THE PLACEMENT RULE (place() is its only statement).  A matrix that is not pinned is STAGED: uploaded straight out of the
+// caller's rows (hipMemcpy2D, so windows cost nothing extra) with the bits beyond its last column cleared on the device, and
+// downloaded touching only the words and bits the reference would touch (mzd.h:117-123).  A pinned matrix, or a window of one, IS
+// its device copy and is used IN PLACE -- unless it is a window that shares its last word with neighbouring columns of the parent
+// (ncols off the word grid and narrower than the parent) AND the call writes it or needs the bits beyond its last column clean:
+// then it is staged as a masked device-to-device copy, and what was written goes back under the column mask.  Whatever a call
+// writes in a pinned parent leaves the host copy stale until m4ri_amd_sync / m4ri_amd_unpin.
+//
+// THE LOCKING RULE.  One lock per DEVICE (g_dev_mu) for everything that works on that device's arena, solver scratch and engine:
+// a HostCall holds the lock of the current device from its construction on, so threads that drive different GPUs run side by side
+// and threads on one GPU take turns.  g_pin_mu guards the LIST of pins only; an ENTRY is guarded by the lock of the device it lives
+// on (PinLock), whatever device the calling thread has current.  g_stats_mu guards the statistics.
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
 #include <cstdarg>
@@ -37,20 +48,18 @@ namespace {
 constexpr uint8_t FLAG_EXCESS = 0x2;  // mzd.h:144
 constexpr uint8_t FLAG_WINDOW = 0x4;  // mzd.h:150
 
-// Locks of the host entry points.  One per DEVICE for everything that works on that device's staging arena, solver scratch and
-// engine (ApiLock: host threads that drive different GPUs run side by side, threads on one GPU take turns -- round 3 had one lock
-// for all devices), one short lock for the table of pinned matrices, one for the statistics.
+// The locks of the host entry points (the locking rule above)
 constexpr int ARENA_DEVICES = 16;
 std::mutex g_dev_mu[ARENA_DEVICES];
 std::mutex g_pin_mu, g_stats_mu;
-struct ApiLock {
-  std::unique_lock<std::mutex> lk;
-  ApiLock() {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= ARENA_DEVICES) dev = 0;
-    lk = std::unique_lock<std::mutex>(g_dev_mu[dev]);
-  }
-};
+std::unique_lock<std::mutex> lock_device(int dev) {  // a device HIP could not name or this table does not hold: slot 0
+  return std::unique_lock<std::mutex>(g_dev_mu[dev >= 0 && dev < ARENA_DEVICES ? dev : 0]);
+}
+std::unique_lock<std::mutex> lock_current_device() {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) dev = 0;
+  return lock_device(dev);
+}
 
 // M4RI_AMD_STATS=1: at exit, print how many products went through the host entry points, the time
 // spent in them (transfers included) and the bytes moved over PCIe -- for judging what an LD_PRELOAD
@@ -417,23 +426,35 @@ std::list<Pin> g_pins;  // a list: entries stay where they are while other threa
 
 // Locking rule of the table: g_pin_mu guards the walk and the edits of the LIST; the lock of the device a pin lives on
 // (g_dev_mu[pin.device]) guards the ENTRY -- its device copy, its dev_newer flag, its removal.  A product holds that lock for its
-// whole duration (it runs on the pin's device or dies, operand()), so whoever changes or removes a pin takes the PIN'S device lock,
-// not the lock of whatever device its own thread happens to have current (PinLock).  A Pin* from find_pin is therefore valid for as
-// long as the caller holds the lock of the device the pin is on.
-Pin *find_pin(const mzd_t *M) {
+// whole duration (it runs on the pin's device or dies, HostCall::view()), so whoever changes or removes a pin takes the PIN'S device
+// lock, not the lock of whatever device its own thread happens to have current (PinLock).  A Pin* from find_pin is therefore valid
+// for as long as the caller holds the lock of the device the pin is on.
+bool covers(const Pin &p, const mzd_t *M) {  // M is the pinned matrix or a window into it: inside its block, with its layout
+  return M->data >= p.hbase && M->data < p.hbase + p.words && M->rowstride == p.rowstride;
+}
+
+Pin *pin_of(const mzd_t *M) {  // with g_pin_mu held
   if (!M || !M->data) return nullptr;
-  std::lock_guard<std::mutex> pl(g_pin_mu);
   for (Pin &p : g_pins)
-    if (M->data >= p.hbase && M->data < p.hbase + p.words && M->rowstride == p.rowstride) return &p;
+    if (covers(p, M)) return &p;
   return nullptr;
 }
 
-int pin_device(const mzd_t *M) {  // the device M's pinned parent lives on, -1 when there is none (read under the list's lock)
-  if (!M || !M->data) return -1;
+Pin *find_pin(const mzd_t *M) {
   std::lock_guard<std::mutex> pl(g_pin_mu);
-  for (Pin &p : g_pins)
-    if (M->data >= p.hbase && M->data < p.hbase + p.words && M->rowstride == p.rowstride) return p.device;
-  return -1;
+  return pin_of(M);
+}
+
+int pin_device(const mzd_t *M) {  // the device M's pinned parent lives on, -1 when there is none (read under the list's lock)
+  std::lock_guard<std::mutex> pl(g_pin_mu);
+  const Pin *p = pin_of(M);
+  return p ? p->device : -1;
+}
+
+void erase_pin(const Pin *p) {  // with the lock of the pin's device held
+  std::lock_guard<std::mutex> pl(g_pin_mu);
+  for (auto it = g_pins.begin(); it != g_pins.end(); ++it)
+    if (&*it == p) { g_pins.erase(it); break; }
 }
 
 // the pin of M with the lock of ITS device held and that device current (restored on the way out); p == nullptr: not pinned
@@ -462,23 +483,136 @@ struct PinLock {
   }
 };
 
-// device view of a host operand: inside its pinned parent, or a staged upload (copy == false: space only)
-DevMat operand(const mzd_t *M, bool copy, Pin **pin_out = nullptr) {
-  DevMat d;
-  Pin *p = find_pin(M);
-  if (pin_out) *pin_out = p;
-  if (p) {
-    int dev = 0;
-    HIPDIE(hipGetDevice(&dev));
-    if (p->device != dev) die("m4ri_amd: matrix pinned on device %d used while device %d is current\n", p->device, dev);
-    d.p      = p->dbase + (M->data - p->hbase);
-    d.stride = p->rowstride;
-    return d;
-  }
-  if (copy) upload(d, M);
-  else dev_alloc(d, M->nrows, M->ncols);
-  return d;
+// ---- one host call and the placement of its operands ------------------------------------------------------------------
+// What an entry point declares of each matrix (or plain buffer) it works on: decided once, by place(), and used for all three of
+// how many words of the arena it takes, how it is bound when the call is staged, and what happens to it when the call finishes.
+struct Operand {
+  enum Bind { VIEW, UPLOAD, SPACE, COPY_IN, WORDS };  // in the pinned parent | host rows sent up | room only | masked copy out of the parent | plain words
+  enum Finish { NOTHING, NEWER, COPY_BACK, DOWNLOAD };  // | parent written in place | masked copy into the parent (then NEWER) | rows sent down
+  DevMat d;  // valid after HostCall::stage()
+  const mzd_t *M = nullptr;
+  Pin *pin       = nullptr;
+  Bind bind      = SPACE;
+  Finish finish  = NOTHING;
+  int64_t rows = 0, ncols = 0;  // of the staged copy
+  size_t words = 0;             // of the arena: 0 in place
+  const void *src  = nullptr;   // WORDS: host data sent along
+  size_t src_bytes = 0;
+  bool staged() const { return bind != VIEW; }
+};
+
+// THE placement rule (the head of the file).  clean_tail: the call needs the bits beyond the last column zero in a matrix it only
+// reads; always_staged: the result is built apart from the matrix it goes to whatever that is (mzd_transpose, where DST may be A)
+Operand place(const mzd_t *M, bool read, bool write, bool clean_tail, bool always_staged) {
+  Operand o;
+  o.M = M; o.rows = M->nrows; o.ncols = M->ncols;
+  o.pin = find_pin(M);
+  const bool shares_last_word = o.pin && M->ncols % 64 != 0 && M->ncols != o.pin->ncols;
+  const bool staged = !o.pin || always_staged || (shares_last_word && (write || clean_tail));
+  o.bind   = !staged ? Operand::VIEW : !read ? Operand::SPACE : o.pin ? Operand::COPY_IN : Operand::UPLOAD;
+  o.finish = !write ? Operand::NOTHING : !o.pin ? Operand::DOWNLOAD : staged ? Operand::COPY_BACK : Operand::NEWER;
+  o.words  = staged ? dev_words(o.rows, o.ncols) : 0;
+  return o;
 }
+
+// A host entry point running on the current device: the device's lock taken and the device initialised on construction; operands
+// declared (in / inout / out / space / words), then stage() -- ONE reserve of what the declarations add up to, and the bindings in
+// the order declared -- then the device work on each operand's `d`, then finish(): the write-backs in the order declared, the
+// device synchronised, the call counted.  A body that returns before finish() has touched nothing.
+struct HostCall {
+  enum Kind { COUNTED, UNCOUNTED, PRODUCT };  // PRODUCT: the statistics' seconds run from the lock to the end of the call, which is counted there
+  std::unique_lock<std::mutex> lk;
+  int dev = 0;
+  const Kind kind;
+  timespec t0;
+  Operand ops[16];  // mzd_process_rows6: M, six tables with their index lists, the row indices
+  int nops = 0;
+
+  explicit HostCall(Kind k = COUNTED) : kind(k) {
+    const hipError_t no_device = hipGetDevice(&dev);
+    lk = lock_device(no_device ? 0 : dev);
+    if (kind == PRODUCT) clock_gettime(CLOCK_MONOTONIC, &t0);
+    if (no_device) die("m4ri_amd: HIP failure '%s' in hipGetDevice\n", hipGetErrorString(no_device));
+    HIPDIE(m4ri_amd_init(dev));
+  }
+  ~HostCall() {
+    if (kind != PRODUCT) return;
+    timespec t1;
+    clock_gettime(CLOCK_MONOTONIC, &t1);
+    std::lock_guard<std::mutex> sl(g_stats_mu);
+    g_api_stats.seconds += (double)(t1.tv_sec - t0.tv_sec) + 1e-9 * (double)(t1.tv_nsec - t0.tv_nsec);
+    g_api_stats.calls += 1;
+  }
+
+  Operand &declare(const Operand &o) {
+    if (nops == (int)(sizeof(ops) / sizeof(ops[0]))) die("m4ri_amd: too many operands in one call (internal error)\n");
+    return ops[nops++] = o;
+  }
+  Operand &in(const mzd_t *M, bool clean_tail = false) { return declare(place(M, true, false, clean_tail, false)); }
+  Operand &inout(mzd_t *M) { return declare(place(M, true, true, false, false)); }
+  Operand &out(mzd_t *M, bool always_staged = false) { return declare(place(M, false, true, false, always_staged)); }
+  Operand &space(int64_t rows, int64_t ncols) {  // a matrix of the call's own
+    Operand o;
+    o.rows = rows; o.ncols = ncols; o.words = dev_words(rows, ncols);
+    return declare(o);
+  }
+  static void download_to(Operand &o, mzd_t *R) {  // ... which finish() is to send down to a fresh host matrix, known only now
+    o.M = R; o.finish = Operand::DOWNLOAD;
+  }
+  Operand &words(size_t n, const void *src = nullptr, size_t src_bytes = 0) {  // plain words (256-byte granules), host data sent along
+    Operand o;
+    o.bind = Operand::WORDS; o.words = (n + 31) & ~(size_t)31; o.src = src; o.src_bytes = src_bytes;
+    return declare(o);
+  }
+
+  // M inside its pinned parent: the same offset into the device copy
+  DevMat view(const Pin &p, const mzd_t *M) const {
+    if (p.device != dev) die("m4ri_amd: matrix pinned on device %d used while device %d is current\n", p.device, dev);
+    return DevMat{p.dbase + (M->data - p.hbase), p.rowstride};
+  }
+
+  void stage() {
+    size_t need = 0;
+    for (int i = 0; i < nops; ++i) need += ops[i].words;
+    arena_reserve(need);
+    for (int i = 0; i < nops; ++i) {
+      Operand &o = ops[i];
+      switch (o.bind) {
+        case Operand::VIEW: o.d = view(*o.pin, o.M); break;
+        case Operand::UPLOAD: upload(o.d, o.M); break;
+        case Operand::SPACE: dev_alloc(o.d, o.rows, o.ncols); break;
+        case Operand::COPY_IN: {
+          dev_alloc(o.d, o.rows, o.ncols);
+          const DevMat src = view(*o.pin, o.M);
+          HIPDIE(hipMemcpy2DAsync(o.d.p, (size_t)o.d.stride * 8, src.p, (size_t)src.stride * 8, (size_t)o.M->width * 8, (size_t)o.M->nrows,
+                                  hipMemcpyDeviceToDevice, nullptr));
+          HIPDIE(m4ri_amd_mask_tail_dev(o.d.p, o.d.stride, o.M->nrows, o.M->ncols, nullptr));
+          break;
+        }
+        case Operand::WORDS:
+          o.d.p = g_arena.base + g_arena.used;
+          g_arena.used += o.words;
+          if (g_arena.used > g_arena.cap) die("m4ri_amd: staging arena overrun (internal error)\n");
+          if (o.src) HIPDIE(hipMemcpyAsync(o.d.p, o.src, o.src_bytes, hipMemcpyHostToDevice, nullptr));
+          break;
+      }
+    }
+  }
+
+  void finish() {
+    for (int i = 0; i < nops; ++i) {
+      Operand &o = ops[i];
+      if (o.finish == Operand::COPY_BACK) {
+        const DevMat dst = view(*o.pin, o.M);
+        HIPDIE(gf2_launch_copy_masked(nullptr, dst.p, dst.stride, o.d.p, o.d.stride, o.M->nrows, o.M->ncols));
+      }
+      if (o.finish == Operand::COPY_BACK || o.finish == Operand::NEWER) set_newer(*o.pin, true);  // the host copy is stale until m4ri_amd_sync / m4ri_amd_unpin
+      if (o.finish == Operand::DOWNLOAD) download(o.d, const_cast<mzd_t *>(o.M));
+    }
+    HIPDIE(hipDeviceSynchronize());
+    if (kind == COUNTED) { std::lock_guard<std::mutex> sl(g_stats_mu); g_api_stats.calls += 1; }
+  }
+};
 
 int norm_cutoff(int cutoff, const char *who) {  // strassen.c:348-354
   if (cutoff < 0) die("%s: cutoff must be >= 0.\n", who);
@@ -792,34 +926,26 @@ bool run_pipelined(mzd_t *C, const mzd_t *A, const mzd_t *B, bool add, int cutof
 // the whole product: strassen == true runs the Strassen-Winograd engine, false a single leaf
 // `late`: C == nullptr and the result is still being allocated (LateC; never with add, never empty)
 mzd_t *run(mzd_t *C, const mzd_t *A, const mzd_t *B, bool add, bool strassen, int cutoff, LateC *late = nullptr) {
-  ApiLock lk;
   const rci_t cm = A->nrows, cn = B->ncols;
   if (cm == 0 || cn == 0) return late ? late->get() : C;  // strassen.c:44
-  struct Timer {
-    timespec t0;
-    Timer() { clock_gettime(CLOCK_MONOTONIC, &t0); }
-    ~Timer() { timespec t1; clock_gettime(CLOCK_MONOTONIC, &t1); std::lock_guard<std::mutex> sl(g_stats_mu); g_api_stats.seconds += (double)(t1.tv_sec - t0.tv_sec) + 1e-9 * (double)(t1.tv_nsec - t0.tv_nsec); g_api_stats.calls += 1; }
-  } timer;
-  int dev = 0;
-  HIPDIE(hipGetDevice(&dev));
-  HIPDIE(m4ri_amd_init(dev));
+  HostCall call(HostCall::PRODUCT);
   const bool same = (A == B);
-  Pin *pinC = late ? nullptr : find_pin(C);
+  const bool all_on_host = !find_pin(C) && !find_pin(A) && !find_pin(B);  // (C == nullptr, a late result: not pinned)
   // products the launch / PCIe floor of a call would dominate: this library's own host Four Russians (small_host.cpp), on an
   // initialised device and only for matrices that live in host memory (a pinned operand is already on the GPU)
-  if (!late && !pinC && small_product_wanted(cm, A->ncols, cn, g_small_threshold.load()) && !find_pin(A) && !find_pin(B)) {
-    lk.lk.unlock();  // the routine needs no device state: small products of many threads run side by side
+  if (!late && all_on_host && small_product_wanted(cm, A->ncols, cn, g_small_threshold.load())) {
+    call.lk.unlock();  // the routine needs no device state: small products of many threads run side by side
     if (m4ri_amd_small_mul_host(C, A, B, add ? 1 : 0)) die("m4ri_amd: small product failed (internal error)\n");
     g_small_count += 1;
     return C;
   }
-  if (strassen && !same && !pinC && !find_pin(A) && !find_pin(B) && run_pipelined(C, A, B, add, cutoff, late)) return late ? late->get() : C;
+  if (strassen && !same && all_on_host && run_pipelined(C, A, B, add, cutoff, late)) return late ? late->get() : C;
   // nothing pinned and a few MiB in all: one asynchronous transfer each way through the device's pinned buffer
-  if (!late && !pinC && !find_pin(A) && !find_pin(B)) {
+  if (!late && all_on_host) {
     const size_t wa = dev_words(A->nrows, A->ncols), wb = same ? 0 : dev_words(B->nrows, B->ncols), wc = dev_words(cm, cn);
     if ((wa + wb + wc) * 8 <= SMALL_STAGE_BYTES) {
       arena_reserve(wa + wb + wc);
-      word *hs = host_stage(dev, wa + wb + wc);
+      word *hs = host_stage(call.dev, wa + wb + wc);
       DevMat dA, dB, dC;
       dev_alloc(dA, A->nrows, A->ncols);
       if (same) dB = dA; else dev_alloc(dB, B->nrows, B->ncols);
@@ -840,25 +966,12 @@ mzd_t *run(mzd_t *C, const mzd_t *A, const mzd_t *B, bool add, bool strassen, in
       return C;
     }
   }
-  // a pinned C whose last word is shared with other columns of its parent is computed in staging and
-  // merged under the column mask; otherwise the engine writes straight into the parent
-  const bool c_staged = !pinC || (cn % 64 != 0 && cn != pinC->ncols);
-  arena_reserve((find_pin(A) ? 0 : dev_words(A->nrows, A->ncols)) + ((same || find_pin(B)) ? 0 : dev_words(B->nrows, B->ncols)) +
-                (c_staged ? dev_words(cm, cn) : 0));
-  const DevMat dA = operand(A, true);
-  const DevMat dB = same ? dA : operand(B, true);
-  DevMat dC;
-  if (!c_staged) dC = operand(C, false);
-  else if (!pinC) { if (add) upload(dC, C); else dev_alloc(dC, cm, cn); }
-  else {
-    dev_alloc(dC, cm, cn);
-    if (add) {
-      const DevMat src = operand(C, false);
-      HIPDIE(hipMemcpy2DAsync(dC.p, (size_t)dC.stride * 8, src.p, (size_t)src.stride * 8, (size_t)C->width * 8, (size_t)C->nrows,
-                              hipMemcpyDeviceToDevice, nullptr));
-      HIPDIE(m4ri_amd_mask_tail_dev(dC.p, dC.stride, C->nrows, C->ncols, nullptr));
-    }
-  }
+  // the general path: every operand by the placement rule; a result still on its way (late) has room in staging and is first
+  // dereferenced when it is downloaded
+  Operand &a = call.in(A), &b = same ? a : call.in(B);
+  Operand &c = late ? call.space(cm, cn) : add ? call.inout(C) : call.out(C);
+  call.stage();
+  const DevMat dA = a.d, dB = b.d, dC = c.d;
   if (strassen)
     HIPDIE(m4ri_amd_mul_dev(dC.p, dC.stride, dA.p, dA.stride, dB.p, dB.stride, A->nrows, A->ncols, B->ncols, add, cutoff, nullptr));
   else
@@ -867,92 +980,26 @@ mzd_t *run(mzd_t *C, const mzd_t *A, const mzd_t *B, bool add, bool strassen, in
   // land in C's excess columns: clear them before the result leaves the staging buffer
   // (an unstaged pinned C spans its parent's full width, so its excess bits must be zero anyway:
   // mzd.h:115-121 -- mask there as well, or sync/unpin would carry the neighbours' bits to the host)
-  if (c_staged || cn % 64 != 0) HIPDIE(m4ri_amd_mask_tail_dev(dC.p, dC.stride, cm, cn, nullptr));
-  if (pinC) {
-    if (c_staged) {
-      const DevMat dst = operand(C, false);
-      HIPDIE(gf2_launch_copy_masked(nullptr, dst.p, dst.stride, dC.p, dC.stride, C->nrows, C->ncols));
-    }
-    set_newer(*pinC, true);  // the host copy is stale until m4ri_amd_sync / m4ri_amd_unpin
-  } else {
-    if (late) C = late->get();
-    download(dC, C);
-  }
-  HIPDIE(hipDeviceSynchronize());
+  if (c.staged() || cn % 64 != 0) HIPDIE(m4ri_amd_mask_tail_dev(dC.p, dC.stride, cm, cn, nullptr));
+  if (late) HostCall::download_to(c, C = late->get());
+  call.finish();
   return C;
-}
-
-// ---- in/out matrices of the solvers (B of a TRSM, A of a PLE) --------------------------------------
-// device view of a matrix that is read AND written: inside its pinned parent when the engine may write
-// whole last words there, otherwise a staged copy (uploaded, or copied out of the pinned parent)
-struct InOut {
-  DevMat d;
-  bool staged = true;
-  Pin *pin    = nullptr;
-};
-
-size_t inout_words(const mzd_t *M) {
-  Pin *p = find_pin(M);
-  const bool staged = !p || (M->ncols % 64 != 0 && M->ncols != p->ncols);
-  return staged ? dev_words(M->nrows, M->ncols) : 0;
-}
-
-InOut inout_begin(mzd_t *M) {
-  InOut io;
-  io.pin    = find_pin(M);
-  io.staged = !io.pin || (M->ncols % 64 != 0 && M->ncols != io.pin->ncols);
-  if (!io.staged) { io.d = operand(M, false); return io; }
-  if (!io.pin) { upload(io.d, M); return io; }
-  dev_alloc(io.d, M->nrows, M->ncols);
-  const DevMat src = operand(M, false);
-  HIPDIE(hipMemcpy2DAsync(io.d.p, (size_t)io.d.stride * 8, src.p, (size_t)src.stride * 8, (size_t)M->width * 8, (size_t)M->nrows,
-                          hipMemcpyDeviceToDevice, nullptr));
-  HIPDIE(m4ri_amd_mask_tail_dev(io.d.p, io.d.stride, M->nrows, M->ncols, nullptr));
-  return io;
-}
-
-void inout_end(InOut &io, mzd_t *M) {
-  if (io.pin) {
-    if (io.staged) {
-      const DevMat dst = operand(M, false);
-      HIPDIE(gf2_launch_copy_masked(nullptr, dst.p, dst.stride, io.d.p, io.d.stride, M->nrows, M->ncols));
-    }
-    set_newer(*io.pin, true);
-  } else {
-    download(io.d, M);
-  }
 }
 
 // B <- T^-1 B (left) or B <- B T^-1 (right) for a unit triangular T (triangular.c:41-514); T's other triangle and
 // diagonal are never read
 void run_trsm(bool upper, const mzd_t *T, mzd_t *B, int cutoff, bool right = false) {
-  ApiLock lk;
   if (B->nrows == 0 || B->ncols == 0 || (!right && B->nrows <= 1) || (right && B->ncols <= 1)) return;  // one unknown per system: X = B
-  int dev = 0;
-  HIPDIE(hipGetDevice(&dev));
-  HIPDIE(m4ri_amd_init(dev));
+  HostCall call;
   // T as the solver wants it: bits beyond its last column clean (trsm.hip: solve()).  A ragged window into a pinned parent
   // carries the parent's neighbouring columns in its last word: such a T is solved from a masked copy, like an in/out matrix
-  Pin *pinT             = find_pin(T);
-  const bool t_staged   = pinT && T->ncols % 64 != 0 && T->ncols != pinT->ncols;
-  arena_reserve(((pinT && !t_staged) ? 0 : dev_words(T->nrows, T->ncols)) + inout_words(B));
-  DevMat dT;
-  if (t_staged) {
-    dev_alloc(dT, T->nrows, T->ncols);
-    const DevMat src = operand(T, false);
-    HIPDIE(hipMemcpy2DAsync(dT.p, (size_t)dT.stride * 8, src.p, (size_t)src.stride * 8, (size_t)T->width * 8, (size_t)T->nrows, hipMemcpyDeviceToDevice, nullptr));
-    HIPDIE(m4ri_amd_mask_tail_dev(dT.p, dT.stride, T->nrows, T->ncols, nullptr));
-  } else {
-    dT = operand(T, true);
-  }
-  InOut io        = inout_begin(B);
-  if (right && upper) HIPDIE(m4ri_amd_trsm_upper_right_dev(dT.p, dT.stride, io.d.p, io.d.stride, B->nrows, B->ncols, cutoff, nullptr));
-  else if (right)     HIPDIE(m4ri_amd_trsm_lower_right_dev(dT.p, dT.stride, io.d.p, io.d.stride, B->nrows, B->ncols, cutoff, nullptr));
-  else if (upper)     HIPDIE(m4ri_amd_trsm_upper_left_dev(dT.p, dT.stride, io.d.p, io.d.stride, B->nrows, B->ncols, cutoff, nullptr));
-  else                HIPDIE(m4ri_amd_trsm_lower_left_dev(dT.p, dT.stride, io.d.p, io.d.stride, B->nrows, B->ncols, cutoff, nullptr));
-  inout_end(io, B);
-  HIPDIE(hipDeviceSynchronize());
-  { std::lock_guard<std::mutex> sl(g_stats_mu); g_api_stats.calls += 1; }
+  Operand &t = call.in(T, /*clean_tail=*/true), &b = call.inout(B);
+  call.stage();
+  typedef int (*trsm_dev_fn)(const word *, int64_t, word *, int64_t, int64_t, int64_t, int, void *);
+  static const trsm_dev_fn fn[2][2] = {{m4ri_amd_trsm_lower_left_dev, m4ri_amd_trsm_upper_left_dev},
+                                       {m4ri_amd_trsm_lower_right_dev, m4ri_amd_trsm_upper_right_dev}};
+  HIPDIE(fn[right][upper](t.d.p, t.d.stride, b.d.p, b.d.stride, B->nrows, B->ncols, cutoff, nullptr));
+  call.finish();
 }
 
 void pin_download(Pin &p) {
@@ -1087,7 +1134,7 @@ int m4ri_amd_small_product_wanted(int64_t m, int64_t l, int64_t n) { return smal
 
 // A + B + C bytes from which the host entry points pipeline a product over row slabs (0: never); returns the previous value
 int64_t m4ri_amd_set_host_pipeline(int64_t min_bytes) {
-  ApiLock lk;
+  const std::unique_lock<std::mutex> lk = lock_current_device();
   const int64_t old = (int64_t)g_pipeline_min_bytes;
   if (min_bytes >= 0) g_pipeline_min_bytes = (size_t)min_bytes;
   return old;
@@ -1125,23 +1172,18 @@ void _mzd_trsm_lower_right(mzd_t const *L, mzd_t *B, const int cutoff) { run_trs
 
 // ---- PLE decomposition: the reference's names, host mzd_t / mzp_t in and out ---------
 static rci_t run_ple(mzd_t *A, mzp_t *P, mzp_t *Q, bool pluq, bool russian) {
-  ApiLock lk;
-  int dev = 0;
-  HIPDIE(hipGetDevice(&dev));
-  HIPDIE(m4ri_amd_init(dev));
   if (A->nrows == 0 || A->ncols == 0) {
     for (rci_t i = 0; i < A->nrows; ++i) P->values[i] = i;
     for (rci_t j = 0; j < A->ncols; ++j) Q->values[j] = j;
     return 0;
   }
-  arena_reserve(inout_words(A));
-  InOut io = inout_begin(A);
+  HostCall call;
+  Operand &a = call.inout(A);
+  call.stage();
   int32_t rank = 0;
-  HIPDIE((pluq ? m4ri_amd_pluq_dev : m4ri_amd_ple_dev)(io.d.p, io.d.stride, A->nrows, A->ncols, P->values, Q->values, &rank,
+  HIPDIE((pluq ? m4ri_amd_pluq_dev : m4ri_amd_ple_dev)(a.d.p, a.d.stride, A->nrows, A->ncols, P->values, Q->values, &rank,
                                                        russian ? 0 : M4RI_AMD_PLE_CUTOFF, nullptr));
-  inout_end(io, A);
-  HIPDIE(hipDeviceSynchronize());
-  { std::lock_guard<std::mutex> sl(g_stats_mu); g_api_stats.calls += 1; }
+  call.finish();
   return rank;
 }
 
@@ -1166,32 +1208,22 @@ rci_t _mzd_pluq_russian(mzd_t *A, mzp_t *P, mzp_t *Q, int k) { (void)k; return r
 void mzd_apply_p_right_trans_tri(mzd_t *A, mzp_t const *Q) {  // mzp.c:279-293
   if (Q->length != A->ncols) die("mzd_apply_p_right_trans_tri: Permutation length (%d) must match A ncols (%d)\n", Q->length, A->ncols);
   if (A->nrows == 0 || A->ncols == 0) return;
-  ApiLock lk;
-  int dev = 0;
-  HIPDIE(hipGetDevice(&dev));
-  HIPDIE(m4ri_amd_init(dev));
-  arena_reserve(inout_words(A));
-  InOut io = inout_begin(A);
-  HIPDIE(m4ri_amd_apply_p_right_trans_tri_dev(io.d.p, io.d.stride, A->nrows, A->ncols, Q->values, nullptr));
-  inout_end(io, A);
-  HIPDIE(hipDeviceSynchronize());
-  { std::lock_guard<std::mutex> sl(g_stats_mu); g_api_stats.calls += 1; }
+  HostCall call;
+  Operand &a = call.inout(A);
+  call.stage();
+  HIPDIE(m4ri_amd_apply_p_right_trans_tri_dev(a.d.p, a.d.stride, A->nrows, A->ncols, Q->values, nullptr));
+  call.finish();
 }
 
 // ---- echelon forms and the column permutations (echelon.hip) -----------------------------------------------------
 static rci_t run_echelonize(mzd_t *A, int full) {
   if (A->nrows == 0 || A->ncols == 0) return 0;
-  ApiLock lk;
-  int dev = 0;
-  HIPDIE(hipGetDevice(&dev));
-  HIPDIE(m4ri_amd_init(dev));
-  arena_reserve(inout_words(A));
-  InOut io = inout_begin(A);
+  HostCall call;
+  Operand &a = call.inout(A);
+  call.stage();
   int32_t rank = 0;
-  HIPDIE(m4ri_amd_echelonize_dev(io.d.p, io.d.stride, A->nrows, A->ncols, full, &rank, nullptr));
-  inout_end(io, A);
-  HIPDIE(hipDeviceSynchronize());
-  { std::lock_guard<std::mutex> sl(g_stats_mu); g_api_stats.calls += 1; }
+  HIPDIE(m4ri_amd_echelonize_dev(a.d.p, a.d.stride, A->nrows, A->ncols, full, &rank, nullptr));
+  call.finish();
   return rank;
 }
 rci_t mzd_echelonize(mzd_t *A, int full) { return run_echelonize(A, full); }                  // echelonform.c:29-31
@@ -1205,16 +1237,11 @@ rci_t _mzd_echelonize_m4ri(mzd_t *A, const int full, int k, int heuristic, const
 
 static void run_apply_p_right(mzd_t *A, mzp_t const *P, int trans) {  // mzp.c:193-260
   if (A->nrows == 0 || A->ncols == 0) return;
-  ApiLock lk;
-  int dev = 0;
-  HIPDIE(hipGetDevice(&dev));
-  HIPDIE(m4ri_amd_init(dev));
-  arena_reserve(inout_words(A));
-  InOut io = inout_begin(A);
-  HIPDIE(m4ri_amd_apply_p_right_dev(io.d.p, io.d.stride, A->nrows, A->ncols, P->values, P->length, trans, nullptr));
-  inout_end(io, A);
-  HIPDIE(hipDeviceSynchronize());
-  { std::lock_guard<std::mutex> sl(g_stats_mu); g_api_stats.calls += 1; }
+  HostCall call;
+  Operand &a = call.inout(A);
+  call.stage();
+  HIPDIE(m4ri_amd_apply_p_right_dev(a.d.p, a.d.stride, A->nrows, A->ncols, P->values, P->length, trans, nullptr));
+  call.finish();
 }
 void mzd_apply_p_right(mzd_t *A, mzp_t const *P) { run_apply_p_right(A, P, 0); }
 void mzd_apply_p_right_trans(mzd_t *A, mzp_t const *P) { run_apply_p_right(A, P, 1); }
@@ -1222,44 +1249,28 @@ void mzd_apply_p_right_trans(mzd_t *A, mzp_t const *P) { run_apply_p_right(A, P,
 // ---- the drivers over PLUQ: systems, kernels, inverses, row permutations (solve.hip) ---------------------------------
 static void run_apply_p_left(mzd_t *A, mzp_t const *P, int trans) {  // mzp.c:65-81
   if (A->nrows == 0 || A->ncols == 0) return;
-  ApiLock lk;
-  int dev = 0;
-  HIPDIE(hipGetDevice(&dev));
-  HIPDIE(m4ri_amd_init(dev));
-  arena_reserve(inout_words(A));
-  InOut io = inout_begin(A);
-  HIPDIE(m4ri_amd_apply_p_left_dev(io.d.p, io.d.stride, A->nrows, A->ncols, P->values, P->length, trans, nullptr));
-  inout_end(io, A);
-  HIPDIE(hipDeviceSynchronize());
-  { std::lock_guard<std::mutex> sl(g_stats_mu); g_api_stats.calls += 1; }
+  HostCall call;
+  Operand &a = call.inout(A);
+  call.stage();
+  HIPDIE(m4ri_amd_apply_p_left_dev(a.d.p, a.d.stride, A->nrows, A->ncols, P->values, P->length, trans, nullptr));
+  call.finish();
 }
 void mzd_apply_p_left(mzd_t *A, mzp_t const *P) { run_apply_p_left(A, P, 0); }
 void mzd_apply_p_left_trans(mzd_t *A, mzp_t const *P) { run_apply_p_left(A, P, 1); }
 
 // A == nullptr-decomposition variant: rank/P/Q given (mzd_pluq_solve_left); otherwise A is decomposed in place
 static int run_solve_left(mzd_t *A, mzd_t const *Adec, rci_t rank, mzp_t const *P, mzp_t const *Q, mzd_t *B, int cutoff, int check) {
-  ApiLock lk;
-  int dev = 0;
-  HIPDIE(hipGetDevice(&dev));
-  HIPDIE(m4ri_amd_init(dev));
+  HostCall call;
   int retval = 0;
   if (cutoff < 0) cutoff = 0;
-  if (A) {
-    arena_reserve(inout_words(A) + inout_words(B));
-    InOut ia = inout_begin(A), ib = inout_begin(B);
-    HIPDIE(m4ri_amd_solve_left_dev(ia.d.p, ia.d.stride, A->nrows, A->ncols, ib.d.p, ib.d.stride, B->nrows, B->ncols, cutoff, check, &retval, nullptr));
-    inout_end(ia, A);
-    inout_end(ib, B);
-  } else {
-    arena_reserve((find_pin(Adec) ? 0 : dev_words(Adec->nrows, Adec->ncols)) + inout_words(B));
-    const DevMat dA = operand(Adec, true);
-    InOut ib        = inout_begin(B);
-    HIPDIE(m4ri_amd_pluq_solve_left_dev(dA.p, dA.stride, Adec->nrows, Adec->ncols, rank, P->values, Q->values, ib.d.p, ib.d.stride, B->nrows, B->ncols,
+  Operand &a = A ? call.inout(A) : call.in(Adec), &b = call.inout(B);
+  call.stage();
+  if (A)
+    HIPDIE(m4ri_amd_solve_left_dev(a.d.p, a.d.stride, A->nrows, A->ncols, b.d.p, b.d.stride, B->nrows, B->ncols, cutoff, check, &retval, nullptr));
+  else
+    HIPDIE(m4ri_amd_pluq_solve_left_dev(a.d.p, a.d.stride, Adec->nrows, Adec->ncols, rank, P->values, Q->values, b.d.p, b.d.stride, B->nrows, B->ncols,
                                         cutoff, check, &retval, nullptr));
-    inout_end(ib, B);
-  }
-  HIPDIE(hipDeviceSynchronize());
-  { std::lock_guard<std::mutex> sl(g_stats_mu); g_api_stats.calls += 1; }
+  call.finish();
   return retval;
 }
 
@@ -1283,31 +1294,22 @@ int _mzd_pluq_solve_left(mzd_t const *A, rci_t rank, mzp_t const *P, mzp_t const
 }
 
 mzd_t *mzd_kernel_left_pluq(mzd_t *A, int const cutoff) {  // solve.c:154-191
-  ApiLock lk;
-  int dev = 0;
-  HIPDIE(hipGetDevice(&dev));
-  HIPDIE(m4ri_amd_init(dev));
+  HostCall call;
   if (A->ncols == 0) return nullptr;  // rank 0 == ncols
   if (A->nrows == 0) {                // rank 0: every vector is in the kernel (solve.c:168-180 leaves the identity)
     mzd_t *I = result_init(A->ncols, A->ncols);
     for (rci_t i = 0; i < A->ncols; ++i) I->data[(int64_t)i * I->rowstride + i / 64] |= (word)1 << (i % 64);
     return I;
   }
-  arena_reserve(inout_words(A) + dev_words(A->ncols, A->ncols));
-  InOut ia = inout_begin(A);
-  DevMat dR;
-  dev_alloc(dR, A->ncols, A->ncols);  // the kernel has at most ncols columns; its real width is known after the PLUQ
+  Operand &a = call.inout(A), &r = call.space(A->ncols, A->ncols);  // the kernel has at most ncols columns; its real width is known after the PLUQ
+  call.stage();
+  const DevMat dR = r.d;
   HIPDIE(hipMemsetAsync(dR.p, 0, (size_t)A->ncols * dR.stride * 8, nullptr));
   int32_t rank = 0;
-  HIPDIE(m4ri_amd_kernel_left_pluq_dev(ia.d.p, ia.d.stride, A->nrows, A->ncols, dR.p, dR.stride, cutoff < 0 ? 0 : cutoff, &rank, nullptr));
-  inout_end(ia, A);
+  HIPDIE(m4ri_amd_kernel_left_pluq_dev(a.d.p, a.d.stride, A->nrows, A->ncols, dR.p, dR.stride, cutoff < 0 ? 0 : cutoff, &rank, nullptr));
   mzd_t *R = nullptr;
-  if (rank < A->ncols) {
-    R = result_init(A->ncols, A->ncols - rank);
-    download(dR, R);
-  }
-  HIPDIE(hipDeviceSynchronize());
-  { std::lock_guard<std::mutex> sl(g_stats_mu); g_api_stats.calls += 1; }
+  if (rank < A->ncols) HostCall::download_to(r, R = result_init(A->ncols, A->ncols - rank));
+  call.finish();
   return R;
 }
 
@@ -1317,17 +1319,13 @@ mzd_t *mzd_inv_m4ri(mzd_t *B, mzd_t const *A, int k) {  // brilliantrussian.c:97
   if (B == nullptr) B = result_init(A->nrows, A->ncols);
   else if (B->nrows != A->nrows || B->ncols != A->ncols) die("mzd_inv_m4ri: B (%d x %d) has wrong dimensions.\n", B->nrows, B->ncols);
   if (A->nrows == 0) return B;
-  ApiLock lk;
-  int dev = 0;
-  HIPDIE(hipGetDevice(&dev));
-  HIPDIE(m4ri_amd_init(dev));
-  arena_reserve((find_pin(A) ? 0 : dev_words(A->nrows, A->ncols)) + inout_words(B));
-  const DevMat dA = operand(A, true);
-  InOut ib        = inout_begin(B);
-  HIPDIE(m4ri_amd_inv_dev(ib.d.p, ib.d.stride, dA.p, dA.stride, A->nrows, nullptr));
-  inout_end(ib, B);
-  HIPDIE(hipDeviceSynchronize());
-  { std::lock_guard<std::mutex> sl(g_stats_mu); g_api_stats.calls += 1; }
+  HostCall call;
+  // m4ri_amd_inv_dev wants the bits beyond A's last column zero (its elimination of [A | I] reads whole words of A): a ragged
+  // window of a pinned parent is inverted from a masked copy, like the T of a triangular solve
+  Operand &a = call.in(A, /*clean_tail=*/true), &b = call.inout(B);
+  call.stage();
+  HIPDIE(m4ri_amd_inv_dev(b.d.p, b.d.stride, a.d.p, a.d.stride, A->nrows, nullptr));
+  call.finish();
   return B;
 }
 
@@ -1336,54 +1334,29 @@ mzd_t *mzd_transpose(mzd_t *DST, mzd_t const *A) {  // mzd.c:1118-1139
   if (DST == nullptr) DST = result_init(A->ncols, A->nrows);
   else if (DST->nrows != A->ncols || DST->ncols != A->nrows) die("mzd_transpose: Wrong size for return matrix.\n");
   if (A->nrows == 0 || A->ncols == 0) return DST;
-  ApiLock lk;
-  int dev = 0;
-  HIPDIE(hipGetDevice(&dev));
-  HIPDIE(m4ri_amd_init(dev));
+  HostCall call;
   // the result is always built in staging: DST may be A itself, a window with neighbours in its last word, or pinned
-  arena_reserve((find_pin(A) ? 0 : dev_words(A->nrows, A->ncols)) + dev_words(DST->nrows, DST->ncols));
-  const DevMat dA = operand(A, true);
-  DevMat dD;
-  dev_alloc(dD, DST->nrows, DST->ncols);
-  HIPDIE(m4ri_amd_transpose_dev(dD.p, dD.stride, dA.p, dA.stride, A->nrows, A->ncols, nullptr));
-  if (Pin *pd = find_pin(DST)) {
-    const DevMat dst = operand(DST, false);
-    HIPDIE(gf2_launch_copy_masked(nullptr, dst.p, dst.stride, dD.p, dD.stride, DST->nrows, DST->ncols));
-    set_newer(*pd, true);
-  } else {
-    download(dD, DST);
-  }
-  HIPDIE(hipDeviceSynchronize());
-  { std::lock_guard<std::mutex> sl(g_stats_mu); g_api_stats.calls += 1; }
+  Operand &a = call.in(A), &d = call.out(DST, /*always_staged=*/true);
+  call.stage();
+  HIPDIE(m4ri_amd_transpose_dev(d.d.p, d.d.stride, a.d.p, a.d.stride, A->nrows, A->ncols, nullptr));
+  call.finish();
   return DST;
 }
 
 static mzd_t *run_trtri_upper(mzd_t *A, const char *who) {  // triangular.c:518-547, triangular_russian.c:384-470
   if (A->nrows != A->ncols) die("%s: matrix must be square and is found to be (%d) x (%d).\n", who, A->nrows, A->ncols);
   if (A->nrows <= 1) return A;
-  ApiLock lk;
-  int dev = 0;
-  HIPDIE(hipGetDevice(&dev));
-  HIPDIE(m4ri_amd_init(dev));
-  arena_reserve(inout_words(A));
-  InOut io = inout_begin(A);
-  HIPDIE(m4ri_amd_trtri_upper_dev(io.d.p, io.d.stride, A->nrows, nullptr));
-  inout_end(io, A);
-  HIPDIE(hipDeviceSynchronize());
-  { std::lock_guard<std::mutex> sl(g_stats_mu); g_api_stats.calls += 1; }
+  HostCall call;
+  Operand &a = call.inout(A);
+  call.stage();
+  HIPDIE(m4ri_amd_trtri_upper_dev(a.d.p, a.d.stride, A->nrows, nullptr));
+  call.finish();
   return A;
 }
 mzd_t *mzd_trtri_upper(mzd_t *A) { return run_trtri_upper(A, "mzd_trtri_upper"); }
 mzd_t *mzd_trtri_upper_russian(mzd_t *A, int k) { (void)k; return run_trtri_upper(A, "mzd_trtri_upper_russian"); }
 
 // ---- the table primitives of the elimination routines (elim.hip) -------------------------
-static word *arena_raw(size_t words) {  // plain words from the staging arena (256-byte granules)
-  word *p = g_arena.base + g_arena.used;
-  g_arena.used += (words + 31) & ~(size_t)31;
-  if (g_arena.used > g_arena.cap) die("m4ri_amd: staging arena overrun (internal error)\n");
-  return p;
-}
-
 // how mzd_process_rowsN cuts the k-bit strip into N groups, lowest bits first (brilliantrussian.c:357-361,
 // :394-398, :440-445, :490-494, :546-552)
 static void split_k(int k, int n, int32_t *kb) {
@@ -1396,36 +1369,31 @@ static void split_k(int k, int n, int32_t *kb) {
 static void run_process_rows(mzd_t *M, rci_t startrow, rci_t stoprow, rci_t startcol, int k, int nt, mzd_t const *const *T,
                              rci_t const *const *L) {
   if (stoprow <= startrow || M->ncols == 0) return;
-  ApiLock lk;
-  int dev = 0;
-  HIPDIE(hipGetDevice(&dev));
-  HIPDIE(m4ri_amd_init(dev));
+  HostCall call;
   int32_t kb[6] = {0, 0, 0, 0, 0, 0};
   split_k(k, nt, kb);
   mzd_t W = *M;  // the rows that are touched, as a window of M
   W.data  = M->data + (int64_t)startrow * M->rowstride;
   W.nrows = stoprow - startrow;
   W.flags |= FLAG_WINDOW;
-  size_t need = inout_words(&W) + 64 + (((size_t)3 * (size_t)W.nrows + 31) & ~(size_t)31);
-  for (int t = 0; t < nt; ++t) need += (find_pin(T[t]) ? 0 : dev_words(T[t]->nrows, T[t]->ncols)) + ((((size_t)1 << kb[t]) / 2 + 1 + 31) & ~(size_t)31);
-  arena_reserve(need);
-  InOut io = inout_begin(&W);
+  Operand &w = call.inout(&W);
+  Operand *tab[6], *lst[6];
+  for (int t = 0; t < nt; ++t) {  // each table, then its list of 2^kb int32 indices
+    const size_t n = (size_t)1 << kb[t];
+    tab[t] = &call.in(T[t]);
+    lst[t] = &call.words(n / 2 + 1, L[t], n * 4);
+  }
+  Operand &idx = call.words((size_t)3 * (size_t)W.nrows);  // the kernels' own: three words per row
+  call.stage();
   const word *dT[6];
   int64_t ts[6];
   const int32_t *dL[6];
   for (int t = 0; t < nt; ++t) {
-    const DevMat d = operand(T[t], true);
-    dT[t] = d.p; ts[t] = d.stride;
-    const size_t n = (size_t)1 << kb[t];
-    int32_t *l = reinterpret_cast<int32_t *>(arena_raw(n / 2 + 1));
-    HIPDIE(hipMemcpyAsync(l, L[t], n * 4, hipMemcpyHostToDevice, nullptr));
-    dL[t] = l;
+    dT[t] = tab[t]->d.p; ts[t] = tab[t]->d.stride;
+    dL[t] = reinterpret_cast<const int32_t *>(lst[t]->d.p);
   }
-  int32_t *idx = reinterpret_cast<int32_t *>(arena_raw((size_t)3 * (size_t)W.nrows));
-  HIPDIE(m4ri_amd_process_rows_dev(io.d.p, io.d.stride, M->width, 0, W.nrows, startcol, nt, kb, dT, ts, dL, idx, nullptr));
-  inout_end(io, &W);
-  HIPDIE(hipDeviceSynchronize());
-  { std::lock_guard<std::mutex> sl(g_stats_mu); g_api_stats.calls += 1; }
+  HIPDIE(m4ri_amd_process_rows_dev(w.d.p, w.d.stride, M->width, 0, W.nrows, startcol, nt, kb, dT, ts, dL, reinterpret_cast<int32_t *>(idx.d.p), nullptr));
+  call.finish();
 }
 
 void mzd_process_rows(mzd_t *M, rci_t startrow, rci_t endrow, rci_t startcol, int k, mzd_t const *T, rci_t const *L) {  // brilliantrussian.c:213
@@ -1470,40 +1438,34 @@ void mzd_make_table(mzd_t const *M, rci_t r, rci_t c, int k, mzd_t *T, rci_t *L)
     jstar[(size_t)i] = js;
   }
   if (M->ncols == 0 || c / 64 >= M->width) return;
-  ApiLock lk;
-  int dev = 0;
-  HIPDIE(hipGetDevice(&dev));
-  HIPDIE(m4ri_amd_init(dev));
+  HostCall call(HostCall::UNCOUNTED);  // the statistics have never counted the tables, only the calls that use them
   mzd_t W = *M;  // the k source rows
   W.data  = M->data + (int64_t)r * M->rowstride;
   W.nrows = (r + k <= M->nrows) ? k : (M->nrows > r ? M->nrows - r : 0);
   W.flags |= FLAG_WINDOW;
-  Pin *pinT = find_pin(T);  // a pinned T IS its device copy: build the table there (the host copy goes stale like any pinned result)
-  arena_reserve((find_pin(&W) ? 0 : dev_words(W.nrows, W.ncols)) + (pinT ? 0 : dev_words(T->nrows, T->ncols)) + (((size_t)twokay / 2 + 1 + 31) & ~(size_t)31) + 64);
-  DevMat dM{};
-  if (W.nrows > 0) dM = operand(&W, true);
-  DevMat dT;
+  // T is outside the placement rule: a pinned T IS its device copy, whatever its shape, and the table is built there (the host copy
+  // goes stale like any pinned result); any other T gets room in staging and partial, unmasked copies of its own, below
+  Pin *pinT      = find_pin(T);
+  Operand *rows  = W.nrows > 0 ? &call.in(&W) : nullptr;
+  Operand *room  = pinT ? nullptr : &call.space(T->nrows, T->ncols);
+  Operand &dj    = call.words((size_t)twokay / 2 + 1);
+  call.stage();
+  const DevMat dM = rows ? rows->d : DevMat{}, dT = pinT ? call.view(*pinT, T) : room->d;
   const int64_t home = c / 64, wide = M->width - home;
-  if (pinT) {
-    dT = operand(T, false);
-  } else {
-    dev_alloc(dT, T->nrows, T->ncols);
-    // the table's present content, unmasked (rows whose source row is missing keep it, and T[0] seeds the chain)
+  if (!pinT)  // the table's present content, unmasked (rows whose source row is missing keep it, and T[0] seeds the chain)
     HIPDIE(hipMemcpy2D(dT.p + home, (size_t)dT.stride * 8, T->data + home, (size_t)T->rowstride * 8, (size_t)wide * 8, (size_t)twokay, hipMemcpyHostToDevice));
-  }
-  int32_t *dj = reinterpret_cast<int32_t *>(arena_raw((size_t)twokay / 2 + 1));
-  HIPDIE(hipMemcpyAsync(dj, jstar.data(), (size_t)twokay * 4, hipMemcpyHostToDevice, nullptr));
-  HIPDIE(m4ri_amd_make_table_dev(dM.p, dM.stride, W.nrows, M->ncols, 0, c, k, dT.p, dT.p, dT.stride, dj, nullptr));
+  HIPDIE(hipMemcpyAsync(dj.d.p, jstar.data(), (size_t)twokay * 4, hipMemcpyHostToDevice, nullptr));
+  HIPDIE(m4ri_amd_make_table_dev(dM.p, dM.stride, W.nrows, M->ncols, 0, c, k, dT.p, dT.p, dT.stride, reinterpret_cast<int32_t *>(dj.d.p), nullptr));
   if (pinT) set_newer(*pinT, true);
   else
     HIPDIE(hipMemcpy2D(T->data + (int64_t)T->rowstride + home, (size_t)T->rowstride * 8, dT.p + dT.stride + home, (size_t)dT.stride * 8, (size_t)wide * 8,
                        (size_t)(twokay - 1), hipMemcpyDeviceToHost));
-  HIPDIE(hipDeviceSynchronize());
+  call.finish();
 }
 
 void gf2_release_staging(void) {  // called by m4ri_amd_release_workspace: the current device's arena, the parked result blocks
   g_big_cache.drop();
-  ApiLock lk;
+  const std::unique_lock<std::mutex> lk = lock_current_device();
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= ARENA_DEVICES) return;
   if (g_host_stage[dev].p) {
@@ -1538,12 +1500,10 @@ int m4ri_amd_pin(mzd_t *M) {
       // a matrix freed without unpin left this entry behind and the allocator reused its address: the
       // device copy belongs to a dead matrix -- drop it (without a download) and pin M afresh
       (void)hipFree(old.p->dbase);
-      std::lock_guard<std::mutex> pl(g_pin_mu);
-      for (auto it = g_pins.begin(); it != g_pins.end(); ++it)
-        if (&*it == old.p) { g_pins.erase(it); break; }
+      erase_pin(old.p);
     }
   }
-  ApiLock lk;
+  const std::unique_lock<std::mutex> lk = lock_current_device();
   if (M->nrows == 0 || M->ncols == 0 || !M->data) return -1;
   int dev = 0;
   HIPDIE(hipGetDevice(&dev));
@@ -1556,8 +1516,7 @@ int m4ri_amd_pin(mzd_t *M) {
   pin_upload(p);
   {
     std::lock_guard<std::mutex> pl(g_pin_mu);
-    for (Pin &q : g_pins)  // another thread pinned the same block in the meantime: keep theirs
-      if (M->data >= q.hbase && M->data < q.hbase + q.words && M->rowstride == q.rowstride) { (void)hipFree(p.dbase); return 0; }
+    if (pin_of(M)) { (void)hipFree(p.dbase); return 0; }  // another thread pinned the same block in the meantime: keep theirs
     g_pins.push_back(p);
   }
   return 0;
@@ -1582,22 +1541,16 @@ int m4ri_amd_unpin(mzd_t *M) {
   if (!pl.p) return -1;
   pin_download(*pl.p);
   HIPDIE(hipFree(pl.p->dbase));
-  {
-    std::lock_guard<std::mutex> gl(g_pin_mu);
-    for (auto it = g_pins.begin(); it != g_pins.end(); ++it)
-      if (&*it == pl.p) { g_pins.erase(it); break; }
-  }
+  erase_pin(pl.p);
   return 0;
 }
 
 // A status query: the list's short lock only, never the device lock -- it does not wait for a product running on the pin's device
 // (the flag it reads is the one the LAST completed call left; a product in flight sets it before it returns)
 int m4ri_amd_is_pinned(const mzd_t *M) {
-  if (!M || !M->data) return 0;
   std::lock_guard<std::mutex> pl(g_pin_mu);
-  for (const Pin &p : g_pins)
-    if (M->data >= p.hbase && M->data < p.hbase + p.words && M->rowstride == p.rowstride) return is_newer(p) ? 2 : 1;
-  return 0;
+  const Pin *p = pin_of(M);
+  return !p ? 0 : is_newer(*p) ? 2 : 1;
 }
 
 // mp.c:277-297 / :299-324.  Several devices + a product large enough: the top Strassen-Winograd
