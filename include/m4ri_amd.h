@@ -229,7 +229,14 @@ int m4ri_amd_device_count(void);
  * reference's meaning (recurse until 3*dim < 4*cutoff for some dim, strassen.c:39,51).
  * Asynchronous on `stream`.  The engine has ONE workspace per device, so a product issued on another
  * stream than the previous one first waits (on the device) for that one to finish; several host
- * threads may call concurrently (the host side is serialised). */
+ * threads may call concurrently (the host side is serialised).
+ * Limits of the four product calls (m4ri_amd_mul_dev, m4ri_amd_m4rm_dev and their batch forms), each hipErrorInvalidValue
+ * before any HIP call and whatever the depth (`cutoff`, the engine's own choice of levels), so C is never partly written: the
+ * leaf kernels address one chunk of B with 32-bit byte offsets, and the smallest chunk is 64 rows, so for l > 64, 64 rows of B
+ * may span at most 2^32 - 2^20 bytes (b_stride at most 8 386 560 words); for l <= 64 the l rows of B must span less than 2^32
+ * bytes.  One row of A (a_stride words) may span at most 2^32 - 2^20 bytes, rows of A and C being cut one by one (m = 1: less
+ * than 2^32 bytes).  n is at most INT32_MAX.  Within these limits any stride is legal: operands of 4 GiB and more -- windows of
+ * a very wide parent included, in a batch as in a single call -- are cut into chunks, same bits. */
 int m4ri_amd_mul_dev(word *C, int64_t c_stride, const word *A, int64_t a_stride, const word *B,
                      int64_t b_stride, int64_t m, int64_t l, int64_t n, int add, int cutoff,
                      void *stream);

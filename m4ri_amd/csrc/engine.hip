@@ -371,6 +371,14 @@ int launch_leaf(Engine *e, hipStream_t st, word *C, int64_t cs, int64_t cbs, con
                 const word *B, int64_t bs, int64_t bbs, int64_t m, int64_t l, int64_t n, int64_t batch,
                 bool add, int ksplit_req, bool a_prepacked = false) {
   constexpr uint64_t LIMIT = (1ull << 32) - (1ull << 20);
+  if (batch > 1 && !a_prepacked && m > 0 && n > 0 &&
+      ((uint64_t)m * (uint64_t)as * 8 >= LIMIT || (uint64_t)l * (uint64_t)bs * 8 >= LIMIT)) {
+    // members too large for one descriptor each (windows of a very wide parent): one member at a time through the cuts below --
+    // the same bits as the batched launch, and as `batch` single calls
+    for (int64_t b = 0; b < batch; ++b)
+      if (int rc = launch_leaf(e, st, C + b * cbs, cs, 0, A + b * abs_, as, 0, B + b * bbs, bs, 0, m, l, n, 1, add, ksplit_req)) return rc;
+    return 0;
+  }
   if (batch == 1 && !a_prepacked) {
     if ((uint64_t)m * (uint64_t)as * 8 >= LIMIT && m > 1) {  // rows of A and C: whole tiles when the stride allows
       int64_t m1 = (int64_t)(LIMIT / ((uint64_t)as * 8));     // (a window of a very wide parent may allow fewer)
@@ -394,6 +402,20 @@ int launch_leaf(Engine *e, hipStream_t st, word *C, int64_t cs, int64_t cbs, con
     }
   }
   return launch_leaf_one(e, st, C, cs, cbs, A, as, abs_, B, bs, bbs, m, l, n, batch, add, ksplit_req, a_prepacked);
+}
+
+// What launch_leaf refuses, decided from the strides alone: one row of A it cannot address, or a B whose smallest chunk (64 rows, or
+// all l of them up to 64) it cannot.  Every entry of the engine asks this FIRST, whatever depth the product then runs at: a
+// product with levels would otherwise read such operands through the passes, write the even block of C and meet the refusal only
+// in a remainder strip -- or, on a shape without strips, not at all.  One rule for every depth, and nothing written when it says no.
+bool leaf_operands_refused(int64_t m, int64_t l, int64_t n, int64_t as, int64_t bs) {
+  constexpr uint64_t LIMIT = (1ull << 32) - (1ull << 20);  // launch_leaf's
+  if (m == 0 || n == 0) return false;
+  if (n > INT32_MAX) return true;
+  const uint64_t arow = (uint64_t)as * 8, brow = (uint64_t)bs * 8;
+  if (m > 1 ? arow > LIMIT : arow >= (1ull << 32)) return true;
+  if (l > 64 ? 64 * brow > LIMIT : (uint64_t)l * brow >= (1ull << 32)) return true;
+  return false;
 }
 
 int reserve_apk(Engine *e, size_t words) {
@@ -793,6 +815,7 @@ size_t df_words(const Engine *e, int64_t m, int64_t l, int64_t n, int L, double 
 int engine_mul(Engine *e, hipStream_t st, DMat C, DMat A, DMat B, bool add, int cutoff) {
   const int64_t m = A.nrows, l = A.ncols, n = B.ncols;
   if (m == 0 || n == 0) return 0;
+  if (leaf_operands_refused(m, l, n, A.stride, B.stride)) return (int)hipErrorInvalidValue;
   // the engine's own plan may cut the rows into blocks, each at its depth (plan_row_blocks); a caller's cutoff or the developer's
   // M4RI_AMD_LEVELS mean one product at that depth
   std::vector<RowBlock> blocks;
@@ -829,6 +852,7 @@ int engine_mul(Engine *e, hipStream_t st, DMat C, DMat A, DMat B, bool add, int 
 int engine_mul_batch(Engine *e, hipStream_t st, DMat C, int64_t c_bs, DMat A, int64_t a_bs, DMat B, int64_t b_bs, int64_t batch, bool add, int cutoff) {
   const int64_t m = A.nrows, l = A.ncols, n = B.ncols;
   if (m == 0 || n == 0 || batch <= 0) return 0;
+  if (leaf_operands_refused(m, l, n, A.stride, B.stride)) return (int)hipErrorInvalidValue;
   auto one_by_one = [&]() {
     for (int64_t b = 0; b < batch; ++b) {
       DMat c = C, a = A, bb = B;
@@ -909,6 +933,7 @@ int m4ri_amd_mul_dev(word *C, int64_t c_stride, const word *A, int64_t a_stride,
   EngineLock el;
   Engine *e = el.e;
   if (!e || cutoff < 0 || m < 0 || l < 0 || n < 0) return (int)hipErrorInvalidValue;
+  if (leaf_operands_refused(m, l, n, a_stride, b_stride)) return (int)hipErrorInvalidValue;  // before any HIP call
   reset_stats(e);
   if (cutoff > 0) { cutoff = cutoff / 64 * 64; if (cutoff < 64) cutoff = 64; }  // strassen.c:351-354
   DMat dC{C, m, n, c_stride}, dA{const_cast<word *>(A), m, l, a_stride}, dB{const_cast<word *>(B), l, n, b_stride};
@@ -926,6 +951,7 @@ int m4ri_amd_mul_batch_dev(word *C, int64_t c_stride, int64_t c_bs, const word *
   Engine *e = el.e;
   if (!e || cutoff < 0 || m < 0 || l < 0 || n < 0 || batch < 0) return (int)hipErrorInvalidValue;
   if (batch == 0) return 0;
+  if (leaf_operands_refused(m, l, n, a_stride, b_stride)) return (int)hipErrorInvalidValue;  // before any HIP call
   reset_stats(e);
   if (cutoff > 0) { cutoff = cutoff / 64 * 64; if (cutoff < 64) cutoff = 64; }  // strassen.c:351-354
   DMat dC{C, m, n, c_stride}, dA{const_cast<word *>(A), m, l, a_stride}, dB{const_cast<word *>(B), l, n, b_stride};
@@ -939,6 +965,7 @@ int m4ri_amd_m4rm_dev(word *C, int64_t c_stride, const word *A, int64_t a_stride
   EngineLock el;
   Engine *e = el.e;
   if (!e || m < 0 || l < 0 || n < 0) return (int)hipErrorInvalidValue;
+  if (leaf_operands_refused(m, l, n, a_stride, b_stride)) return (int)hipErrorInvalidValue;  // before any HIP call
   reset_stats(e);
   if (int rc = order_after_previous(e, (hipStream_t)stream)) return rc;
   if (int rc = reserve_apk(e, packed_a_words(m, l, 1))) return rc;
@@ -955,6 +982,7 @@ int m4ri_amd_m4rm_batch_dev(word *C, int64_t c_stride, int64_t c_bs, const word 
   Engine *e = el.e;
   if (!e || m < 0 || l < 0 || n < 0 || batch < 0) return (int)hipErrorInvalidValue;
   if (batch == 0 || m == 0 || n == 0) return 0;
+  if (leaf_operands_refused(m, l, n, a_stride, b_stride)) return (int)hipErrorInvalidValue;
   reset_stats(e);
   if (int rc = order_after_previous(e, (hipStream_t)stream)) return rc;
   if (int rc = launch_leaf(e, (hipStream_t)stream, C, c_stride, c_bs, A, a_stride, a_bs, B, b_stride, b_bs, m, l, n, batch, add != 0, 0)) return rc;

@@ -57,3 +57,22 @@ def tables_for(make, M, r, c, k, nt):
         Ls.append(L)
         off += kb[t]
     return Ts, Ls
+
+
+def make(kind, m, n, seed):
+    """The matrix kinds of the elimination tests: random, lowrank, sparse, zerocols."""
+    A = Mzd.random(m, n, seed)
+    if kind == "lowrank" and m > 2 and n > 2:         # rank <= min(m, n) / 3: many columns without a pivot
+        r = max(1, min(m, n) // 3)
+        X, Y = Mzd.random(m, r, seed + 1).to_bits().astype(np.int64), Mzd.random(r, n, seed + 2).to_bits().astype(np.int64)
+        A = Mzd.from_bits(((X @ Y) & 1).astype(np.uint8))
+    elif kind == "sparse":                            # ~3 % density: pivots far down, empty column blocks
+        b = A.to_bits() & Mzd.random(m, n, seed + 3).to_bits() & Mzd.random(m, n, seed + 4).to_bits()
+        b &= Mzd.random(m, n, seed + 5).to_bits() & Mzd.random(m, n, seed + 6).to_bits()
+        A = Mzd.from_bits(b)
+    elif kind == "zerocols" and n > 70:               # whole 64-column blocks of zeros, then data
+        b = A.to_bits()
+        b[:, : 64 + 7] = 0
+        b[:, n // 2: n // 2 + 3] = 0
+        A = Mzd.from_bits(b)
+    return A
