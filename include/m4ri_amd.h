@@ -513,9 +513,9 @@ int m4ri_amd_plan_perm_batch(int64_t nrows, int64_t ncols, int right);
 /* Device twin of mzd_trtri_upper: U (n x n) <- U^-1.  Only the bits strictly above the diagonal (and below column n) are read
  * and written: the diagonal, the lower triangle, the bits beyond column n of a row's last word (whatever they are), the words
  * from words(n) to `stride` and the rows around U come back untouched.  Any word alignment, any stride >= words(n).
- * Asynchronous on `stream`; scratch grow-only per device (growing it synchronises the device), one call at a time per device:
- * two calls in flight on different streams are NOT ordered against each other.  hipErrorInvalidValue, before any HIP call, for
- * n < 0. */
+ * Asynchronous on `stream`; the calls share grow-only scratch per device (growing it synchronises the device), and a call on
+ * another stream than the previous one first waits, on the device, for that one.  hipErrorInvalidValue, before any HIP call,
+ * for n < 0. */
 int m4ri_amd_trtri_upper_dev(word *U, int64_t stride, int64_t n, void *stream);
 /* Device twin of mzd_echelonize* (echelon.hip): A (nrows x ncols) <- its (reduced, full != 0) row echelon form, *rank_out the
  * rank.  Blocking.  Bits at column >= ncols: zero in, zero out (rows are written in whole words, last word included).  Only rows

@@ -13,6 +13,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <vector>
+#include "dev_scratch.h"  // Scratch: the device temporaries of a one-by-one path
 #include "gf2_internal.h"
 
 namespace {
@@ -194,33 +195,6 @@ inline uintptr_t member_span_bytes(int64_t batch, int64_t bs, int64_t rows, int6
 inline bool spans_meet(const void *p, uintptr_t pn, const void *q, uintptr_t qn) {
   return (uintptr_t)p < (uintptr_t)q + qn && (uintptr_t)q < (uintptr_t)p + pn;
 }
-
-// The device scratch of a one-by-one path.  Work queued on the stream may still use a buffer when the function leaves early, so
-// unless done() was reached the stream is synchronised first; then the buffers are freed, in the order they were allocated.
-class Scratch {
- public:
-  explicit Scratch(hipStream_t st) : st_(st) {}
-  Scratch(const Scratch &)            = delete;
-  Scratch &operator=(const Scratch &) = delete;
-  ~Scratch() {
-    if (!done_) (void)hipStreamSynchronize(st_);
-    for (void *p : bufs_) (void)hipFree(p);
-  }
-  int words(word **p, int64_t n) {
-    HIPTRY(hipMalloc(reinterpret_cast<void **>(p), (size_t)n * 8));
-    bufs_.push_back(*p);
-    return 0;
-  }
-  int done() {  // the function's successful end, after its last synchronisation
-    done_ = true;
-    return 0;
-  }
-
- private:
-  hipStream_t st_;
-  bool done_ = false;
-  std::vector<void *> bufs_;
-};
 
 // a clean copy (tail bits zero) of the rows x ncols matrix at src into scratch
 inline int clean_copy(word *dst, int64_t dst_stride, const word *src, int64_t src_stride, int64_t rows, int64_t ncols, hipStream_t st) {

@@ -18,7 +18,9 @@
 // on the columns of U that share that word it produces U^-1 U = identity, which is what :105 writes anyway.
 #include <hip/hip_runtime.h>
 #include <vector>
+#include "dev_scratch.h"
 #include "gf2_internal.h"
+#include "row_gather.h"
 #include "../../include/m4ri_amd.h"
 
 namespace {
@@ -30,27 +32,8 @@ constexpr int EC_THREADS = 256;
 template <bool LDSROW>
 __global__ __launch_bounds__(EC_THREADS) void colperm_gather_kernel(word *__restrict__ A, int64_t stride, int64_t width, int64_t w0, int64_t w1,
                                                                     int64_t ncols, const uint32_t *__restrict__ map, const word *__restrict__ rowcopy) {
-  extern __shared__ word lrow[];
-  word *row = A + (int64_t)blockIdx.x * stride;
-  const word *src;
-  if (LDSROW) {
-    for (int64_t w = threadIdx.x; w < width; w += EC_THREADS) lrow[w] = row[w];
-    __syncthreads();
-    src = lrow;
-  } else {
-    src = rowcopy + (int64_t)blockIdx.x * width;
-  }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int64_t w = w0 + wave; w < w1; w += EC_THREADS / 64) {
-    const int64_t c = w * 64 + lane;
-    int bit         = 0;
-    if (c < ncols) {
-      const uint32_t sc = map[c];
-      bit               = (int)((src[sc >> 6] >> (sc & 63)) & 1);
-    }
-    const word v = __ballot(bit);
-    if (lane == 0) row[w] = v;
-  }
+  const word *copy = LDSROW ? nullptr : rowcopy + (int64_t)blockIdx.x * width;
+  gather_row<LDSROW, EC_THREADS>(A + (int64_t)blockIdx.x * stride, width, copy, map, w0, w1, ncols);
 }
 
 // full = 0, after the PLE (echelonform.c:116-132): row i < rank loses its bits 0 .. i (the multipliers) and gets its
@@ -114,30 +97,25 @@ int apply_map(word *A, int64_t stride, int64_t rows, int64_t ncols, const std::v
   uint32_t *d_map = nullptr;
   word *d_copy    = nullptr;
   const bool ldsrow = width * 8 <= 64 * 1024;
-  auto run = [&]() -> int {
-    HIPTRY(hipMalloc(reinterpret_cast<void **>(&d_map), (size_t)ncols * 4));
-    HIPTRY(hipMemcpyAsync(d_map, map.data(), (size_t)ncols * 4, hipMemcpyHostToDevice, st));
-    if (ldsrow) {
-      hipLaunchKernelGGL((colperm_gather_kernel<true>), dim3((unsigned)rows), dim3(EC_THREADS), (size_t)width * 8, st, A, stride, width, lo / 64, hi / 64 + 1,
-                         ncols, d_map, nullptr);
-    } else {
-      const int64_t chunk = 4096;  // rows per copy
-      HIPTRY(hipMalloc(reinterpret_cast<void **>(&d_copy), (size_t)(rows < chunk ? rows : chunk) * width * 8));
-      for (int64_t r0 = 0; r0 < rows; r0 += chunk) {
-        const int64_t n = rows - r0 < chunk ? rows - r0 : chunk;
-        HIPTRY(hipMemcpy2DAsync(d_copy, (size_t)width * 8, A + r0 * stride, (size_t)stride * 8, (size_t)width * 8, (size_t)n, hipMemcpyDeviceToDevice, st));
-        hipLaunchKernelGGL((colperm_gather_kernel<false>), dim3((unsigned)n), dim3(EC_THREADS), 0, st, A + r0 * stride, stride, width, lo / 64, hi / 64 + 1,
-                           ncols, d_map, d_copy);
-      }
+  Scratch tmp(st);
+  HIPTRY(tmp.alloc(&d_map, (size_t)ncols));
+  HIPTRY(hipMemcpyAsync(d_map, map.data(), (size_t)ncols * 4, hipMemcpyHostToDevice, st));
+  if (ldsrow) {
+    hipLaunchKernelGGL((colperm_gather_kernel<true>), dim3((unsigned)rows), dim3(EC_THREADS), (size_t)width * 8, st, A, stride, width, lo / 64, hi / 64 + 1,
+                       ncols, d_map, nullptr);
+  } else {
+    const int64_t chunk = 4096;  // rows per copy
+    HIPTRY(tmp.alloc(&d_copy, (size_t)(rows < chunk ? rows : chunk) * width));
+    for (int64_t r0 = 0; r0 < rows; r0 += chunk) {
+      const int64_t n = rows - r0 < chunk ? rows - r0 : chunk;
+      HIPTRY(hipMemcpy2DAsync(d_copy, (size_t)width * 8, A + r0 * stride, (size_t)stride * 8, (size_t)width * 8, (size_t)n, hipMemcpyDeviceToDevice, st));
+      hipLaunchKernelGGL((colperm_gather_kernel<false>), dim3((unsigned)n), dim3(EC_THREADS), 0, st, A + r0 * stride, stride, width, lo / 64, hi / 64 + 1,
+                         ncols, d_map, d_copy);
     }
-    HIPTRY(hipGetLastError());
-    HIPTRY(hipStreamSynchronize(st));
-    return 0;
-  };
-  const int rc = run();
-  if (d_map) (void)hipFree(d_map);
-  if (d_copy) (void)hipFree(d_copy);
-  return rc;
+  }
+  HIPTRY(hipGetLastError());
+  HIPTRY(hipStreamSynchronize(st));
+  return tmp.done();
 }
 
 }  // namespace
@@ -170,32 +148,29 @@ int m4ri_amd_echelonize_dev(word *A, int64_t stride, int64_t nrows, int64_t ncol
   int32_t rank = 0;
   if (!full) {
     if (int rc = m4ri_amd_ple_dev(A, stride, nrows, ncols, P.data(), Q.data(), &rank, 0, st)) return rc;
+    Scratch tmp(st);
     int32_t *d_Q = nullptr;
     if (rank > 0) {
-      HIPTRY(hipMalloc(reinterpret_cast<void **>(&d_Q), (size_t)rank * 4));
-      hipError_t e = hipMemcpyAsync(d_Q, Q.data(), (size_t)rank * 4, hipMemcpyHostToDevice, st);
-      if (e != hipSuccess) { (void)hipFree(d_Q); return (int)e; }
+      HIPTRY(tmp.alloc(&d_Q, (size_t)rank));
+      HIPTRY(hipMemcpyAsync(d_Q, Q.data(), (size_t)rank * 4, hipMemcpyHostToDevice, st));
     }
-    hipLaunchKernelGGL(echelon_from_ple_kernel, dim3((unsigned)nrows), dim3(EC_THREADS), 0, st, A, stride, width, nrows, (int)rank, d_Q);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (d_Q) (void)hipFree(d_Q);
     *rank_out = rank;
-    return (int)e;
+    hipLaunchKernelGGL(echelon_from_ple_kernel, dim3((unsigned)nrows), dim3(EC_THREADS), 0, st, A, stride, width, nrows, (int)rank, d_Q);
+    HIPTRY(hipGetLastError());
+    HIPTRY(hipStreamSynchronize(st));
+    return tmp.done();
   }
   if (int rc = m4ri_amd_pluq_dev(A, stride, nrows, ncols, P.data(), Q.data(), &rank, 0, st)) return rc;
   *rank_out = rank;
   if (rank > 0 && rank != ncols) {  // echelonform.c:66-103
-    const int64_t wr = words_of(rank);
+    Scratch tmp(st);
     word *U = nullptr;
-    HIPTRY(hipMalloc(reinterpret_cast<void **>(&U), (size_t)rank * wr * 8));
-    int rc = (int)hipMemcpy2DAsync(U, (size_t)wr * 8, A, (size_t)stride * 8, (size_t)wr * 8, (size_t)rank, hipMemcpyDeviceToDevice, st);
-    if (!rc) rc = m4ri_amd_mask_tail_dev(U, wr, rank, rank, st);  // the copy's last word also took the first columns of B along
+    HIPTRY(tmp.alloc(&U, (size_t)rank * words_of(rank)));
+    HIPTRY(gf2_square_copy(U, A, stride, rank, st));  // masked: the copy's last word also took the first columns of B along
     const int64_t w0 = rank / 64;
-    if (!rc) rc = m4ri_amd_trsm_upper_left_dev(U, wr, A + w0, stride, rank, ncols - w0 * 64, 0, st);
-    if (!rc) rc = (int)hipStreamSynchronize(st);
-    (void)hipFree(U);
-    if (rc) return rc;
+    HIPTRY(m4ri_amd_trsm_upper_left_dev(U, words_of(rank), A + w0, stride, rank, ncols - w0 * 64, 0, st));
+    HIPTRY(hipStreamSynchronize(st));
+    tmp.done();
   }
   hipLaunchKernelGGL(echelon_identity_kernel, dim3((unsigned)nrows), dim3(EC_THREADS), 0, st, A, stride, width, nrows, (int)rank);
   HIPTRY(hipGetLastError());

@@ -47,7 +47,6 @@ int g_max_fuse = 4;  // deepest levels covered by one fused pass each way (1..4)
 constexpr int DEFAULT_CUTOFF  = 4096;  // engine default: split while l/2 >= this ...
 constexpr int DEFAULT_CUTOFF_M = 4096; // ... and m/2 >= this (one generation-4 tile row)
 constexpr int DEFAULT_CUTOFF_N = 4096; // ... and n/2 >= this (8 column tiles)
-constexpr int NUM_DEVICES_MAX = 16;
 
 struct Engine {
   int device            = -1;
@@ -76,7 +75,7 @@ struct Engine {
 };
 
 std::mutex g_cfg_mu;  // the process-wide knobs (workspace budget, fuse depth)
-Engine g_engines[NUM_DEVICES_MAX];
+Engine g_engines[GF2_MAX_DEVICES];
 
 // the engine of the calling thread's device, locked: host threads issuing on DIFFERENT devices (the ranks of multi.hip) run
 // side by side, threads on one device take turns
@@ -85,7 +84,7 @@ struct EngineLock {
   std::unique_lock<std::mutex> lk;
   EngineLock() {
     int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= NUM_DEVICES_MAX) return;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= GF2_MAX_DEVICES) return;
     e  = &g_engines[dev];
     lk = std::unique_lock<std::mutex>(e->mu);
     e->device = dev;

@@ -21,6 +21,9 @@ struct DMat {
 
 static inline int64_t words_of(int64_t ncols) { return (ncols + 63) >> 6; }
 
+// HIP device ids the per-device tables hold (engines, arenas, solver scratch): 0 .. GF2_MAX_DEVICES - 1
+constexpr int GF2_MAX_DEVICES = 16;
+
 static inline DMat dview(const DMat &M, int64_t r0, int64_t c0_bits, int64_t nr, int64_t nc_bits) {
   DMat V;
   V.p      = M.p + r0 * M.stride + (c0_bits >> 6);

@@ -81,6 +81,12 @@ hipError_t gf2_launch_fill_splitmix_rows(hipStream_t s, word *M, int64_t stride,
 hipError_t gf2_launch_transpose_tiles(hipStream_t st, word *D, int64_t d_stride, int64_t d_bs, const word *A, int64_t a_stride, int64_t a_bs,
                                       int64_t nrows, int64_t ncols, int64_t batch);
 
+// ---- solver glue (solve.hip) ------------------------------------------------------------------------------------------------
+// dst (r rows of words_of(r) words) <- a clean copy of the leading r x r block of A, its last word masked to r columns: the
+// triangular solves split their triangle into blocks that go to the multiply engine as operands, which must not carry bits of
+// the neighbouring columns
+int gf2_square_copy(word *dst, const word *A, int64_t stride, int64_t r, hipStream_t st);
+
 // ---- host side ----------------------------------------------------------------------------------------------------------------
 double gf2_small_host_cost(int64_t m, int64_t l, int64_t n);  // small_host.cpp: word operations of the host product
 int gf2_multi_wanted(int64_t m, int64_t l, int64_t n);         // multi.hip: would mzd_mul_mp spread this product over devices?

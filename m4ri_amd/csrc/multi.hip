@@ -348,9 +348,9 @@ void default_devices() {
     int have = 0;
     if (hipGetDeviceCount(&have) != hipSuccess) have = 0;
     bool ok = g_devices.size() <= (size_t)MAX_RANKS;
-    for (int id : g_devices) ok = ok && id >= 0 && id < have && id < 16;
+    for (int id : g_devices) ok = ok && id >= 0 && id < have && id < GF2_MAX_DEVICES;
     if (!ok) {
-      fprintf(stderr, "m4ri_amd: M4RI_AMD_DEVICES=\"%s\" names a device outside 0..%d: ignored, using every visible device\n", env, (have < 16 ? have : 16) - 1);
+      fprintf(stderr, "m4ri_amd: M4RI_AMD_DEVICES=\"%s\" names a device outside 0..%d: ignored, using every visible device\n", env, (have < GF2_MAX_DEVICES ? have : GF2_MAX_DEVICES) - 1);
       g_devices.clear();
     }
   }
@@ -1309,7 +1309,7 @@ int m4ri_amd_set_devices(int n, const int *ids) {
   int have = 0;
   if (hipGetDeviceCount(&have) != hipSuccess) have = 0;
   for (int i = 0; i < n; ++i)
-    if (ids[i] < 0 || ids[i] >= have || ids[i] >= 16) return -1;  // ... on device ids the per-device tables (arena, scratch: 16 entries) hold
+    if (ids[i] < 0 || ids[i] >= have || ids[i] >= GF2_MAX_DEVICES) return -1;  // ... on device ids the per-device tables (arena, scratch) hold
   g_devices.assign(ids, ids + n);
   g_devices_set = n > 0;  // n == 0: back to the default (M4RI_AMD_DEVICES or every visible device)
   return 0;

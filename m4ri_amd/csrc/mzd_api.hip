@@ -49,11 +49,10 @@ constexpr uint8_t FLAG_EXCESS = 0x2;  // mzd.h:144
 constexpr uint8_t FLAG_WINDOW = 0x4;  // mzd.h:150
 
 // The locks of the host entry points (the locking rule above)
-constexpr int ARENA_DEVICES = 16;
-std::mutex g_dev_mu[ARENA_DEVICES];
+std::mutex g_dev_mu[GF2_MAX_DEVICES];
 std::mutex g_pin_mu, g_stats_mu;
 std::unique_lock<std::mutex> lock_device(int dev) {  // a device HIP could not name or this table does not hold: slot 0
-  return std::unique_lock<std::mutex>(g_dev_mu[dev >= 0 && dev < ARENA_DEVICES ? dev : 0]);
+  return std::unique_lock<std::mutex>(g_dev_mu[dev >= 0 && dev < GF2_MAX_DEVICES ? dev : 0]);
 }
 std::unique_lock<std::mutex> lock_current_device() {
   int dev = 0;
@@ -283,14 +282,14 @@ struct Arena {
   size_t cap  = 0;  // words
   size_t used = 0;
 };
-Arena g_arenas[ARENA_DEVICES];  // one per HIP device: run() works on whatever device is current
+Arena g_arenas[GF2_MAX_DEVICES];  // one per HIP device: run() works on whatever device is current
 thread_local int g_arena_dev = 0;  // the device whose arena this thread is carving (set by arena_reserve, under that device's lock)
 #define g_arena g_arenas[g_arena_dev]
 
 void arena_reserve(size_t words) {
   int dev = 0;
   HIPDIE(hipGetDevice(&dev));
-  if (dev < 0 || dev >= ARENA_DEVICES) die("m4ri_amd: HIP device %d out of range\n", dev);
+  if (dev < 0 || dev >= GF2_MAX_DEVICES) die("m4ri_amd: HIP device %d out of range\n", dev);
   g_arena_dev = dev;
   g_arena.used = 0;
   if (words <= g_arena.cap) return;
@@ -364,7 +363,7 @@ struct HostStage {
   word *p    = nullptr;
   size_t cap = 0;  // words
 };
-HostStage g_host_stage[ARENA_DEVICES];
+HostStage g_host_stage[GF2_MAX_DEVICES];
 constexpr size_t SMALL_STAGE_BYTES = (size_t)2 << 20;  // A + B + C above this: the 2-D copies straight from / to the caller's rows (4096^3 = 6 MiB: 0.32 ms packed against 0.25 ms direct)
 
 word *host_stage(int dev, size_t words) {
@@ -465,7 +464,7 @@ struct PinLock {
   explicit PinLock(const mzd_t *M) {
     for (;;) {  // until the look and the lock agree: giving up would report a pinned matrix as "not pinned" (a stale host copy unnoticed)
       const int d = pin_device(M);
-      if (d < 0 || d >= ARENA_DEVICES) return;
+      if (d < 0 || d >= GF2_MAX_DEVICES) return;
       lk = std::unique_lock<std::mutex>(g_dev_mu[d]);
       Pin *q = find_pin(M);
       if (q && q->device == d) {
@@ -642,7 +641,7 @@ bool small_product_wanted(int64_t m, int64_t l, int64_t n, int64_t threshold) {
   return gf2_small_host_cost(m, l, n) <= (double)threshold / 240.0;
 }
 std::atomic<size_t> g_pipeline_min_bytes{(size_t)64 << 20};  // A + B + C bytes from which blocks are used (16384^3: 2.62 -> 2.42 ms, 24576^3: 6.3 -> 5.3 ms); 0 disables (m4ri_amd_set_host_pipeline)
-hipStream_t g_compute_stream[ARENA_DEVICES];
+hipStream_t g_compute_stream[GF2_MAX_DEVICES];
 
 bool run_pipelined(mzd_t *C, const mzd_t *A, const mzd_t *B, bool add, int cutoff, LateC *late) {
   const int64_t m = A->nrows, l = A->ncols, n = B->ncols;
@@ -1467,7 +1466,7 @@ void gf2_release_staging(void) {  // called by m4ri_amd_release_workspace: the c
   g_big_cache.drop();
   const std::unique_lock<std::mutex> lk = lock_current_device();
   int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= ARENA_DEVICES) return;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= GF2_MAX_DEVICES) return;
   if (g_host_stage[dev].p) {
     (void)hipDeviceSynchronize();
     (void)hipHostFree(g_host_stage[dev].p);

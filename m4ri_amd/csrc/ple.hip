@@ -30,7 +30,9 @@
 #include <cstring>
 #include <mutex>
 #include <vector>
+#include "dev_scratch.h"
 #include "gf2_internal.h"
+#include "row_gather.h"
 #include "../../include/m4ri_amd.h"
 
 namespace {
@@ -568,30 +570,10 @@ __global__ __launch_bounds__(QT_THREADS) void qtri_build_kernel(const uint32_t *
 template <bool LDSROW>
 __global__ __launch_bounds__(QT_THREADS) void qtri_gather_kernel(word *__restrict__ A, int64_t stride, int64_t width, int64_t wend, int64_t ncols,
                                                                   int64_t row_hi, const uint32_t *__restrict__ S, const word *__restrict__ rowcopy) {  // rowcopy: rows row_hi-g+1 .. row_hi
-  extern __shared__ word lrow[];
   const int i       = blockIdx.x;
   const int64_t rho = row_hi - i;
-  word *row         = A + rho * stride;
-  const word *src;
-  if (LDSROW) {
-    for (int64_t w = threadIdx.x; w < width; w += QT_THREADS) lrow[w] = row[w];
-    __syncthreads();
-    src = lrow;
-  } else {
-    src = rowcopy + (int64_t)(gridDim.x - 1 - i) * width;
-  }
-  const uint32_t *s = S + (int64_t)i * ncols;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int64_t w = rho / 64 + wave; w < wend; w += QT_THREADS / 64) {
-    const int64_t c = w * 64 + lane;
-    int bit         = 0;
-    if (c < ncols) {
-      const uint32_t sc = s[c];
-      bit               = (int)((src[sc >> 6] >> (sc & 63)) & 1);
-    }
-    const word v = __ballot(bit);
-    if (lane == 0) row[w] = v;
-  }
+  const word *copy  = LDSROW ? nullptr : rowcopy + (int64_t)(gridDim.x - 1 - i) * width;
+  gather_row<LDSROW, QT_THREADS>(A + rho * stride, width, copy, S + (int64_t)i * ncols, rho / 64, wend, ncols);
 }
 
 // ---- 6. the panel step ---------------------------------------------------------------------------------------------
@@ -636,24 +618,22 @@ __global__ __launch_bounds__(256) void ple_panel_scatter_kernel(word *__restrict
 #define PLE_PANEL_MAX 32
 
 // ---- per-device scratch ------------------------------------------------------------------------------------------
-struct Scratch {
-  word *V = nullptr, *Mc = nullptr, *Lc = nullptr, *pivmask = nullptr;
-  int32_t *Q = nullptr;
+struct PleScratch {
+  GrowBuf<word> V, Mc, Lc, pivmask;  // Lc holds 64 words per 64-column block of the matrix (a block's triangle is read later, on the side stream)
+  GrowBuf<int32_t> Q;
   PleBlock *blk = nullptr;
   PleBlock *hblk = nullptr;  // pinned host mirror
   int *lastrow = nullptr, *hlastrow = nullptr;
-  word *Lsq = nullptr, *Ubuf = nullptr;           // the panel step: multipliers among the pivot rows, the pivot rows' trailing parts
+  word *Lsq = nullptr;                            // the panel step: multipliers among the pivot rows,
+  GrowBuf<word> Ubuf;                             // and the pivot rows' trailing parts
   int32_t *rowmap = nullptr, *hrowmap = nullptr;  // panel column -> its pivot's row, or -1 (device; pinned host)
-  int64_t ubuf_words = 0;
-  int64_t lc_blocks = 0;          // Lc holds 64 words per 64-column block of the matrix (a block's triangle is read later, on the side stream)
   hipStream_t side = nullptr;     // the pivot rows' own solves run here, off the critical path
   hipEvent_t ev_main = nullptr, ev_side = nullptr, ev_copy = nullptr;
-  int64_t rows = 0, cols = 0;
 };
 std::mutex g_ple_mu;
-Scratch g_scratch[16];
+PleScratch g_scratch[GF2_MAX_DEVICES];
 
-int reserve(Scratch &s, int64_t nrows, int64_t ncols) {
+int reserve(PleScratch &s, int64_t nrows, int64_t ncols) {
   if (!s.blk) {
     HIPTRY(hipMalloc(reinterpret_cast<void **>(&s.blk), sizeof(PleBlock)));
     HIPTRY(hipHostMalloc(reinterpret_cast<void **>(&s.hblk), sizeof(PleBlock), hipHostMallocDefault));
@@ -667,35 +647,12 @@ int reserve(Scratch &s, int64_t nrows, int64_t ncols) {
     HIPTRY(hipMalloc(reinterpret_cast<void **>(&s.rowmap), (size_t)PLE_PANEL_MAX * 64 * 4));
     HIPTRY(hipHostMalloc(reinterpret_cast<void **>(&s.hrowmap), (size_t)2 * PLE_PANEL_MAX * 64 * 4, hipHostMallocDefault));  // two: see close_panel
   }
-  {
-    const int64_t need = (int64_t)PLE_PANEL_MAX * 64 * ((words_of(ncols) + 1) & ~(int64_t)1);
-    if (need > s.ubuf_words) {
-      if (s.Ubuf) { HIPTRY(hipDeviceSynchronize()); HIPTRY(hipFree(s.Ubuf)); }
-      s.Ubuf = nullptr; s.ubuf_words = 0;
-      HIPTRY(hipMalloc(reinterpret_cast<void **>(&s.Ubuf), (size_t)need * 8));
-      s.ubuf_words = need;
-    }
-  }
-  if (nrows > s.rows) {
-    if (s.V) { HIPTRY(hipFree(s.V)); HIPTRY(hipFree(s.Mc)); }
-    s.V = s.Mc = nullptr; s.rows = 0;
-    HIPTRY(hipMalloc(reinterpret_cast<void **>(&s.V), (size_t)nrows * 8));
-    HIPTRY(hipMalloc(reinterpret_cast<void **>(&s.Mc), (size_t)nrows * 8));
-    s.rows = nrows;
-  }
-  if (words_of(ncols) > s.lc_blocks) {
-    if (s.Lc) { HIPTRY(hipDeviceSynchronize()); HIPTRY(hipFree(s.Lc)); }
-    s.Lc = nullptr; s.lc_blocks = 0;
-    HIPTRY(hipMalloc(reinterpret_cast<void **>(&s.Lc), (size_t)words_of(ncols) * 64 * 8));
-    s.lc_blocks = words_of(ncols);
-  }
-  if (ncols > s.cols) {
-    if (s.Q) { HIPTRY(hipFree(s.Q)); HIPTRY(hipFree(s.pivmask)); }
-    s.Q = nullptr; s.pivmask = nullptr; s.cols = 0;
-    HIPTRY(hipMalloc(reinterpret_cast<void **>(&s.Q), (size_t)ncols * 4));
-    HIPTRY(hipMalloc(reinterpret_cast<void **>(&s.pivmask), (size_t)words_of(ncols) * 8));
-    s.cols = ncols;
-  }
+  HIPTRY(s.Ubuf.reserve((size_t)PLE_PANEL_MAX * 64 * (size_t)((words_of(ncols) + 1) & ~(int64_t)1)));
+  HIPTRY(s.V.reserve((size_t)nrows));
+  HIPTRY(s.Mc.reserve((size_t)nrows));
+  HIPTRY(s.Lc.reserve((size_t)words_of(ncols) * 64));
+  HIPTRY(s.Q.reserve((size_t)ncols));
+  HIPTRY(s.pivmask.reserve((size_t)words_of(ncols)));
   return 0;
 }
 
@@ -705,7 +662,7 @@ struct PleRun {
   int64_t stride, nrows, ncols, width;
   int32_t *P, *Q;
   hipStream_t st;
-  Scratch *s;
+  PleScratch *s;
   int64_t r0;      // rows finished so far = pivots found so far
   int64_t cutoff;  // __M4RI_PLE_CUTOFF of the reference build being matched (words); 0: no recursion
   bool side_used = false;
@@ -719,7 +676,7 @@ struct PleRun {
 // bring the words to the right of the finished panel up to date (see "the panel step" above)
 int close_panel(PleRun &R) {
   if (R.pw0 < 0) return 0;
-  Scratch &s = *R.s;
+  PleScratch &s = *R.s;
   word *A    = R.A;
   hipStream_t st = R.st;
   const int64_t stride = R.stride, p0 = R.pw0, pend = R.pend, rp = R.r0 - R.prow0, pwn = pend - p0, wtrail = R.width - pend;
@@ -731,14 +688,14 @@ int close_panel(PleRun &R) {
     HIPTRY(hipStreamWaitEvent(st, s.ev_side, 0));
   }
   HIPTRY(hipMemcpyAsync(s.rowmap, s.hrowmap + R.which * PLE_PANEL_MAX * 64, (size_t)pwn * 64 * 4, hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(ple_panel_gather_kernel, dim3((unsigned)(pwn * 64)), dim3(256), 0, st, A, stride, p0, (int)pwn, pend, wtrail, s.rowmap, s.Lsq, s.Ubuf,
+  hipLaunchKernelGGL(ple_panel_gather_kernel, dim3((unsigned)(pwn * 64)), dim3(256), 0, st, A, stride, p0, (int)pwn, pend, wtrail, s.rowmap, s.Lsq, s.Ubuf.p,
                      ustride);
   HIPTRY(hipGetLastError());
-  HIPTRY(m4ri_amd_trsm_lower_left_dev(s.Lsq, pwn, s.Ubuf, ustride, pwn * 64, trailcols, 0, st));
-  hipLaunchKernelGGL(ple_panel_scatter_kernel, dim3((unsigned)(pwn * 64)), dim3(256), 0, st, A, stride, pend, wtrail, s.rowmap, s.Ubuf, ustride);
+  HIPTRY(m4ri_amd_trsm_lower_left_dev(s.Lsq, pwn, s.Ubuf.p, ustride, pwn * 64, trailcols, 0, st));
+  hipLaunchKernelGGL(ple_panel_scatter_kernel, dim3((unsigned)(pwn * 64)), dim3(256), 0, st, A, stride, pend, wtrail, s.rowmap, s.Ubuf.p, ustride);
   HIPTRY(hipGetLastError());
   if (R.nrows - R.r0 > 0)
-    HIPTRY(m4ri_amd_mul_dev(A + R.r0 * stride + pend, stride, A + R.r0 * stride + p0, stride, s.Ubuf, ustride, R.nrows - R.r0, pwn * 64, trailcols, 1, 0, st));
+    HIPTRY(m4ri_amd_mul_dev(A + R.r0 * stride + pend, stride, A + R.r0 * stride + p0, stride, s.Ubuf.p, ustride, R.nrows - R.r0, pwn * 64, trailcols, 1, 0, st));
   // the next panel fills the OTHER host map; this one is reused a panel later, by when at least one block's record has been
   // waited for that follows this copy in the stream
   R.which ^= 1;
@@ -747,7 +704,7 @@ int close_panel(PleRun &R) {
 
 // Columns [c0, c1) (c0 on a word boundary) in blocks of 64: the t-th pivot found goes to Q[c0 + t].
 int ple_blocks(PleRun &R, int64_t c0, int64_t c1, int64_t *found) {
-  Scratch &s = *R.s;
+  PleScratch &s = *R.s;
   word *A = R.A;
   const int64_t stride = R.stride, nrows = R.nrows, ncols = R.ncols, width = R.width, first = R.r0;
   hipStream_t st = R.st;
@@ -778,7 +735,7 @@ int ple_blocks(PleRun &R, int64_t c0, int64_t c1, int64_t *found) {
     const int64_t r0 = R.r0;
     const int ncb = (int)((c1 - wb * 64) < 64 ? (c1 - wb * 64) : 64);
     const int64_t nleft = nrows - r0;
-    word *Lc = s.Lc + wb * 64;
+    word *Lc = s.Lc.p + wb * 64;
     const unsigned row_grid = (unsigned)((nleft + ROW_THREADS - 1) / ROW_THREADS);
     // rows below, words to the right: C ^= (M L^-1) * U*, inner dimension = the block's rank, U* the pivot rows as they are;
     // dev_rank: the kernel takes the rank from the block's record (it is launched before the host has read it)
@@ -789,8 +746,8 @@ int ple_blocks(PleRun &R, int64_t c0, int64_t c1, int64_t *found) {
       const int skip       = (int)(wb + 1 - wfirst);
       word *C              = A + (r0 + rank) * stride + wfirst;
       const word *U        = A + r0 * stride + wfirst;
-      if (vec) HIPTRY(launch_rank_update<true>(st, variant, C, stride, s.Mc, U, stride, nleft - rank, wn, rank, skip, dev_rank ? s.blk : nullptr));
-      else HIPTRY(launch_rank_update<false>(st, variant, C, stride, s.Mc, U, stride, nleft - rank, wn, rank, skip, dev_rank ? s.blk : nullptr));
+      if (vec) HIPTRY(launch_rank_update<true>(st, variant, C, stride, s.Mc.p, U, stride, nleft - rank, wn, rank, skip, dev_rank ? s.blk : nullptr));
+      else HIPTRY(launch_rank_update<false>(st, variant, C, stride, s.Mc.p, U, stride, nleft - rank, wn, rank, skip, dev_rank ? s.blk : nullptr));
       return 0;
     };
     int rank = 0;
@@ -804,7 +761,7 @@ int ple_blocks(PleRun &R, int64_t c0, int64_t c1, int64_t *found) {
       HIPTRY(hipGetLastError());
       HIPTRY(hipEventRecord(s.ev_copy, st));
       hipLaunchKernelGGL(ple_permute_rows_kernel, dim3((unsigned)((width + PERM_TW - 1) / PERM_TW)), dim3(ROW_THREADS), 0, st, A, stride, width, wb, r0, s.blk);
-      hipLaunchKernelGGL(ple_finish_kernel, dim3(row_grid), dim3(ROW_THREADS), 0, st, A, stride, nrows, r0, wb, col, stride, s.blk, s.Mc, Lc);
+      hipLaunchKernelGGL(ple_finish_kernel, dim3(row_grid), dim3(ROW_THREADS), 0, st, A, stride, nrows, r0, wb, col, stride, s.blk, s.Mc.p, Lc);
       HIPTRY(hipGetLastError());
       if (int rc = update(0, true)) return rc;
       HIPTRY(hipEventRecord(s.ev_main, st));
@@ -825,7 +782,7 @@ int ple_blocks(PleRun &R, int64_t c0, int64_t c1, int64_t *found) {
           if (rank > 0) {
             hipLaunchKernelGGL(ple_permute_rows_kernel, dim3((unsigned)((width + PERM_TW - 1) / PERM_TW)), dim3(ROW_THREADS), 0, st, A, stride, width, wb, r0,
                                s.blk);
-            hipLaunchKernelGGL(ple_finish_kernel, dim3(row_grid), dim3(ROW_THREADS), 0, st, A, stride, nrows, r0, wb, col, stride, s.blk, s.Mc, Lc);
+            hipLaunchKernelGGL(ple_finish_kernel, dim3(row_grid), dim3(ROW_THREADS), 0, st, A, stride, nrows, r0, wb, col, stride, s.blk, s.Mc.p, Lc);
             HIPTRY(hipGetLastError());
             if (int rc = update(rank, false)) return rc;
             HIPTRY(hipEventRecord(s.ev_main, st));
@@ -836,8 +793,8 @@ int ple_blocks(PleRun &R, int64_t c0, int64_t c1, int64_t *found) {
       }
     }
     if (!done) {  // the general search works on a dense copy of the slice
-      hipLaunchKernelGGL(ple_extract_kernel, dim3(row_grid), dim3(ROW_THREADS), 0, st, A, stride, nrows, r0, wb, s.V);
-      hipLaunchKernelGGL(ple_pivots_kernel, dim3(1), dim3(SLICE_THREADS), 0, st, nleft, r0, ncb, s.V, s.blk);
+      hipLaunchKernelGGL(ple_extract_kernel, dim3(row_grid), dim3(ROW_THREADS), 0, st, A, stride, nrows, r0, wb, s.V.p);
+      hipLaunchKernelGGL(ple_pivots_kernel, dim3(1), dim3(SLICE_THREADS), 0, st, nleft, r0, ncb, s.V.p, s.blk);
       HIPTRY(hipGetLastError());
       HIPTRY(hipMemcpyAsync(s.hblk, s.blk, sizeof(PleBlock), hipMemcpyDeviceToHost, st));
       HIPTRY(hipStreamSynchronize(st));
@@ -845,7 +802,7 @@ int ple_blocks(PleRun &R, int64_t c0, int64_t c1, int64_t *found) {
       if (rank > 0) {
         hipLaunchKernelGGL(ple_swap_rows_kernel, dim3((unsigned)((width + ROW_THREADS - 1) / ROW_THREADS)), dim3(ROW_THREADS), 0, st, A, stride, width, wb, r0,
                            s.blk);
-        hipLaunchKernelGGL(ple_finish_kernel, dim3(row_grid), dim3(ROW_THREADS), 0, st, A, stride, nrows, r0, wb, s.V, (int64_t)1, s.blk, s.Mc, Lc);
+        hipLaunchKernelGGL(ple_finish_kernel, dim3(row_grid), dim3(ROW_THREADS), 0, st, A, stride, nrows, r0, wb, s.V.p, (int64_t)1, s.blk, s.Mc.p, Lc);
         HIPTRY(hipGetLastError());
         if (int rc = update(rank, false)) return rc;
         HIPTRY(hipEventRecord(s.ev_main, st));
@@ -906,7 +863,7 @@ int ple_rec(PleRun &R, int64_t rows, int64_t c0, int64_t c1, int64_t *found) {
   for (int64_t c = c0; c < c1; ++c) R.Q[c] = (int32_t)c;
   *found = 0;
   if (rows <= 0) return 0;
-  Scratch &s = *R.s;
+  PleScratch &s = *R.s;
   if (R.pw0 >= 0 && c0 / 64 + width > R.pend)  // the window reaches beyond the open panel, where the panel's update is still due
     if (int rc = close_panel(R)) return rc;
   HIPTRY(hipMemsetAsync(s.lastrow, 0, sizeof(int), R.st));
@@ -945,9 +902,8 @@ int m4ri_amd_ple_dev(word *A, int64_t stride, int64_t nrows, int64_t ncols, int3
   if (nrows == 0 || ncols == 0) return 0;
   std::lock_guard<std::mutex> lk(g_ple_mu);
   int dev = 0;
-  HIPTRY(hipGetDevice(&dev));
-  if (dev < 0 || dev >= 16) return (int)hipErrorInvalidDevice;
-  Scratch &s = g_scratch[dev];
+  HIPTRY(device_slot(&dev));
+  PleScratch &s = g_scratch[dev];
   if (int rc = reserve(s, nrows, ncols)) return rc;
   const int64_t width = words_of(ncols);
   PleRun run{A, stride, nrows, ncols, width, P, Q, st, &s, 0, recursion_cutoff};
@@ -966,10 +922,10 @@ int m4ri_amd_ple_dev(word *A, int64_t stride, int64_t nrows, int64_t ncols, int3
     bool identity = true;
     for (int j = 0; j < rank; ++j) { pm[(size_t)(Q[j] >> 6)] |= (word)1 << (Q[j] & 63); identity = identity && Q[j] == j; }
     if (!identity) {  // pivots on the diagonal: L already sits where it belongs
-      HIPTRY(hipMemcpyAsync(s.Q, Q, (size_t)rank * 4, hipMemcpyHostToDevice, st));
-      HIPTRY(hipMemcpyAsync(s.pivmask, pm.data(), (size_t)width * 8, hipMemcpyHostToDevice, st));
+      HIPTRY(hipMemcpyAsync(s.Q.p, Q, (size_t)rank * 4, hipMemcpyHostToDevice, st));
+      HIPTRY(hipMemcpyAsync(s.pivmask.p, pm.data(), (size_t)width * 8, hipMemcpyHostToDevice, st));
       hipLaunchKernelGGL(ple_compress_kernel, dim3((unsigned)nrows), dim3(ROW_THREADS), (size_t)((rank - 1) / 64 + 1) * 8, st, A, stride, nrows, width,
-                         s.Q, s.pivmask, rank);
+                         s.Q.p, s.pivmask.p, rank);
       HIPTRY(hipGetLastError());
       HIPTRY(hipStreamSynchronize(st));  // pm / Q are host temporaries of this call
     }
@@ -1024,40 +980,34 @@ int m4ri_amd_apply_p_right_trans_tri_dev(word *A, int64_t stride, int64_t nrows,
   int32_t *d_cnt = nullptr;
   word *d_rowcopy = nullptr;
   const bool ldsrow = width * 8 <= 64 * 1024;
-  int rc = 0;
-  auto run = [&]() -> int {
-    HIPTRY(hipMalloc(reinterpret_cast<void **>(&d_base[0]), (size_t)ncols * 4));
-    HIPTRY(hipMalloc(reinterpret_cast<void **>(&d_base[1]), (size_t)ncols * 4));
-    HIPTRY(hipMalloc(reinterpret_cast<void **>(&d_S), (size_t)G * ncols * 4));
-    HIPTRY(hipMalloc(reinterpret_cast<void **>(&d_writes), (writes.size() + 1) * sizeof(int2)));
-    HIPTRY(hipMalloc(reinterpret_cast<void **>(&d_cnt), cnts.size() * 4));
-    if (!ldsrow) HIPTRY(hipMalloc(reinterpret_cast<void **>(&d_rowcopy), (size_t)G * width * 8));
-    HIPTRY(hipMemcpyAsync(d_base[0], base0.data(), (size_t)ncols * 4, hipMemcpyHostToDevice, st));
-    if (!writes.empty()) HIPTRY(hipMemcpyAsync(d_writes, writes.data(), writes.size() * sizeof(int2), hipMemcpyHostToDevice, st));
-    HIPTRY(hipMemcpyAsync(d_cnt, cnts.data(), cnts.size() * 4, hipMemcpyHostToDevice, st));
-    int cur = 0;
-    for (const Group &gr : groups) {
-      hipLaunchKernelGGL(qtri_build_kernel, dim3((unsigned)gr.g + 1), dim3(QT_THREADS), 0, st, d_base[cur], d_S, d_base[cur ^ 1], ncols,
-                         d_writes + gr.woff, d_cnt + gr.coff, gr.g);
-      if (ldsrow) {
-        hipLaunchKernelGGL((qtri_gather_kernel<true>), dim3((unsigned)gr.g), dim3(QT_THREADS), (size_t)width * 8, st, A, stride, width, wend, ncols, gr.hi,
-                           d_S, nullptr);
-      } else {
-        const word *lo = A + (gr.hi - gr.g + 1) * stride;
-        HIPTRY(hipMemcpy2DAsync(d_rowcopy, (size_t)width * 8, lo, (size_t)stride * 8, (size_t)width * 8, (size_t)gr.g, hipMemcpyDeviceToDevice, st));
-        hipLaunchKernelGGL((qtri_gather_kernel<false>), dim3((unsigned)gr.g), dim3(QT_THREADS), 0, st, A, stride, width, wend, ncols, gr.hi, d_S,
-                           d_rowcopy);
-      }
-      HIPTRY(hipGetLastError());
-      cur ^= 1;
+  Scratch tmp(st);
+  HIPTRY(tmp.alloc(&d_base[0], (size_t)ncols));
+  HIPTRY(tmp.alloc(&d_base[1], (size_t)ncols));
+  HIPTRY(tmp.alloc(&d_S, (size_t)G * ncols));
+  HIPTRY(tmp.alloc(&d_writes, writes.size() + 1));
+  HIPTRY(tmp.alloc(&d_cnt, cnts.size()));
+  if (!ldsrow) HIPTRY(tmp.alloc(&d_rowcopy, (size_t)G * width));
+  HIPTRY(hipMemcpyAsync(d_base[0], base0.data(), (size_t)ncols * 4, hipMemcpyHostToDevice, st));
+  if (!writes.empty()) HIPTRY(hipMemcpyAsync(d_writes, writes.data(), writes.size() * sizeof(int2), hipMemcpyHostToDevice, st));
+  HIPTRY(hipMemcpyAsync(d_cnt, cnts.data(), cnts.size() * 4, hipMemcpyHostToDevice, st));
+  int cur = 0;
+  for (const Group &gr : groups) {
+    hipLaunchKernelGGL(qtri_build_kernel, dim3((unsigned)gr.g + 1), dim3(QT_THREADS), 0, st, d_base[cur], d_S, d_base[cur ^ 1], ncols,
+                       d_writes + gr.woff, d_cnt + gr.coff, gr.g);
+    if (ldsrow) {
+      hipLaunchKernelGGL((qtri_gather_kernel<true>), dim3((unsigned)gr.g), dim3(QT_THREADS), (size_t)width * 8, st, A, stride, width, wend, ncols, gr.hi,
+                         d_S, nullptr);
+    } else {
+      const word *lo = A + (gr.hi - gr.g + 1) * stride;
+      HIPTRY(hipMemcpy2DAsync(d_rowcopy, (size_t)width * 8, lo, (size_t)stride * 8, (size_t)width * 8, (size_t)gr.g, hipMemcpyDeviceToDevice, st));
+      hipLaunchKernelGGL((qtri_gather_kernel<false>), dim3((unsigned)gr.g), dim3(QT_THREADS), 0, st, A, stride, width, wend, ncols, gr.hi, d_S,
+                         d_rowcopy);
     }
-    HIPTRY(hipStreamSynchronize(st));
-    return 0;
-  };
-  rc = run();
-  for (void *p : {(void *)d_base[0], (void *)d_base[1], (void *)d_S, (void *)d_writes, (void *)d_cnt, (void *)d_rowcopy})
-    if (p) (void)hipFree(p);
-  return rc;
+    HIPTRY(hipGetLastError());
+    cur ^= 1;
+  }
+  HIPTRY(hipStreamSynchronize(st));
+  return tmp.done();
 }
 
 // PLUQ in place (ple.c:50-60): the PLE above, then the column step on the first `rank` rows (all rows when the rank

@@ -9,6 +9,7 @@
 // cross PCIe once per step).
 #include <hip/hip_runtime.h>
 #include <vector>
+#include "dev_scratch.h"
 #include "gf2_internal.h"
 #include "../../include/m4ri_amd.h"
 
@@ -68,34 +69,28 @@ int zero_rows(word *A, int64_t stride, int64_t r0, int64_t r1, int64_t width, hi
 int is_zero(const word *A, int64_t stride, int64_t rows, int64_t width, hipStream_t st, bool *zero) {
   *zero = true;
   if (rows <= 0 || width <= 0) return 0;
+  Scratch tmp(st);
   int *d = nullptr, h = 0;
-  HIPTRY(hipMalloc(reinterpret_cast<void **>(&d), sizeof(int)));
-  int rc = (int)hipMemsetAsync(d, 0, sizeof(int), st);
-  if (!rc) {
-    hipLaunchKernelGGL(any_nonzero_kernel, dim3((unsigned)rows), dim3(SV_THREADS), 0, st, A, stride, rows, width, d);
-    rc = (int)hipGetLastError();
-  }
-  if (!rc) rc = (int)hipMemcpyAsync(&h, d, sizeof(int), hipMemcpyDeviceToHost, st);
-  if (!rc) rc = (int)hipStreamSynchronize(st);
-  (void)hipFree(d);
+  HIPTRY(tmp.alloc(&d, 1));
+  HIPTRY(hipMemsetAsync(d, 0, sizeof(int), st));
+  hipLaunchKernelGGL(any_nonzero_kernel, dim3((unsigned)rows), dim3(SV_THREADS), 0, st, A, stride, rows, width, d);
+  HIPTRY(hipGetLastError());
+  HIPTRY(hipMemcpyAsync(&h, d, sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPTRY(hipStreamSynchronize(st));
   *zero = h == 0;
-  return rc;
-}
-
-// a clean copy of the leading r x r block of A (its last word masked to r columns): the triangular solves split their
-// triangle into blocks that go to the multiply engine as operands, which must not carry bits of the neighbouring columns
-int square_copy(word **out, const word *A, int64_t stride, int64_t r, hipStream_t st) {
-  *out = nullptr;
-  if (r <= 0) return 0;
-  const int64_t wr = words_of(r);
-  HIPTRY(hipMalloc(reinterpret_cast<void **>(out), (size_t)r * wr * 8));
-  HIPTRY(hipMemcpy2DAsync(*out, (size_t)wr * 8, A, (size_t)stride * 8, (size_t)wr * 8, (size_t)r, hipMemcpyDeviceToDevice, st));
-  return m4ri_amd_mask_tail_dev(*out, wr, r, r, st);
+  return tmp.done();
 }
 
 }  // namespace
 
 extern "C" {
+
+int gf2_square_copy(word *dst, const word *A, int64_t stride, int64_t r, hipStream_t st) {
+  if (r <= 0) return 0;
+  const int64_t wr = words_of(r);
+  HIPTRY(hipMemcpy2DAsync(dst, (size_t)wr * 8, A, (size_t)stride * 8, (size_t)wr * 8, (size_t)r, hipMemcpyDeviceToDevice, st));
+  return m4ri_amd_mask_tail_dev(dst, wr, r, r, st);
+}
 
 // The row transpositions (i, P[i]), i < min(length, nrows), ascending (trans == 0: mzd_apply_p_left) or descending
 // (mzd_apply_p_left_trans), mzp.c:65-81.  P: HOST array.  Blocking.
@@ -119,23 +114,18 @@ int m4ri_amd_apply_p_left_dev(word *A, int64_t stride, int64_t nrows, int64_t nc
     if (src[(size_t)r] != r) { moved.push_back((int32_t)r); from.push_back(src[(size_t)r]); }
   if (moved.empty()) return (int)hipStreamSynchronize(st);  // "blocking": whatever the caller queued on A is complete on return
   const int64_t width = words_of(ncols), k = (int64_t)moved.size();
-  word *tmp = nullptr;
+  Scratch tmp(st);
+  word *rows = nullptr;
   int32_t *d_idx = nullptr;
-  auto run = [&]() -> int {
-    HIPTRY(hipMalloc(reinterpret_cast<void **>(&tmp), (size_t)k * width * 8));
-    HIPTRY(hipMalloc(reinterpret_cast<void **>(&d_idx), (size_t)k * 8));
-    HIPTRY(hipMemcpyAsync(d_idx, from.data(), (size_t)k * 4, hipMemcpyHostToDevice, st));
-    HIPTRY(hipMemcpyAsync(d_idx + k, moved.data(), (size_t)k * 4, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)k), dim3(SV_THREADS), 0, st, tmp, width, A, stride, width, d_idx);
-    hipLaunchKernelGGL(scatter_rows_kernel, dim3((unsigned)k), dim3(SV_THREADS), 0, st, A, stride, tmp, width, width, d_idx + k);
-    HIPTRY(hipGetLastError());
-    HIPTRY(hipStreamSynchronize(st));
-    return 0;
-  };
-  const int rc = run();
-  if (tmp) (void)hipFree(tmp);
-  if (d_idx) (void)hipFree(d_idx);
-  return rc;
+  HIPTRY(tmp.alloc(&rows, (size_t)k * width));
+  HIPTRY(tmp.alloc(&d_idx, (size_t)k * 2));
+  HIPTRY(hipMemcpyAsync(d_idx, from.data(), (size_t)k * 4, hipMemcpyHostToDevice, st));
+  HIPTRY(hipMemcpyAsync(d_idx + k, moved.data(), (size_t)k * 4, hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)k), dim3(SV_THREADS), 0, st, rows, width, A, stride, width, d_idx);
+  hipLaunchKernelGGL(scatter_rows_kernel, dim3((unsigned)k), dim3(SV_THREADS), 0, st, A, stride, rows, width, width, d_idx + k);
+  HIPTRY(hipGetLastError());
+  HIPTRY(hipStreamSynchronize(st));
+  return tmp.done();
 }
 
 // B <- the solution steps of _mzd_pluq_solve_left (solve.c:57-121) for a device matrix A that holds its PLUQ
@@ -149,28 +139,26 @@ int m4ri_amd_pluq_solve_left_dev(const word *A, int64_t a_stride, int64_t m, int
   hipStream_t st = (hipStream_t)stream;
   *retval = 0;
   const int64_t bw = words_of(b_cols), wr = words_of(rank);
+  Scratch tmp(st);
   word *LU = nullptr;
-  auto run = [&]() -> int {
-    if (int rc = m4ri_amd_apply_p_left_dev(B, b_stride, b_rows, b_cols, P, m, 0, st)) return rc;                       // solve.c:72
-    if (int rc = square_copy(&LU, A, a_stride, rank, st)) return rc;                                                   // :76
-    if (int rc = m4ri_amd_trsm_lower_left_dev(LU, wr, B, b_stride, rank, b_cols, cutoff, st)) return rc;               // :77-79
-    if (inconsistency_check) {                                                                                         // :81-98
-      if (m < b_rows) HIPTRY(zero_rows(B, b_stride, m, b_rows, bw, st));
-      if (m > rank && rank > 0 && b_cols > 0)  // the rows of A behind the rank hold L only: nothing beyond column `rank`
-        HIPTRY(m4ri_amd_mul_dev(B + (int64_t)rank * b_stride, b_stride, A + (int64_t)rank * a_stride, a_stride, B, b_stride, m - rank, rank, b_cols, 1,
-                                cutoff, st));
-      bool zero = true;
-      if (int rc = is_zero(B + (int64_t)rank * b_stride, b_stride, m - rank, bw, st, &zero)) return rc;
-      if (!zero) *retval = -1;
-    }
-    if (int rc = m4ri_amd_trsm_upper_left_dev(LU, wr, B, b_stride, rank, b_cols, cutoff, st)) return rc;               // :100
-    if (!inconsistency_check) HIPTRY(zero_rows(B, b_stride, rank, b_rows, bw, st));                                    // :104-114
-    if (int rc = m4ri_amd_apply_p_left_dev(B, b_stride, b_rows, b_cols, Q, n, 1, st)) return rc;                       // :116
-    return (int)hipStreamSynchronize(st);
-  };
-  const int rc = run();
-  if (LU) (void)hipFree(LU);
-  return rc;
+  HIPTRY(m4ri_amd_apply_p_left_dev(B, b_stride, b_rows, b_cols, P, m, 0, st));                       // solve.c:72
+  if (rank > 0) HIPTRY(tmp.alloc(&LU, (size_t)rank * wr));
+  HIPTRY(gf2_square_copy(LU, A, a_stride, rank, st));                                                // :76
+  HIPTRY(m4ri_amd_trsm_lower_left_dev(LU, wr, B, b_stride, rank, b_cols, cutoff, st));               // :77-79
+  if (inconsistency_check) {                                                                         // :81-98
+    if (m < b_rows) HIPTRY(zero_rows(B, b_stride, m, b_rows, bw, st));
+    if (m > rank && rank > 0 && b_cols > 0)  // the rows of A behind the rank hold L only: nothing beyond column `rank`
+      HIPTRY(m4ri_amd_mul_dev(B + (int64_t)rank * b_stride, b_stride, A + (int64_t)rank * a_stride, a_stride, B, b_stride, m - rank, rank, b_cols, 1,
+                              cutoff, st));
+    bool zero = true;
+    HIPTRY(is_zero(B + (int64_t)rank * b_stride, b_stride, m - rank, bw, st, &zero));
+    if (!zero) *retval = -1;
+  }
+  HIPTRY(m4ri_amd_trsm_upper_left_dev(LU, wr, B, b_stride, rank, b_cols, cutoff, st));               // :100
+  if (!inconsistency_check) HIPTRY(zero_rows(B, b_stride, rank, b_rows, bw, st));                    // :104-114
+  HIPTRY(m4ri_amd_apply_p_left_dev(B, b_stride, b_rows, b_cols, Q, n, 1, st));                       // :116
+  HIPTRY(hipStreamSynchronize(st));
+  return tmp.done();
 }
 
 // _mzd_solve_left (solve.c:123-152): A <- its PLUQ decomposition (the reference's flavour, recursion leftovers in Q
@@ -207,12 +195,13 @@ int m4ri_amd_kernel_left_pluq_dev(word *A, int64_t a_stride, int64_t m, int64_t 
   if (r > 0) {
     hipLaunchKernelGGL(extract_cols_kernel, dim3((unsigned)r), dim3(SV_THREADS), 0, st, R, r_stride, A, a_stride, words_of(n), (int64_t)r, kc);   // :170-175
     HIPTRY(hipGetLastError());
+    Scratch tmp(st);
     word *U = nullptr;
-    int rc  = square_copy(&U, A, a_stride, r, st);
-    if (!rc) rc = m4ri_amd_trsm_upper_left_dev(U, words_of(r), R, r_stride, r, kc, cutoff, st);                                                   // :177
-    if (!rc) rc = (int)hipStreamSynchronize(st);
-    if (U) (void)hipFree(U);
-    if (rc) return rc;
+    HIPTRY(tmp.alloc(&U, (size_t)r * words_of(r)));
+    HIPTRY(gf2_square_copy(U, A, a_stride, r, st));
+    HIPTRY(m4ri_amd_trsm_upper_left_dev(U, words_of(r), R, r_stride, r, kc, cutoff, st));                                                         // :177
+    HIPTRY(hipStreamSynchronize(st));
+    tmp.done();
   }
   hipLaunchKernelGGL(set_diagonal_kernel, dim3((unsigned)((kc + 255) / 256)), dim3(256), 0, st, R, r_stride, (int64_t)r, (int64_t)0, kc);        // :179
   HIPTRY(hipGetLastError());
@@ -230,40 +219,36 @@ int m4ri_amd_inv_dev(word *Binv, int64_t b_stride, const word *A, int64_t a_stri
   if (n == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
   const int64_t wn = words_of(n), cw = 2 * wn, ws = (wn + 1) & ~(int64_t)1;
+  Scratch tmp(st);
   word *C = nullptr;
-  HIPTRY(hipMalloc(reinterpret_cast<void **>(&C), (size_t)n * (size_t)(cw > ws ? cw : ws) * 8));
-  auto by_decomposition = [&](bool &done) -> int {
-    done = false;
+  HIPTRY(tmp.alloc(&C, (size_t)n * (size_t)(cw > ws ? cw : ws)));
+  {  // by decomposition
     HIPTRY(hipMemcpy2DAsync(C, (size_t)ws * 8, A, (size_t)a_stride * 8, (size_t)wn * 8, (size_t)n, hipMemcpyDeviceToDevice, st));
     if (ws != wn) HIPTRY(hipMemset2DAsync(C + wn, (size_t)ws * 8, 0, 8, (size_t)n, st));
     HIPTRY(m4ri_amd_mask_tail_dev(C, ws, n, n, st));
     std::vector<int32_t> P((size_t)n), Q((size_t)n);
     int32_t rank = 0;
-    if (int rc = m4ri_amd_pluq_dev(C, ws, n, n, P.data(), Q.data(), &rank, 0, st)) return rc;
-    if (rank != n) return 0;
-    HIPTRY(hipMemset2DAsync(Binv, (size_t)b_stride * 8, 0, (size_t)wn * 8, (size_t)n, st));
-    hipLaunchKernelGGL(set_diagonal_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, Binv, b_stride, (int64_t)0, (int64_t)0, n);
-    HIPTRY(hipGetLastError());
-    int ret = 0;
-    if (int rc = m4ri_amd_pluq_solve_left_dev(C, ws, n, n, rank, P.data(), Q.data(), Binv, b_stride, n, n, 0, 0, &ret, st)) return rc;
-    done = true;
-    return (int)hipStreamSynchronize(st);
-  };
-  auto by_elimination = [&]() -> int {
-    HIPTRY(hipMemsetAsync(C, 0, (size_t)n * cw * 8, st));
-    HIPTRY(hipMemcpy2DAsync(C, (size_t)cw * 8, A, (size_t)a_stride * 8, (size_t)wn * 8, (size_t)n, hipMemcpyDeviceToDevice, st));
-    hipLaunchKernelGGL(set_diagonal_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, C, cw, (int64_t)0, wn * 64, n);
-    HIPTRY(hipGetLastError());
-    int32_t rank = 0;
-    if (int rc = m4ri_amd_echelonize_dev(C, cw, n, cw * 64, 1, &rank, st)) return rc;
-    HIPTRY(hipMemcpy2DAsync(Binv, (size_t)b_stride * 8, C + wn, (size_t)cw * 8, (size_t)wn * 8, (size_t)n, hipMemcpyDeviceToDevice, st));
-    return (int)hipStreamSynchronize(st);
-  };
-  bool done = false;
-  int rc = by_decomposition(done);
-  if (rc == 0 && !done) rc = by_elimination();
-  (void)hipFree(C);
-  return rc;
+    HIPTRY(m4ri_amd_pluq_dev(C, ws, n, n, P.data(), Q.data(), &rank, 0, st));
+    if (rank == n) {
+      HIPTRY(hipMemset2DAsync(Binv, (size_t)b_stride * 8, 0, (size_t)wn * 8, (size_t)n, st));
+      hipLaunchKernelGGL(set_diagonal_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, Binv, b_stride, (int64_t)0, (int64_t)0, n);
+      HIPTRY(hipGetLastError());
+      int ret = 0;
+      HIPTRY(m4ri_amd_pluq_solve_left_dev(C, ws, n, n, rank, P.data(), Q.data(), Binv, b_stride, n, n, 0, 0, &ret, st));
+      HIPTRY(hipStreamSynchronize(st));
+      return tmp.done();
+    }
+  }
+  // by elimination
+  HIPTRY(hipMemsetAsync(C, 0, (size_t)n * cw * 8, st));
+  HIPTRY(hipMemcpy2DAsync(C, (size_t)cw * 8, A, (size_t)a_stride * 8, (size_t)wn * 8, (size_t)n, hipMemcpyDeviceToDevice, st));
+  hipLaunchKernelGGL(set_diagonal_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, C, cw, (int64_t)0, wn * 64, n);
+  HIPTRY(hipGetLastError());
+  int32_t rank = 0;
+  HIPTRY(m4ri_amd_echelonize_dev(C, cw, n, cw * 64, 1, &rank, st));
+  HIPTRY(hipMemcpy2DAsync(Binv, (size_t)b_stride * 8, C + wn, (size_t)cw * 8, (size_t)wn * 8, (size_t)n, hipMemcpyDeviceToDevice, st));
+  HIPTRY(hipStreamSynchronize(st));
+  return tmp.done();
 }
 
 }  // extern "C"

@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 #include <mutex>
 #include <stdlib.h>
+#include "dev_scratch.h"
 #include "gf2_internal.h"
 #include "../../include/m4ri_amd.h"
 
@@ -167,11 +168,10 @@ __global__ __launch_bounds__(TB) void trsm_invert_blocks_kernel(const word *__re
 }
 
 struct TrsmScratch {
-  word *inv = nullptr, *tmp = nullptr, *big = nullptr, *mid = nullptr;  // big: inverses of 4096-row blocks; mid: the middle products while building them
-  size_t inv_words = 0, tmp_words = 0, big_words = 0, mid_words = 0;
-  hipEvent_t last = nullptr;  // end of the previous solve that used the scratch (it may have run on another stream)
+  GrowBuf<word> inv, tmp, big, mid;  // big: inverses of 4096-row blocks; mid: the middle products while building them
+  ScratchTurn turn;                  // the previous solve that used the scratch may have run on another stream
 };
-TrsmScratch g_trsm_scratch[16];
+TrsmScratch g_trsm_scratch[GF2_MAX_DEVICES];
 std::mutex g_trsm_mu;
 
 struct TrsmRun {
@@ -185,6 +185,13 @@ struct TrsmRun {
   const word *inv;  // the inverted diagonal blocks of `be` rows, block k at inv + k * be * (be / 64)
   word *tmp;        // be x words_of(nb) words
   int64_t be = TB;  // rows of an inverted block: TB, or TRSM_BIG when the bigger inverses were built
+};
+
+// What a solve holds from prepare() until it is queued.  The order of the members matters: they end in reverse, the turn first,
+// so that its event is recorded while the lock is still held.
+struct TrsmHold {
+  std::unique_lock<std::mutex> lk;
+  ScratchTurn::Guard turn;
 };
 
 // rows [r0, r0 + mb) of the system, r0 a multiple of TB
@@ -248,24 +255,58 @@ __global__ __launch_bounds__(TB) void trsm_big_scatter_kernel(const word *__rest
 int build_big_inverses(bool upper, const word *T, int64_t ts, int64_t mb, TrsmScratch &s, hipStream_t st) {
   static_assert(BIG % TB == 0 && BIGW == 64, "4096-row blocks, 64 words wide");
   const int64_t ng = (mb + BIG - 1) / BIG, nblk = (mb + TB - 1) / TB;
-  if (upper) hipLaunchKernelGGL((trsm_big_clean_kernel<true>), dim3((unsigned)(ng * BIG)), dim3(64), 0, st, T, ts, mb, s.big);
-  else       hipLaunchKernelGGL((trsm_big_clean_kernel<false>), dim3((unsigned)(ng * BIG)), dim3(64), 0, st, T, ts, mb, s.big);
-  hipLaunchKernelGGL(trsm_big_scatter_kernel, dim3((unsigned)(ng * (BIG / TB))), dim3(TB), 0, st, s.inv, nblk, s.big);
+  if (upper) hipLaunchKernelGGL((trsm_big_clean_kernel<true>), dim3((unsigned)(ng * BIG)), dim3(64), 0, st, T, ts, mb, s.big.p);
+  else       hipLaunchKernelGGL((trsm_big_clean_kernel<false>), dim3((unsigned)(ng * BIG)), dim3(64), 0, st, T, ts, mb, s.big.p);
+  hipLaunchKernelGGL(trsm_big_scatter_kernel, dim3((unsigned)(ng * (BIG / TB))), dim3(TB), 0, st, s.inv.p, nblk, s.big.p);
   HIPTRY(hipGetLastError());
   const int64_t gs = BIG * BIGW;  // words between consecutive blocks
   for (int64_t sb = TB; sb < BIG; sb *= 2) {
     const int64_t sw = sb / 64;
     for (int64_t base = 0; base < BIG; base += 2 * sb) {
-      word *X00 = s.big + base * BIGW + base / 64, *X11 = s.big + (base + sb) * BIGW + (base + sb) / 64;
-      word *off = upper ? s.big + base * BIGW + (base + sb) / 64 : s.big + (base + sb) * BIGW + base / 64;  // U01 | L10
+      word *X00 = s.big.p + base * BIGW + base / 64, *X11 = s.big.p + (base + sb) * BIGW + (base + sb) / 64;
+      word *off = upper ? s.big.p + base * BIGW + (base + sb) / 64 : s.big.p + (base + sb) * BIGW + base / 64;  // U01 | L10
       if (upper) {  // X01 = X00 * U01 * X11
-        HIPTRY(m4ri_amd_m4rm_batch_dev(s.mid, sw, sb * sw, X00, BIGW, gs, off, BIGW, gs, sb, sb, sb, ng, 0, st));
-        HIPTRY(m4ri_amd_m4rm_batch_dev(off, BIGW, gs, s.mid, sw, sb * sw, X11, BIGW, gs, sb, sb, sb, ng, 0, st));
+        HIPTRY(m4ri_amd_m4rm_batch_dev(s.mid.p, sw, sb * sw, X00, BIGW, gs, off, BIGW, gs, sb, sb, sb, ng, 0, st));
+        HIPTRY(m4ri_amd_m4rm_batch_dev(off, BIGW, gs, s.mid.p, sw, sb * sw, X11, BIGW, gs, sb, sb, sb, ng, 0, st));
       } else {      // X10 = X11 * L10 * X00
-        HIPTRY(m4ri_amd_m4rm_batch_dev(s.mid, sw, sb * sw, off, BIGW, gs, X00, BIGW, gs, sb, sb, sb, ng, 0, st));
-        HIPTRY(m4ri_amd_m4rm_batch_dev(off, BIGW, gs, X11, BIGW, gs, s.mid, sw, sb * sw, sb, sb, sb, ng, 0, st));
+        HIPTRY(m4ri_amd_m4rm_batch_dev(s.mid.p, sw, sb * sw, off, BIGW, gs, X00, BIGW, gs, sb, sb, sb, ng, 0, st));
+        HIPTRY(m4ri_amd_m4rm_batch_dev(off, BIGW, gs, X11, BIGW, gs, s.mid.p, sw, sb * sw, sb, sb, sb, ng, 0, st));
       }
     }
+  }
+  return 0;
+}
+
+// What a solve against the n x n triangle T needs before its recursion, for both sides: the lock, the device's scratch with
+// tmp_words words of `tmp` (tmp_big_words when the 4096-row inverses are used) and the turn on it, the diagonal blocks inverted
+// (one launch) and, for a big system, the 4096-row inverses built from them.  Fills R.inv, R.tmp and R.be; the lock and the turn
+// end with H, the caller's.
+// The operands handed to the multiply engine must not carry bits beyond their own columns: the sub-diagonal blocks
+// T[r.., c..c+l) end on a 512-column boundary or on the triangle's last column n -- the caller keeps T's bits beyond
+// column n out of the way (a clean n x n matrix, or a masked copy: see echelon.hip / solve.hip).
+int prepare(TrsmHold &H, TrsmRun &R, int64_t n, size_t tmp_words, size_t tmp_big_words) {
+  H.lk = std::unique_lock<std::mutex>(g_trsm_mu);
+  int dev = 0;
+  HIPTRY(device_slot(&dev));
+  TrsmScratch &s = g_trsm_scratch[dev];
+  const int64_t nblk = (n + TB - 1) / TB;
+  HIPTRY(s.inv.reserve((size_t)nblk * TB * (TB / 64)));
+  HIPTRY(s.tmp.reserve(tmp_words));
+  HIPTRY(H.turn.take(s.turn, R.st));
+  if (R.upper) hipLaunchKernelGGL((trsm_invert_blocks_kernel<true>), dim3((unsigned)nblk), dim3(TB), 0, R.st, R.T, R.ts, n, s.inv.p);
+  else         hipLaunchKernelGGL((trsm_invert_blocks_kernel<false>), dim3((unsigned)nblk), dim3(TB), 0, R.st, R.T, R.ts, n, s.inv.p);
+  HIPTRY(hipGetLastError());
+  R.inv = s.inv.p; R.tmp = s.tmp.p;
+  static const int big_env = getenv("M4RI_AMD_TRSM_BIG") ? atoi(getenv("M4RI_AMD_TRSM_BIG")) : -1;
+  // from 4097 rows on, whatever the number of columns: these solves are bound by their launches (8192 x 512: 1.12 -> 0.75 ms,
+  // 16384 x 16384: 3.4 -> 1.4 ms, 32768^2: 9.4 -> 4.8, 65536^2: 33.3 -> 23.2; M4RI_AMD_TRSM_BIG=0 / 1 forces the choice)
+  if (big_env >= 0 ? (big_env != 0 && n > BIG) : (n > BIG)) {
+    const int64_t ng = (n + BIG - 1) / BIG;
+    HIPTRY(s.big.reserve((size_t)ng * BIG * BIGW));
+    HIPTRY(s.mid.reserve((size_t)ng * (BIG / 2) * (BIGW / 2)));
+    HIPTRY(s.tmp.reserve(tmp_big_words));
+    if (int rc = build_big_inverses(R.upper, R.T, R.ts, n, s, R.st)) return rc;
+    R.inv = s.big.p; R.tmp = s.tmp.p; R.be = BIG;
   }
   return 0;
 }
@@ -280,65 +321,11 @@ int solve(bool upper, const word *T, int64_t ts, word *B, int64_t bs, int64_t mb
     else       hipLaunchKernelGGL((trsm_base_kernel<false>), dim3(g), dim3(TRSM_THREADS), 0, st, T, ts, B, bs, (int)mb, wn, mask);
     return (int)hipGetLastError();
   }
-  // The operands handed to the multiply engine must not carry bits beyond their own columns: the sub-diagonal blocks
-  // T[r.., c..c+l) end on a 512-column boundary or on the triangle's last column mb -- the caller keeps T's bits beyond
-  // column mb out of the way (a clean mb x mb matrix, or a masked copy: see echelon.hip / solve.hip).
-  std::lock_guard<std::mutex> lk(g_trsm_mu);
-  int dev = 0;
-  HIPTRY(hipGetDevice(&dev));
-  if (dev < 0 || dev >= 16) return (int)hipErrorInvalidDevice;
-  TrsmScratch &s = g_trsm_scratch[dev];
-  const int64_t nblk = (mb + TB - 1) / TB, wn = words_of(nb);
-  const size_t need_inv = (size_t)nblk * TB * (TB / 64), need_tmp = (size_t)TB * (size_t)wn;
-  // grow-only scratch; a buffer still in use by an earlier call on another stream must not be freed under it
-  if (need_inv > s.inv_words) {
-    if (s.inv) { HIPTRY(hipDeviceSynchronize()); HIPTRY(hipFree(s.inv)); }
-    s.inv = nullptr; s.inv_words = 0;
-    HIPTRY(hipMalloc(reinterpret_cast<void **>(&s.inv), need_inv * 8));
-    s.inv_words = need_inv;
-  }
-  if (need_tmp > s.tmp_words) {
-    if (s.tmp) { HIPTRY(hipDeviceSynchronize()); HIPTRY(hipFree(s.tmp)); }
-    s.tmp = nullptr; s.tmp_words = 0;
-    HIPTRY(hipMalloc(reinterpret_cast<void **>(&s.tmp), need_tmp * 8));
-    s.tmp_words = need_tmp;
-  }
-  if (!s.last) HIPTRY(hipEventCreateWithFlags(&s.last, hipEventDisableTiming));
-  else HIPTRY(hipStreamWaitEvent(st, s.last, 0));
-  if (upper) hipLaunchKernelGGL((trsm_invert_blocks_kernel<true>), dim3((unsigned)nblk), dim3(TB), 0, st, T, ts, mb, s.inv);
-  else       hipLaunchKernelGGL((trsm_invert_blocks_kernel<false>), dim3((unsigned)nblk), dim3(TB), 0, st, T, ts, mb, s.inv);
-  HIPTRY(hipGetLastError());
-  TrsmRun R{upper, T, ts, B, bs, nb, cutoff, st, s.inv, s.tmp};
-  static const int big_env = getenv("M4RI_AMD_TRSM_BIG") ? atoi(getenv("M4RI_AMD_TRSM_BIG")) : -1;
-  // from 4097 rows on, whatever the number of columns: these solves are bound by their launches (8192 x 512: 1.12 -> 0.75 ms,
-  // 16384 x 16384: 3.4 -> 1.4 ms, 32768^2: 9.4 -> 4.8, 65536^2: 33.3 -> 23.2; M4RI_AMD_TRSM_BIG=0 / 1 forces the choice)
-  if (big_env >= 0 ? (big_env != 0 && mb > BIG) : (mb > BIG)) {
-    const int64_t ng = (mb + BIG - 1) / BIG;
-    const size_t need_big = (size_t)ng * BIG * BIGW, need_mid = (size_t)ng * (BIG / 2) * (BIGW / 2), need_tmp4 = (size_t)BIG * (size_t)wn;
-    if (need_big > s.big_words) {
-      if (s.big) { HIPTRY(hipDeviceSynchronize()); HIPTRY(hipFree(s.big)); }
-      s.big = nullptr; s.big_words = 0;
-      HIPTRY(hipMalloc(reinterpret_cast<void **>(&s.big), need_big * 8));
-      s.big_words = need_big;
-    }
-    if (need_mid > s.mid_words) {
-      if (s.mid) { HIPTRY(hipDeviceSynchronize()); HIPTRY(hipFree(s.mid)); }
-      s.mid = nullptr; s.mid_words = 0;
-      HIPTRY(hipMalloc(reinterpret_cast<void **>(&s.mid), need_mid * 8));
-      s.mid_words = need_mid;
-    }
-    if (need_tmp4 > s.tmp_words) {
-      if (s.tmp) { HIPTRY(hipDeviceSynchronize()); HIPTRY(hipFree(s.tmp)); }
-      s.tmp = nullptr; s.tmp_words = 0;
-      HIPTRY(hipMalloc(reinterpret_cast<void **>(&s.tmp), need_tmp4 * 8));
-      s.tmp_words = need_tmp4;
-    }
-    if (int rc = build_big_inverses(upper, T, ts, mb, s, st)) return rc;
-    R.inv = s.big; R.tmp = s.tmp; R.be = BIG;
-  }
-  const int rc = solve_blocks(R, 0, mb);
-  HIPTRY(hipEventRecord(s.last, st));
-  return rc;
+  const size_t wn = (size_t)words_of(nb);
+  TrsmHold H;
+  TrsmRun R{upper, T, ts, B, bs, nb, cutoff, st};
+  if (int rc = prepare(H, R, mb, (size_t)TB * wn, (size_t)BIG * wn)) return rc;
+  return solve_blocks(R, 0, mb);
 }
 
 // ---- right-hand solves: B <- B * T^-1 (X * T = B) -----------------------------------------------------------------
@@ -400,59 +387,10 @@ int solve_right(bool upper, const word *T, int64_t ts, word *B, int64_t bs, int6
     else       hipLaunchKernelGGL((trsm_right_base_kernel<false>), dim3(g), dim3(256), 0, st, T, ts, B, bs, mb, (int)nb);
     return (int)hipGetLastError();
   }
-  std::lock_guard<std::mutex> lk(g_trsm_mu);
-  int dev = 0;
-  HIPTRY(hipGetDevice(&dev));
-  if (dev < 0 || dev >= 16) return (int)hipErrorInvalidDevice;
-  TrsmScratch &s = g_trsm_scratch[dev];
-  const int64_t nblk = (nb + TB - 1) / TB;
-  const size_t need_inv = (size_t)nblk * TB * (TB / 64), need_tmp = (size_t)mb * (TB / 64);
-  if (need_inv > s.inv_words) {
-    if (s.inv) { HIPTRY(hipDeviceSynchronize()); HIPTRY(hipFree(s.inv)); }
-    s.inv = nullptr; s.inv_words = 0;
-    HIPTRY(hipMalloc(reinterpret_cast<void **>(&s.inv), need_inv * 8));
-    s.inv_words = need_inv;
-  }
-  if (need_tmp > s.tmp_words) {
-    if (s.tmp) { HIPTRY(hipDeviceSynchronize()); HIPTRY(hipFree(s.tmp)); }
-    s.tmp = nullptr; s.tmp_words = 0;
-    HIPTRY(hipMalloc(reinterpret_cast<void **>(&s.tmp), need_tmp * 8));
-    s.tmp_words = need_tmp;
-  }
-  if (!s.last) HIPTRY(hipEventCreateWithFlags(&s.last, hipEventDisableTiming));
-  else HIPTRY(hipStreamWaitEvent(st, s.last, 0));
-  if (upper) hipLaunchKernelGGL((trsm_invert_blocks_kernel<true>), dim3((unsigned)nblk), dim3(TB), 0, st, T, ts, nb, s.inv);
-  else       hipLaunchKernelGGL((trsm_invert_blocks_kernel<false>), dim3((unsigned)nblk), dim3(TB), 0, st, T, ts, nb, s.inv);
-  HIPTRY(hipGetLastError());
-  TrsmRun R{upper, T, ts, B, bs, nb, cutoff, st, s.inv, s.tmp};
-  static const int big_env = getenv("M4RI_AMD_TRSM_BIG") ? atoi(getenv("M4RI_AMD_TRSM_BIG")) : -1;
-  if (big_env >= 0 ? (big_env != 0 && nb > BIG) : (nb > BIG)) {  // the 4096-row block inverses, as in solve()
-    const int64_t ng = (nb + BIG - 1) / BIG;
-    const size_t need_big = (size_t)ng * BIG * BIGW, need_mid = (size_t)ng * (BIG / 2) * (BIGW / 2), need_tmp4 = (size_t)mb * BIGW;
-    if (need_big > s.big_words) {
-      if (s.big) { HIPTRY(hipDeviceSynchronize()); HIPTRY(hipFree(s.big)); }
-      s.big = nullptr; s.big_words = 0;
-      HIPTRY(hipMalloc(reinterpret_cast<void **>(&s.big), need_big * 8));
-      s.big_words = need_big;
-    }
-    if (need_mid > s.mid_words) {
-      if (s.mid) { HIPTRY(hipDeviceSynchronize()); HIPTRY(hipFree(s.mid)); }
-      s.mid = nullptr; s.mid_words = 0;
-      HIPTRY(hipMalloc(reinterpret_cast<void **>(&s.mid), need_mid * 8));
-      s.mid_words = need_mid;
-    }
-    if (need_tmp4 > s.tmp_words) {
-      if (s.tmp) { HIPTRY(hipDeviceSynchronize()); HIPTRY(hipFree(s.tmp)); }
-      s.tmp = nullptr; s.tmp_words = 0;
-      HIPTRY(hipMalloc(reinterpret_cast<void **>(&s.tmp), need_tmp4 * 8));
-      s.tmp_words = need_tmp4;
-    }
-    if (int rc = build_big_inverses(upper, T, ts, nb, s, st)) return rc;
-    R.inv = s.big; R.tmp = s.tmp; R.be = BIG;
-  }
-  const int rc = solve_right_blocks(R, mb, 0, nb);
-  HIPTRY(hipEventRecord(s.last, st));
-  return rc;
+  TrsmHold H;
+  TrsmRun R{upper, T, ts, B, bs, nb, cutoff, st};
+  if (int rc = prepare(H, R, nb, (size_t)mb * (TB / 64), (size_t)mb * BIGW)) return rc;  // tmp: a block's columns of every row
+  return solve_right_blocks(R, mb, 0, nb);
 }
 
 }  // namespace
@@ -543,18 +481,17 @@ __global__ __launch_bounds__(256) void trtri_merge_kernel(word *__restrict__ U, 
   *p = (*p & ~m) | (W[i * ws + w] & m);
 }
 
-struct TrtriScratch { word *buf = nullptr; size_t words = 0; };
+struct TrtriScratch { GrowBuf<word> buf; ScratchTurn turn; };
 #ifndef TRTRI_BATCH_MAX
 #define TRTRI_BATCH_MAX 4096  // levels up to this block size run as batched launches
 #endif
-TrtriScratch g_trtri_scratch[16];
+TrtriScratch g_trtri_scratch[GF2_MAX_DEVICES];
 
 int trtri_upper(word *U, int64_t us, int64_t n, hipStream_t st) {
   if (n <= 1) return 0;
   std::lock_guard<std::mutex> lk(g_trsm_mu);
   int dev = 0;
-  HIPTRY(hipGetDevice(&dev));
-  if (dev < 0 || dev >= 16) return (int)hipErrorInvalidDevice;
+  HIPTRY(device_slot(&dev));
   const int64_t wn = words_of(n), ws = (wn + 1) & ~(int64_t)1, nblk = (n + TB - 1) / TB;
   int64_t smax = TB;
   while (smax * 2 < n) smax *= 2;  // the largest level: pairs of smax-blocks
@@ -562,13 +499,10 @@ int trtri_upper(word *U, int64_t us, int64_t n, hipStream_t st) {
   const size_t w_words = (size_t)n * (size_t)ws, t_words = (n > TB) ? (size_t)smax * (size_t)wt : 0,
                inv_words = (size_t)nblk * TB * (TB / 64);
   TrtriScratch &s = g_trtri_scratch[dev];
-  if (w_words + t_words + inv_words > s.words) {
-    if (s.buf) { HIPTRY(hipDeviceSynchronize()); HIPTRY(hipFree(s.buf)); }
-    s.buf = nullptr; s.words = 0;
-    HIPTRY(hipMalloc(reinterpret_cast<void **>(&s.buf), (w_words + t_words + inv_words) * 8));
-    s.words = w_words + t_words + inv_words;
-  }
-  word *W = s.buf, *T = W + w_words, *inv = T + t_words;
+  HIPTRY(s.buf.reserve(w_words + t_words + inv_words));
+  ScratchTurn::Guard turn;  // an earlier inverse, on whatever stream, works in the same W, T and inv
+  HIPTRY(turn.take(s.turn, st));
+  word *W = s.buf.p, *T = W + w_words, *inv = T + t_words;
   const unsigned g = (unsigned)((n * wn + 255) / 256);
   hipLaunchKernelGGL(trtri_clean_kernel, dim3(g), dim3(256), 0, st, W, ws, U, us, n, wn);
   hipLaunchKernelGGL((trsm_invert_blocks_kernel<true>), dim3((unsigned)nblk), dim3(TB), 0, st, W, ws, n, inv);
@@ -600,7 +534,8 @@ int trtri_upper(word *U, int64_t us, int64_t n, hipStream_t st) {
 }  // namespace
 
 // U (n x n bits) <- U^-1 for a unit upper triangular U: only the bits strictly above the diagonal are read and written.
-// Device pointer; asynchronous on `stream` (the scratch is grow-only per device, calls are serialised by a mutex).
+// Device pointer; asynchronous on `stream`.  The scratch is grow-only per device and shared by all streams: a mutex serialises the
+// enqueueing, and a call's work starts after the work of the previous call on that device, whatever stream that one ran on.
 extern "C" int m4ri_amd_trtri_upper_dev(word *U, int64_t stride, int64_t n, void *stream) {
   if (n < 0) return (int)hipErrorInvalidValue;
   return trtri_upper(U, stride, n, (hipStream_t)stream);

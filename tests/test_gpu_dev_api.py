@@ -7,8 +7,8 @@ between its width and its stride, and three layouts -- `even` (what the host shi
 oracle's, every word outside the operand's rows and words [0, width) must be unchanged, and the bits beyond the last column
 must be what the function's header comment says.  The shapes are the smallest that reach each path: the 64-row and 64-column
 TRSM base kernels over two and three workgroups, the 512-row block inverses with a ragged last block, a non-zero `cutoff`,
-two solves and a trtri in flight on three streams, the column gather on rows wider than 64 KiB, and each of the three update
-kernels of m4ri_amd_process_rows_dev."""
+two solves and a trtri in flight on three streams, two right-hand solves and two trtri on two, the column gather on rows wider
+than 64 KiB, and each of the three update kernels of m4ri_amd_process_rows_dev."""
 import ctypes
 
 import numpy as np
@@ -173,6 +173,50 @@ def test_solves_in_flight_on_two_streams_and_a_trtri_on_a_third(oracle):
             fB.check(want, "zero", f"B {fB.nrows} x {fB.ncols}")
             fT.check_unchanged("T")
         fU.check(want_u if with_trtri else None, "kept", "U")
+
+
+def test_two_trtri_in_flight_on_two_streams(oracle):
+    """Two inverses of different sizes, both above 512 rows (the product levels), share the trtri's per-device scratch, which is
+    sized for the larger one: issued on two streams with no host synchronisation between them, after a round in which the scratch
+    grew, both give the oracle's bits -- each call takes its turn on the scratch."""
+    Us = [Mzd.random(n, n, 1000 + n) for n in (1300, 700)]
+    wants = [oracle.trtri_upper(U.copy()) for U in Us]
+    streams = [torch.cuda.Stream() for _ in Us]
+
+    def issue():
+        frames = [Frame(U, "odd", 6 + i, dirty_tail=True).upload() for i, U in enumerate(Us)]
+        torch.cuda.synchronize()  # the uploads ran on the null stream; torch's own streams do not wait for it
+        for f, U, st in zip(frames, Us, streams):
+            _call("m4ri_amd_trtri_upper_dev", f.ptr, f.stride, U.nrows, st.cuda_stream)
+        torch.cuda.synchronize()
+        return frames
+
+    issue()  # first round: the scratch grows here (growing synchronises the device)
+    for f, want in zip(issue(), wants):
+        f.check(want, "kept", f"U {f.nrows} x {f.ncols}")
+
+
+def test_right_solves_in_flight_on_two_streams(oracle):
+    """The right-hand solves share the same scratch and the same event as the left-hand ones: an upper and a lower solve with
+    different triangles above 512 columns, on two streams, as above."""
+    cases = [(300, 1100, True), (129, 600, False)]
+    ops = [(df.unit_diag(Mzd.random(nb, nb, 1100 + nb)), Mzd.random(mb, nb, 1200 + mb), up) for mb, nb, up in cases]
+    wants = [(oracle.trsm_upper_right if up else oracle.trsm_lower_right)(T, B.copy()) for T, B, up in ops]
+    streams = [torch.cuda.Stream() for _ in ops]
+
+    def issue():
+        frames = [(Frame(T, "odd", 3).upload(), Frame(B, "odd", 4).upload()) for T, B, _ in ops]
+        torch.cuda.synchronize()
+        for (fT, fB), (T, B, up), st in zip(frames, ops, streams):
+            _call("m4ri_amd_trsm_upper_right_dev" if up else "m4ri_amd_trsm_lower_right_dev", fT.ptr, fT.stride, fB.ptr, fB.stride, B.nrows,
+                  B.ncols, 0, st.cuda_stream)
+        torch.cuda.synchronize()
+        return frames
+
+    issue()  # first round: the scratch grows here
+    for (fT, fB), want in zip(issue(), wants):
+        fB.check(want, "zero", f"B {fB.nrows} x {fB.ncols}")
+        fT.check_unchanged("T")
 
 
 # ---- permutations -----------------------------------------------------------------------------------------------------------
