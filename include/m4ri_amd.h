@@ -694,6 +694,40 @@ int m4ri_amd_plan_row_blocks(int64_t m, int64_t l, int64_t n, int64_t *rows, int
    how many inner-dimension splits?  0: no (generation 4 / 1); k >= 1: yes, k splits (k > 1: the splits meet by atomic XOR).  `cus`: the
    compute units the launch is planned for (0 = 256, an MI355X).  Pure host arithmetic, callable without a GPU. */
 int m4ri_amd_plan_small_leaf(int64_t m, int64_t l, int64_t n, int64_t batch, int cus);
+
+/* What ONE leaf launch of the engine does for `batch` products of m x l x n -- the launch every direct product and every Strassen leaf
+   level ends in (engine.hip launch_leaf_one runs exactly this plan and decides nothing itself):
+     gen          5 the one-launch small leaf (256 x 8 word tiles), 4 packed A (4096 x 8), 1 plain A (32 rg x 32); 0: no kernel runs
+                  (an empty product, or l == 0: C is cleared or kept)
+     rg           generation 1: tile rows / 32 (32, 24 or 16); else 0
+     tile_rows, tile_words, tiles_m, tiles_n, tiles   the tile grid of one member and the tiles of the whole launch
+     ksplit       inner-dimension splits handed to the kernel of the whole launch (hybrid plan: of its head, 1).  Generation 4: the
+                  count the kernel really makes (whole stage pairs per split); generations 1 and 5 round the count in their launchers
+     tail_tiles, tail_ksplit   hybrid plan (generation 4): the last tail_tiles tiles -- those of the short last round -- go in a second
+                  launch with this split; 0 and 1 otherwise
+     mode, tail_mode   how the launch (the tail launch) writes C: 0 store, 1 atomic XOR into C, 2 slabs + one reduce pass (tail_mode is 0
+                  without a tail)
+     slabs        1: the splits meet in slabs of the workspace and one reduce pass writes (add: XORs into) C; 0: by atomic XOR, or unsplit
+     zero         what is cleared first: 0 nothing, 1 all of C (every member's m rows of words(n) words), 2 the tail's tiles
+     pack_a       1: a separate pass packs A for generation 4 first (0 when a fused pass has: a_prepacked)
+   ksplit_req: what the caller asks for (m4ri_amd_m4rm_dev's ksplit; 0 = automatic, every other entry).  cus: the compute units planned
+   for (0 or less: 256, an MI355X).  a_prepacked: the fused down pass has written A in packed form (Strassen leaves).  scratch_ok: the
+   engine's packed-A scratch and slab region hold this launch -- every entry reserves them first, except m4ri_amd_m4rm_batch_dev, which
+   takes what the previous call left and falls back to generation 1 when that is too small.  The developer switches M4RI_AMD_LEAF_GEN,
+   M4RI_AMD_SMALL_LEAF, M4RI_AMD_SMALL_LEAF_WORK, M4RI_AMD_SMALL_KS and M4RI_AMD_TAIL_KSPLIT are read as the engine reads them, so the
+   answer is what THIS process would do.  Pure host arithmetic, callable without a GPU.  Returns 0, or hipErrorInvalidValue (1) for
+   out == NULL, a negative size, a dimension beyond INT32_MAX, or a_prepacked on a launch generation 4 cannot take. */
+typedef struct m4ri_amd_leaf_plan {
+  int32_t gen, rg;
+  int32_t tile_rows, tile_words;
+  int64_t tiles_m, tiles_n, tiles;
+  int32_t ksplit, tail_ksplit;
+  int64_t tail_tiles;
+  int32_t mode, tail_mode;
+  int32_t slabs, zero, pack_a, reserved;
+} m4ri_amd_leaf_plan;
+int m4ri_amd_plan_leaf_launch(int64_t m, int64_t l, int64_t n, int64_t batch, int add, int ksplit_req, int cus, int a_prepacked, int scratch_ok,
+                              m4ri_amd_leaf_plan *out);
 /* What the engine's time model gives ONE m x l x n product at `levels` Strassen-Winograd levels, in seconds on the box the
    constants were measured on (the plans above are minima of sums of it; tools/depth_model_sweep.py prints it beside measurements). */
 double m4ri_amd_model_seconds(int64_t m, int64_t l, int64_t n, int levels);

@@ -65,6 +65,22 @@ class Stats(ctypes.Structure):
     ]
 
 
+class LeafPlan(ctypes.Structure):
+    """m4ri_amd_leaf_plan (include/m4ri_amd.h): what one leaf launch of the engine does."""
+
+    _fields_ = [("gen", ctypes.c_int32), ("rg", ctypes.c_int32), ("tile_rows", ctypes.c_int32), ("tile_words", ctypes.c_int32),
+                ("tiles_m", ctypes.c_int64), ("tiles_n", ctypes.c_int64), ("tiles", ctypes.c_int64),
+                ("ksplit", ctypes.c_int32), ("tail_ksplit", ctypes.c_int32), ("tail_tiles", ctypes.c_int64),
+                ("mode", ctypes.c_int32), ("tail_mode", ctypes.c_int32),
+                ("slabs", ctypes.c_int32), ("zero", ctypes.c_int32), ("pack_a", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+    def __repr__(self):
+        return "LeafPlan(" + ", ".join(f"{n}={getattr(self, n)}" for n, _ in self._fields_ if n != "reserved") + ")"
+
+
+(ZERO_NOTHING, ZERO_ALL, ZERO_TAIL) = range(3)  # LeafPlan.zero
+
+
 class DmatInfo(ctypes.Structure):
     """m4ri_amd_dmat_info_t."""
 
@@ -214,6 +230,7 @@ SYMBOLS = {
     "m4ri_amd_set_max_fuse": (_I, [_I]),
     "m4ri_amd_plan_levels": (_I, [_I64, _I64, _I64, _I]),
     "m4ri_amd_plan_small_leaf": (_I, [_I64, _I64, _I64, _I64, _I]),
+    "m4ri_amd_plan_leaf_launch": (_I, [_I64, _I64, _I64, _I64, _I, _I, _I, _I, _I, ctypes.POINTER(LeafPlan)]),
     "m4ri_amd_plan_row_blocks": (_I, [_I64, _I64, _I64, ctypes.c_void_p, ctypes.c_void_p, _I]),
     "m4ri_amd_model_seconds": (ctypes.c_double, [_I64, _I64, _I64, _I]),
     "m4ri_amd_set_workspace_budget": (_I64, [_I64]),
@@ -958,6 +975,16 @@ def plan_row_blocks(m: int, l: int, n: int):
     levels = (ctypes.c_int * 16)()
     k = int(lib().m4ri_amd_plan_row_blocks(m, l, n, ctypes.cast(rows, ctypes.c_void_p), ctypes.cast(levels, ctypes.c_void_p), 16))
     return [(int(rows[i]), int(levels[i])) for i in range(min(k, 16))]
+
+
+def plan_leaf_launch(m: int, l: int, n: int, batch: int = 1, add: bool = False, ksplit: int = 0, cus: int = 0, a_prepacked: bool = False,
+                     scratch_ok: bool = True) -> LeafPlan:
+    """What one leaf launch of `batch` products of m x l x n does in this process (m4ri_amd_plan_leaf_launch; host arithmetic only).
+    scratch_ok: the engine's packed-A scratch and slab region hold the launch (every entry but m4rm_batch_dev reserves them)."""
+    p = LeafPlan()
+    _check(lib().m4ri_amd_plan_leaf_launch(m, l, n, batch, int(bool(add)), ksplit, cus, int(bool(a_prepacked)), int(bool(scratch_ok)), ctypes.byref(p)),
+           "m4ri_amd_plan_leaf_launch")
+    return p
 
 
 def model_seconds(m: int, l: int, n: int, levels: int) -> float:

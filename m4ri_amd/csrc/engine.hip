@@ -191,11 +191,20 @@ size_t packed_a_words(int64_t m, int64_t l, int64_t batch) {
   return (size_t)gf2_m4rm8_a4_words(m, l, batch);
 }
 
+// do the packed-A scratch and the slab region the engine holds take a leaf launch of this shape?  (reserve_apk makes them so; an entry
+// that does not reserve finds what the previous call left)
+bool scratch_holds(const Engine *e, int64_t m, int64_t l, int64_t batch) {
+  return batch > 0 && e->apk != nullptr && e->part != nullptr && (size_t)gf2_m4rm8_a4_words(m, l, batch) <= e->apk_words;
+}
+
+// 32-bit offsets inside one packed operand: can the packed-A kernels address a member of this shape?
+bool packed_a_addressable(int64_t m, int64_t l, int64_t batch) {
+  return batch > 0 && (uint64_t)gf2_m4rm8_a4_words(m, l, batch) * 8 / (uint64_t)batch < (1ull << 32);
+}
+
 // can a leaf launch of this shape use the packed-A kernel `kind` with the scratch the engine holds?
 bool packed_a_fits(const Engine *e, const LeafKind &kind, int64_t m, int64_t l, int64_t batch) {
-  if (kind.gen < 4 || batch <= 0) return false;
-  const size_t need = (size_t)gf2_m4rm8_a4_words(m, l, batch);
-  return e->apk != nullptr && need <= e->apk_words && (uint64_t)need * 8 / (uint64_t)batch < (1ull << 32);
+  return kind.gen >= 4 && scratch_holds(e, m, l, batch) && packed_a_addressable(m, l, batch);
 }
 
 // C = 0 over the batch: one memset when the batch is one contiguous block, else a clearing pass per member
@@ -229,32 +238,35 @@ int timed_leaf(Engine *e, hipStream_t st, int gen, int64_t m, int64_t l, int64_t
   return 0;
 }
 
-// a_prepacked: the engine's packed-A scratch already holds A in the form the picked kernel reads
-// (written by the fused down pass); A itself is then not touched.
-int launch_leaf_one(Engine *e, hipStream_t st, word *C, int64_t cs, int64_t cbs, const word *A, int64_t as, int64_t abs_,
-                    const word *B, int64_t bs, int64_t bbs, int64_t m, int64_t l, int64_t n, int64_t batch,
-                    bool add, int ksplit_req, bool a_prepacked) {
+// ---- the plan of one leaf launch --------------------------------------------------------------------------------------------------
+// Everything launch_leaf_one decides, as pure host arithmetic (m4ri_amd_plan_leaf_launch exports it; tests/test_leaf_plan_cpu.py pins
+// it): the kernel generation and its tiles, the inner-dimension splits of the launch or of its short last round alone, how the
+// splits meet, what is cleared first, whether A is packed by a pass of its own.  launch_leaf_one executes the result and nothing else.
+// scratch_ok: scratch_holds() of the engine that will run it.
+int plan_leaf_launch(int64_t m, int64_t l, int64_t n, int64_t batch, bool add, int ksplit_req, int cus, bool a_prepacked, bool scratch_ok,
+                     m4ri_amd_leaf_plan *p) {
+  *p = m4ri_amd_leaf_plan{};
+  p->ksplit = p->tail_ksplit = 1;
+  if (m < 0 || l < 0 || n < 0 || batch < 0) return (int)hipErrorInvalidValue;
   if (m == 0 || n == 0 || batch == 0) return 0;
   if (m > INT32_MAX || l > INT32_MAX || n > INT32_MAX) return (int)hipErrorInvalidValue;
-  // 32-bit byte offsets inside one operand (raw buffer addressing)
-  if ((uint64_t)m * (uint64_t)as * 8 >= (1ull << 32) || (uint64_t)l * (uint64_t)bs * 8 >= (1ull << 32))
-    return (int)hipErrorInvalidValue;
-  const int64_t wn   = words_of(n);
-  LeafArgs a{};
-  a.A = A; a.B = B; a.C = C;
-  a.a_stride = as; a.b_stride = bs; a.c_stride = cs;
-  a.a_bs = abs_; a.b_bs = bbs; a.c_bs = cbs;
-  a.m = (int32_t)m; a.l = (int32_t)l; a.n = (int32_t)n;
-  a.batch = (int32_t)batch;
-  if (!a_prepacked && ksplit_req <= 0 && l > 0 && small_leaf_wanted(m, l, n, batch)) {
+  if (cus <= 0) cus = 256;
+  const int64_t wn = words_of(n);
+  if (l == 0) {  // empty inner dimension: C = 0, or C kept
+    p->zero = add ? 0 : 1;
+    return 0;
+  }
+  if (!a_prepacked && ksplit_req <= 0 && small_leaf_wanted(m, l, n, batch)) {
     // a small product: ONE launch of the light kernel (m4rm_small.hip) instead of pack + split leaf + reduce
-    const int64_t tiles = ((m + 255) / 256) * ((wn + 7) / 8) * batch;
+    p->gen = 5; p->tile_rows = 256; p->tile_words = 8;
+    p->tiles_m = (m + 255) / 256; p->tiles_n = (wn + 7) / 8;
+    p->tiles   = p->tiles_m * p->tiles_n * batch;
     static const int ks_env = getenv("M4RI_AMD_SMALL_KS") ? atoi(getenv("M4RI_AMD_SMALL_KS")) : 0;  // developer: force the inner split of the small leaf
-    const int ks        = ks_env > 0 ? (ks_env < words_of(l) ? ks_env : (int)words_of(l)) : gf2_m4rm_small_ksplit(tiles, words_of(l), e->cus, batch * m * wn);
-    if (ks > 1 && !add) HIPTRY(zero_c(st, C, cs, cbs, m, wn, batch));  // the splits meet by atomic XOR: they start from zero
-    a.ksplit = ks;
-    a.mode   = (add || ks > 1) ? 1 : 0;
-    return timed_leaf(e, st, 5, m, l, n, batch, add, [&]() -> int { HIPTRY(gf2_launch_m4rm_small(st, a)); return 0; });
+    const int ks = ks_env > 0 ? (ks_env < words_of(l) ? ks_env : (int)words_of(l)) : gf2_m4rm_small_ksplit(p->tiles, words_of(l), cus, batch * m * wn);
+    p->ksplit = ks;
+    p->zero   = (ks > 1 && !add) ? 1 : 0;  // the splits meet by atomic XOR: they start from zero
+    p->mode   = (add || ks > 1) ? 1 : 0;
+    return 0;
   }
   LeafKind kind      = pick_leaf(m, l, n);
   const int64_t tw   = kind.gen == 4 ? 8 : LEAF_TW;  // tile width in words
@@ -283,7 +295,7 @@ int launch_leaf_one(Engine *e, hipStream_t st, word *C, int64_t cs, int64_t cbs,
       return kind.gen == 4 ? ((double)LEAF_SPLIT_COST_BITS + 2.0 * (double)(ntiles * ks)) / (double)sbits : 512.0 / (double)sbits;
     };
     auto cost = [&](int64_t ks) {
-      const int64_t rounds = (tiles * ks + e->cus - 1) / e->cus;
+      const int64_t rounds = (tiles * ks + cus - 1) / cus;
       return (double)rounds * ((double)((stages + ks - 1) / ks) + fixed + (ks > 1 ? split_cost(tiles, ks) : 0.0));
     };
     int64_t cap = stages * sbits / (kind.gen == 4 ? LEAF_MIN_SPLIT_BITS_G4 : LEAF_MIN_SPLIT_BITS);  // inner bits per split: see the constants
@@ -295,10 +307,10 @@ int launch_leaf_one(Engine *e, hipStream_t st, word *C, int64_t cs, int64_t cbs,
       if (cost(ks) < best_cost) { best_cost = cost(ks); ksplit = (int)ks; }
     // Generation 4 can also run the FULL rounds unsplit and only the tiles of the short last round
     // split (two launches over disjoint tile ranges): the remainder pays for atomics, nobody else
-    if (kind.gen == 4 && tiles > e->cus && tiles % e->cus != 0) {
-      const int64_t rem = tiles % e->cus, full_rounds = tiles / e->cus;
+    if (kind.gen == 4 && tiles > cus && tiles % cus != 0) {
+      const int64_t rem = tiles % cus, full_rounds = tiles / cus;
       for (int64_t ks = 2; ks <= cap; ++ks) {
-        const int64_t rounds = (rem * ks + e->cus - 1) / e->cus;
+        const int64_t rounds = (rem * ks + cus - 1) / cus;
         // (the tail's slabs and their reduce pass once per launch, at half the price per slab of a launch that is split as a whole: with
         // the calibration above 16384^3 -- 392 tiles, 1.53 rounds -- stayed unsplit at 0.673 ms where three splits of its 136-tile tail
         // give 0.632; profiles/r04_leaf_split_model_ab.log holds the table of 48 shapes before and after: nothing else moves)
@@ -315,49 +327,85 @@ int launch_leaf_one(Engine *e, hipStream_t st, word *C, int64_t cs, int64_t cbs,
     ksplit      = gf2_m4rm8q_effective_ksplit(l, ksplit);
     tail_ksplit = gf2_m4rm8q_effective_ksplit(l, tail_ksplit);
   }
+  // generation 4 consumes A in a packed, chunk-major form (one streaming pass into the call's scratch first); it needs that
+  // scratch and 32-bit offsets inside one packed operand
+  const bool packed_fits = kind.gen == 4 && scratch_ok && packed_a_addressable(m, l, batch);
   // generation 4 combines the splits through per-split slabs + one reduce pass when they fit the
   // workspace's slab region (no atomics, no zeroing); otherwise, and in the older kernels, by atomic
   // XOR into a zeroed C
-  const bool slabs = kind.gen == 4 && e->part != nullptr && packed_a_fits(e, kind, m, l, batch) &&
-                     (tail_tiles > 0 ? tail_tiles * tail_ksplit : (ksplit > 1 ? tiles * ksplit : PART_SLABS + 1)) <= PART_SLABS;
-  if (l == 0 || (ksplit > 1 && !add && !slabs)) {  // empty inner dimension, or atomics need a zeroed C
-    if (!add) HIPTRY(zero_c(st, C, cs, cbs, m, wn, batch));
-    if (l == 0) return 0;
-  }
-  a.ksplit = ksplit;
-  a.mode   = (ksplit > 1 && slabs) ? 2 : (add || ksplit > 1) ? 1 : 0;
-  a.Cpart = e->part;
-  // generation 4 consumes A in a packed, chunk-major form (one streaming pass into the call's
-  // scratch first); it needs that scratch and 32-bit offsets inside one packed operand
+  const bool slabs = packed_fits && (tail_tiles > 0 ? tail_tiles * tail_ksplit : (ksplit > 1 ? tiles * ksplit : PART_SLABS + 1)) <= PART_SLABS;
+  if (ksplit > 1 && !add && !slabs) p->zero = 1;  // atomics need a zeroed C
+  p->mode = (ksplit > 1 && slabs) ? 2 : (add || ksplit > 1) ? 1 : 0;
   if (a_prepacked) {
-    if (kind.gen < 4 || !packed_a_fits(e, kind, m, l, batch)) return (int)hipErrorInvalidValue;  // caller checked
+    if (!packed_fits) return (int)hipErrorInvalidValue;  // caller checked
   } else if (kind.gen == 4) {
-    if (!packed_a_fits(e, kind, m, l, batch)) kind = LEAF_KINDS[LEAF_KIND_FALLBACK];
-    else {
-      const size_t need = (size_t)gf2_m4rm8_a4_words(m, l, batch);
-      HIPTRY(gf2_launch_a4_pack_rot(st, a, e->apk, 1));  // the index bytes pre-rotated for the leaf's constant selectors
-      e->stats.aux_bytes += 8.0 * (double)batch * (double)m * words_of(l) + 8.0 * (double)need;
+    if (packed_fits) p->pack_a = 1;
+    else {  // no scratch for the packed A: the whole launch, with the split and mode found above, goes to generation 1's 1024-row tiles
+      kind = LEAF_KINDS[LEAF_KIND_FALLBACK];
+      tail_tiles = 0; tail_ksplit = 1;
     }
   }
-  return timed_leaf(e, st, kind.gen, m, l, n, batch, add, [&]() -> int {
-    if (kind.gen == 4 && tail_tiles > 0) {
+  if (kind.gen == 4 && tail_tiles > 0) {
+    p->tail_mode = slabs ? 2 : 1;
+    if (!add && !slabs) p->zero = 2;  // the split tiles are combined by atomic XOR: they start from zero
+  }
+  const int64_t ktw = kind.gen == 4 ? 8 : LEAF_TW;
+  p->gen = kind.gen; p->rg = kind.gen == 1 ? kind.rg : 0;
+  p->tile_rows = kind.rows; p->tile_words = (int32_t)ktw;
+  p->tiles_m = (m + kind.rows - 1) / kind.rows; p->tiles_n = (wn + ktw - 1) / ktw;
+  p->tiles   = p->tiles_m * p->tiles_n * batch;
+  p->ksplit = ksplit; p->tail_tiles = tail_tiles; p->tail_ksplit = tail_ksplit;
+  p->slabs = slabs ? 1 : 0;
+  return 0;
+}
+
+// a_prepacked: the engine's packed-A scratch already holds A in the form the picked kernel reads
+// (written by the fused down pass); A itself is then not touched.
+int launch_leaf_one(Engine *e, hipStream_t st, word *C, int64_t cs, int64_t cbs, const word *A, int64_t as, int64_t abs_,
+                    const word *B, int64_t bs, int64_t bbs, int64_t m, int64_t l, int64_t n, int64_t batch,
+                    bool add, int ksplit_req, bool a_prepacked) {
+  if (m == 0 || n == 0 || batch == 0) return 0;
+  m4ri_amd_leaf_plan p;
+  if (int rc = plan_leaf_launch(m, l, n, batch, add, ksplit_req, e->cus, a_prepacked, scratch_holds(e, m, l, batch), &p)) return rc;
+  // 32-bit byte offsets inside one operand (raw buffer addressing)
+  if ((uint64_t)m * (uint64_t)as * 8 >= (1ull << 32) || (uint64_t)l * (uint64_t)bs * 8 >= (1ull << 32))
+    return (int)hipErrorInvalidValue;
+  const int64_t wn   = words_of(n);
+  LeafArgs a{};
+  a.A = A; a.B = B; a.C = C;
+  a.a_stride = as; a.b_stride = bs; a.c_stride = cs;
+  a.a_bs = abs_; a.b_bs = bbs; a.c_bs = cbs;
+  a.m = (int32_t)m; a.l = (int32_t)l; a.n = (int32_t)n;
+  a.batch = (int32_t)batch;
+  if (p.zero == 1) HIPTRY(zero_c(st, C, cs, cbs, m, wn, batch));
+  if (p.gen == 0) return 0;
+  a.ksplit = p.ksplit;
+  a.mode   = p.mode;
+  if (p.gen == 5) return timed_leaf(e, st, 5, m, l, n, batch, add, [&]() -> int { HIPTRY(gf2_launch_m4rm_small(st, a)); return 0; });
+  a.Cpart = e->part;
+  if (p.pack_a) {
+    HIPTRY(gf2_launch_a4_pack_rot(st, a, e->apk, 1));  // the index bytes pre-rotated for the leaf's constant selectors
+    e->stats.aux_bytes += 8.0 * (double)batch * (double)m * words_of(l) + 8.0 * (double)gf2_m4rm8_a4_words(m, l, batch);
+  }
+  return timed_leaf(e, st, p.gen, m, l, n, batch, add, [&]() -> int {
+    if (p.gen == 4 && p.tail_tiles > 0) {
       LeafArgs head = a, tail = a;
-      head.tile_base = 0; head.tile_count = tiles - tail_tiles;
-      tail.tile_base = tiles - tail_tiles; tail.tile_count = tail_tiles;
-      tail.ksplit = tail_ksplit; tail.mode = slabs ? 2 : 1;
-      const int64_t tm = (m + kind.rows - 1) / kind.rows, tn = (wn + tw - 1) / tw;
-      if (!add && !slabs)  // the split tiles are combined by atomic XOR: they start from zero
-        HIPTRY(gf2_launch_zero_tiles(st, C, cs, cbs, m, wn, kind.rows, tw, tm, tn, tail.tile_base, tail_tiles));
+      head.tile_base = 0; head.tile_count = p.tiles - p.tail_tiles;
+      tail.tile_base = p.tiles - p.tail_tiles; tail.tile_count = p.tail_tiles;
+      tail.ksplit = p.tail_ksplit; tail.mode = p.tail_mode;
+      if (p.zero == 2)
+        HIPTRY(gf2_launch_zero_tiles(st, C, cs, cbs, m, wn, p.tile_rows, p.tile_words, p.tiles_m, p.tiles_n, tail.tile_base, p.tail_tiles));
       HIPTRY(gf2_launch_m4rm8q(st, head, e->apk));
       HIPTRY(gf2_launch_m4rm8q(st, tail, e->apk));
-      if (slabs) HIPTRY(gf2_launch_reduce_partials(st, add ? 1 : 0, C, cs, cbs, m, wn, kind.rows, tw, tm, tn, tail.tile_base, tail_tiles, tail_ksplit, e->part));
-    } else if (kind.gen == 4) {
+      if (p.slabs)
+        HIPTRY(gf2_launch_reduce_partials(st, add ? 1 : 0, C, cs, cbs, m, wn, p.tile_rows, p.tile_words, p.tiles_m, p.tiles_n, tail.tile_base, p.tail_tiles,
+                                          p.tail_ksplit, e->part));
+    } else if (p.gen == 4) {
       HIPTRY(gf2_launch_m4rm8q(st, a, e->apk));
-      if (a.mode == 2)
-        HIPTRY(gf2_launch_reduce_partials(st, add ? 1 : 0, C, cs, cbs, m, wn, kind.rows, tw, (m + kind.rows - 1) / kind.rows, (wn + tw - 1) / tw,
-                                          0, tiles, ksplit, e->part));
+      if (p.mode == 2)
+        HIPTRY(gf2_launch_reduce_partials(st, add ? 1 : 0, C, cs, cbs, m, wn, p.tile_rows, p.tile_words, p.tiles_m, p.tiles_n, 0, p.tiles, p.ksplit, e->part));
     }
-    else HIPTRY(gf2_launch_m4rm_leaf(st, a, kind.rg));
+    else HIPTRY(gf2_launch_m4rm_leaf(st, a, p.rg));
     return 0;
   });
 }
@@ -1021,6 +1069,12 @@ int m4ri_amd_plan_small_leaf(int64_t m, int64_t l, int64_t n, int64_t batch, int
   if (m <= 0 || l <= 0 || n <= 0 || batch <= 0 || !small_leaf_wanted(m, l, n, batch)) return 0;
   const int64_t wn = words_of(n), tiles = ((m + 255) / 256) * ((wn + 7) / 8) * batch;
   return gf2_m4rm_small_ksplit(tiles, words_of(l), cus > 0 ? cus : 256, batch * m * wn);
+}
+
+int m4ri_amd_plan_leaf_launch(int64_t m, int64_t l, int64_t n, int64_t batch, int add, int ksplit_req, int cus, int a_prepacked, int scratch_ok,
+                              m4ri_amd_leaf_plan *out) {  // pure host logic: no device needed
+  if (!out) return (int)hipErrorInvalidValue;
+  return plan_leaf_launch(m, l, n, batch, add != 0, ksplit_req, cus, a_prepacked != 0, scratch_ok != 0, out);
 }
 
 int m4ri_amd_plan_row_blocks(int64_t m, int64_t l, int64_t n, int64_t *rows, int *levels, int cap) {

@@ -618,6 +618,10 @@ def test_leaf_full_rounds_plus_split_tail_matches_plain_launch(add, ragged):
     m, l, n = 3 * 4096, 4096, 100 * 512
     if ragged:  # partial last row tile and last column tile, inner dimension off the word grid
         m, l, n = m - 100, l - 37, n - 77
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    plan = m4ri_amd.plan_leaf_launch(m, l, n, 1, add=add, cus=cus)
+    assert plan.gen == 4 and plan.tail_tiles == plan.tiles % cus > 0 and plan.tail_ksplit > 1 and plan.ksplit == 1, \
+        f"on {cus} compute units the automatic plan of this shape has no split tail, so the comparison below says nothing about one: {plan}"
     A, B = dev_random(m, l, 81), dev_random(l, n, 82)
     C0 = dev_random(m, n, 83)
     w, wl = (n + 63) // 64, (l + 63) // 64
@@ -640,7 +644,12 @@ def test_inner_dimension_splits_fold_to_the_same_bits(add):
     C0 = dev_random(m, n, 93)
     w, wl = (n + 63) // 64, (l + 63) // 64
     ref = None
+    nq = 2 * wl  # 32-bit chunks of a row of A: a split takes an even number of them
     for ksplit in (1, 2, 3, 5, 7, 16, 32, 64):
+        per = -(-nq // ksplit)
+        plan = m4ri_amd.plan_leaf_launch(m, l, n, 1, add=add, ksplit=ksplit)
+        assert plan.gen == 4 and plan.ksplit == -(-nq // (per + (per & 1))), f"ksplit={ksplit}: {plan}"
+        assert plan.ksplit == {1: 1, 2: 2, 3: 3, 5: 5, 7: 7, 16: 16, 32: 29, 64: 52}[ksplit] and (plan.slabs, plan.mode) == ((1, 2) if ksplit > 1 else (0, int(add)))
         C = C0.clone()
         m4ri_amd.m4rm_dev(C.data_ptr(), w, A.data_ptr(), wl, B.data_ptr(), w, m, l, n, add=add, ksplit=ksplit)
         torch.cuda.synchronize()
