@@ -12,13 +12,11 @@
 // All of these are streaming kernels: one 64-bit word (or a 16-byte pair) per lane, rows
 // contiguous -- bounded by HBM bandwidth; only the packed-output passes tile (an LDS transpose).
 #include <hip/hip_runtime.h>
-#include <cstdlib>
 #include "gf2_internal.h"
 
 namespace {
 
 constexpr int AUX_THREADS = 256;
-constexpr int PASS_NT_DEFAULT = 2;  // up3 reads its 343 products once: nontemporal loads measure 0.70 -> 0.60 ms at 65536^3; nontemporal stores in the down passes measure slower
 
 // ---- Winograd operand combinations ----------------------------------------------------------
 // With the parent split into quadrants X11 X12 / X21 X22 the 7 children of the A side are
@@ -309,13 +307,6 @@ inline unsigned grid_for(int64_t total) {
   return (unsigned)g;
 }
 
-// measurement knob: M4RI_AMD_PASS_NT = bit mask of three-level passes that use nontemporal accesses for the 343-way side
-// (1 down3 stores, 2 up3 loads, 4 down3_pack stores)
-inline int pass_nt() {
-  static const int v = getenv("M4RI_AMD_PASS_NT") ? atoi(getenv("M4RI_AMD_PASS_NT")) : PASS_NT_DEFAULT;
-  return v;
-}
-
 inline bool vec_ok(const void *p, int64_t stride, int64_t bs, int64_t cw, int64_t qcols) {
   return ((reinterpret_cast<uintptr_t>(p) & 15) == 0) && (stride % 2 == 0) && (bs % 2 == 0) &&
          (cw % 2 == 0) && (qcols % 2 == 0);
@@ -325,31 +316,28 @@ inline bool vec_ok(const void *p, int64_t stride, int64_t bs, int64_t cw, int64_
 
 typedef unsigned long long __attribute__((ext_vector_type(2))) word2;
 
+// the lane of the one- and two-level passes: a 16-byte pair of words where vec_ok() holds on both sides (VEC = std::true_type), one word
+// otherwise; their launchers hand the kernels pointers, strides and widths in units of it
+template <typename VEC>
+using lane_t = std::conditional_t<VEC::value, word2, word>;
+
 static hipError_t gf2_launch_winograd_down(hipStream_t s, int bside, const word *parent,
                                            int64_t p_stride, int64_t p_bs, word *child,
                                            int64_t nparents, int64_t crows, int64_t cw) {
   // child matrices: crows x cw words, contiguous (stride cw), batch stride crows*cw
   const int64_t c_bs = crows * cw;
   if (nparents * c_bs == 0) return hipSuccess;
-  if (vec_ok(parent, p_stride, p_bs, cw, cw) && vec_ok(child, cw, c_bs, cw, cw)) {
-    const int64_t total = nparents * crows * (cw / 2);
-    if (bside)
-      hipLaunchKernelGGL((winograd_down_kernel<word2, true>), dim3(grid_for(total)), dim3(AUX_THREADS), 0, s,
-                         reinterpret_cast<const word2 *>(parent), p_stride / 2, p_bs / 2,
-                         reinterpret_cast<word2 *>(child), c_bs / 2, nparents, crows, cw / 2, crows, cw / 2);
-    else
-      hipLaunchKernelGGL((winograd_down_kernel<word2, false>), dim3(grid_for(total)), dim3(AUX_THREADS), 0, s,
-                         reinterpret_cast<const word2 *>(parent), p_stride / 2, p_bs / 2,
-                         reinterpret_cast<word2 *>(child), c_bs / 2, nparents, crows, cw / 2, crows, cw / 2);
-  } else {
-    const int64_t total = nparents * crows * cw;
-    if (bside)
-      hipLaunchKernelGGL((winograd_down_kernel<word, true>), dim3(grid_for(total)), dim3(AUX_THREADS), 0, s,
-                         parent, p_stride, p_bs, child, c_bs, nparents, crows, cw, crows, cw);
-    else
-      hipLaunchKernelGGL((winograd_down_kernel<word, false>), dim3(grid_for(total)), dim3(AUX_THREADS), 0, s,
-                         parent, p_stride, p_bs, child, c_bs, nparents, crows, cw, crows, cw);
-  }
+  with_bool(vec_ok(parent, p_stride, p_bs, cw, cw) && vec_ok(child, cw, c_bs, cw, cw), [&](auto VEC) {
+    using V = lane_t<decltype(VEC)>;
+    constexpr int64_t per = sizeof(V) / sizeof(word);
+    const V *src = reinterpret_cast<const V *>(parent);
+    V *dst       = reinterpret_cast<V *>(child);
+    const int64_t w = cw / per;
+    with_bool(bside, [&](auto BS) {
+      hipLaunchKernelGGL((winograd_down_kernel<V, decltype(BS)::value>), dim3(grid_for(nparents * crows * w)), dim3(AUX_THREADS), 0, s, src,
+                         p_stride / per, p_bs / per, dst, c_bs / per, nparents, crows, w, crows, w);
+    });
+  });
   return hipGetLastError();
 }
 
@@ -358,25 +346,17 @@ static hipError_t gf2_launch_winograd_up(hipStream_t s, int acc, const word *pro
                                          int64_t crows, int64_t cw) {
   const int64_t p_bs = crows * cw;
   if (nparents * p_bs == 0) return hipSuccess;
-  if (vec_ok(prod, cw, p_bs, cw, cw) && vec_ok(parent, o_stride, o_bs, cw, cw)) {
-    const int64_t total = nparents * crows * (cw / 2);
-    if (acc)
-      hipLaunchKernelGGL((winograd_up_kernel<word2, true>), dim3(grid_for(total)), dim3(AUX_THREADS), 0, s,
-                         reinterpret_cast<const word2 *>(prod), p_bs / 2, reinterpret_cast<word2 *>(parent),
-                         o_stride / 2, o_bs / 2, nparents, crows, cw / 2, crows, cw / 2);
-    else
-      hipLaunchKernelGGL((winograd_up_kernel<word2, false>), dim3(grid_for(total)), dim3(AUX_THREADS), 0, s,
-                         reinterpret_cast<const word2 *>(prod), p_bs / 2, reinterpret_cast<word2 *>(parent),
-                         o_stride / 2, o_bs / 2, nparents, crows, cw / 2, crows, cw / 2);
-  } else {
-    const int64_t total = nparents * crows * cw;
-    if (acc)
-      hipLaunchKernelGGL((winograd_up_kernel<word, true>), dim3(grid_for(total)), dim3(AUX_THREADS), 0, s,
-                         prod, p_bs, parent, o_stride, o_bs, nparents, crows, cw, crows, cw);
-    else
-      hipLaunchKernelGGL((winograd_up_kernel<word, false>), dim3(grid_for(total)), dim3(AUX_THREADS), 0, s,
-                         prod, p_bs, parent, o_stride, o_bs, nparents, crows, cw, crows, cw);
-  }
+  with_bool(vec_ok(prod, cw, p_bs, cw, cw) && vec_ok(parent, o_stride, o_bs, cw, cw), [&](auto VEC) {
+    using V = lane_t<decltype(VEC)>;
+    constexpr int64_t per = sizeof(V) / sizeof(word);
+    const V *src = reinterpret_cast<const V *>(prod);
+    V *dst       = reinterpret_cast<V *>(parent);
+    const int64_t w = cw / per;
+    with_bool(acc, [&](auto ACC) {
+      hipLaunchKernelGGL((winograd_up_kernel<V, decltype(ACC)::value>), dim3(grid_for(nparents * crows * w)), dim3(AUX_THREADS), 0, s, src,
+                         p_bs / per, dst, o_stride / per, o_bs / per, nparents, crows, w, crows, w);
+    });
+  });
   return hipGetLastError();
 }
 
@@ -462,7 +442,7 @@ extern "C" hipError_t gf2_launch_fill_splitmix(hipStream_t s, word *M, int64_t s
 namespace {
 constexpr int DP_ROWS = 32, DP_V = 8, DP_PITCH = 36;  // tile rows, 16-byte vectors per row, LDS row pitch (dwords)
 
-template <int ROT>  // 0: plain chunk-major, 1: generation 4's byte rotation, 2: generation 5's rotation + chunk swap
+template <int ROT>  // 0: plain chunk-major, 1: generation 4's byte rotation
 __global__ __launch_bounds__(AUX_THREADS) void winograd_down2_pack_kernel(
     const word2 *__restrict__ gparent, int64_t p_stride, int64_t p_bs,  // grandparent array (units of word2)
     uint32_t *__restrict__ a4, int64_t a4_bs,                           // packed grandchildren, a4_bs dwords each
@@ -486,12 +466,11 @@ __global__ __launch_bounds__(AUX_THREADS) void winograd_down2_pack_kernel(
     for (int b = 0; b < 2; ++b) winograd_combos<word2, false>(x[a][b], x[a][b + 2], x[a + 2][b], x[a + 2][b + 2], y[2 * a + b]);
   // write side: thread -> chunk q (0..31 of the tile) and four consecutive rows
   const int q = t >> 3, r4 = (t & 7) * 4;
-  // generation 4 wants the four index bytes of a dword rotated by (row >> 6) & 3 (m4rm8q_leaf.hip),
-  // generation 5 by (row >> 7) & 3 with the two chunks of a word swapped when (row >> 5) & 1
-  // (m4rm8o_leaf.hip); the four rows of one store share those values
+  // generation 4 wants the four index bytes of a dword rotated by (row >> 6) & 3 (m4rm8q_leaf.hip); the four rows of one store share
+  // that value
   const int64_t orow = rt * DP_ROWS + r4;
-  const uint32_t rot = ROT == 1 ? (uint32_t)((orow >> 6) & 3) : ROT == 2 ? (uint32_t)((orow >> 7) & 3) : 0u;
-  const int64_t oq   = (wt * (DP_V * 4) + q) ^ (ROT == 2 ? ((orow >> 5) & 1) : 0);
+  const uint32_t rot = ROT == 1 ? (uint32_t)((orow >> 6) & 3) : 0u;
+  const int64_t oq   = wt * (DP_V * 4) + q;
   uint32_t *o = a4 + (pi * 49) * a4_bs + oq * crows + orow;
 #pragma unroll
   for (int j1 = 0; j1 < 7; ++j1) {
@@ -517,7 +496,7 @@ __global__ __launch_bounds__(AUX_THREADS) void winograd_down2_pack_kernel(
 
 // Grandchild i of the pass lands at a4 + i * (crows * cw * 2) dwords, laid out exactly as
 // gf2_launch_a4_pack(_rot) would have packed the row-major grandchild.  Returns
-// hipErrorInvalidValue when the shape does not tile (caller falls back to down2 + pack).
+// hipErrorInvalidValue when the shape does not tile (caller falls back to down2 + pack) or rot is not 0 or 1.
 static int gf2_winograd_down2_pack_ok(const word *gparent, int64_t p_stride, int64_t p_bs, const word *a4,
                                       int64_t crows, int64_t cw) {
   return vec_ok(gparent, p_stride, p_bs, cw, cw) && crows > 0 && cw > 0 && crows % DP_ROWS == 0 && cw % (2 * DP_V) == 0 &&
@@ -531,12 +510,11 @@ static hipError_t gf2_launch_winograd_down2_pack(hipStream_t s, const word *gpar
   const int64_t tiles_r = crows / DP_ROWS, tiles_w = (cw / 2) / DP_V;
   const int64_t grid = nparents * tiles_r * tiles_w;
   if (grid > 0x7fffffffLL) return hipErrorInvalidValue;
-#define DP2_LAUNCH(R)                                                                                         \
-  hipLaunchKernelGGL((winograd_down2_pack_kernel<R>), dim3((unsigned)grid), dim3(AUX_THREADS), 0, s,                \
-                     reinterpret_cast<const word2 *>(gparent), p_stride / 2, p_bs / 2, reinterpret_cast<uint32_t *>(a4), \
-                     crows * cw * 2, crows, cw / 2, tiles_r, tiles_w)
-  if (rot == 2) DP2_LAUNCH(2); else if (rot == 1) DP2_LAUNCH(1); else DP2_LAUNCH(0);
-#undef DP2_LAUNCH
+  with_bool(rot == 1, [&](auto ROT) {
+    hipLaunchKernelGGL((winograd_down2_pack_kernel<decltype(ROT)::value>), dim3((unsigned)grid), dim3(AUX_THREADS), 0, s,
+                       reinterpret_cast<const word2 *>(gparent), p_stride / 2, p_bs / 2, reinterpret_cast<uint32_t *>(a4), crows * cw * 2,
+                       crows, cw / 2, tiles_r, tiles_w);
+  });
   return hipGetLastError();
 }
 
@@ -590,7 +568,39 @@ __device__ __forceinline__ void winograd_scatter(const V pr, int j, V &c11, V &c
   }
 }
 
-template <bool BSIDE, bool NT>
+// The three-level expansion tree of an 8 x 8 grid of blocks, one child at a time (what keeps the register count down).
+// winograd_expand2: f(7 * j1 + j2, c2) with the 2 x 2 blocks of child j2 of child j1; winograd_expand3: f(49 * j1 + 7 * j2 + j3, v) with
+// the word of descendant (j1, j2, j3).  Everything unrolls: the index is a constant where f uses it.
+template <bool BSIDE, typename F>
+__device__ __forceinline__ void winograd_expand2(const word (&x)[8][8], F &&f) {
+#pragma unroll
+  for (int j1 = 0; j1 < 7; ++j1) {
+    word c1[4][4];
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+      for (int b = 0; b < 4; ++b) c1[a][b] = winograd_child<word, BSIDE>(x[a][b], x[a][b + 4], x[a + 4][b], x[a + 4][b + 4], j1);
+#pragma unroll
+    for (int j2 = 0; j2 < 7; ++j2) {
+      word c2[2][2];
+#pragma unroll
+      for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b) c2[a][b] = winograd_child<word, BSIDE>(c1[a][b], c1[a][b + 2], c1[a + 2][b], c1[a + 2][b + 2], j2);
+      f(7 * j1 + j2, c2);
+    }
+  }
+}
+
+template <bool BSIDE, typename F>
+__device__ __forceinline__ void winograd_expand3(const word (&x)[8][8], F &&f) {
+  winograd_expand2<BSIDE>(x, [&](int g, const word (&c2)[2][2]) {
+#pragma unroll
+    for (int j3 = 0; j3 < 7; ++j3) f(7 * g + j3, winograd_child<word, BSIDE>(c2[0][0], c2[0][1], c2[1][0], c2[1][1], j3));
+  });
+}
+
+template <bool BSIDE>
 __global__ __launch_bounds__(AUX_THREADS) void winograd_down3_kernel(
     const word *__restrict__ anc, int64_t p_stride, int64_t p_bs,  // ancestor array
     word *__restrict__ gchild, int64_t c_bs,                       // great-grandchildren, stride == cw
@@ -610,32 +620,12 @@ __global__ __launch_bounds__(AUX_THREADS) void winograd_down3_kernel(
 #pragma unroll
       for (int b = 0; b < 8; ++b) x[a][b] = p[(int64_t)a * crows * p_stride + (int64_t)b * cw];
     word *c = gchild + (pi * 343) * c_bs + r * cw + w;
-#pragma unroll
-    for (int j1 = 0; j1 < 7; ++j1) {
-      word c1[4][4];
-#pragma unroll
-      for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) c1[a][b] = winograd_child<word, BSIDE>(x[a][b], x[a][b + 4], x[a + 4][b], x[a + 4][b + 4], j1);
-#pragma unroll
-      for (int j2 = 0; j2 < 7; ++j2) {
-        word c2[2][2];
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-          for (int b = 0; b < 2; ++b) c2[a][b] = winograd_child<word, BSIDE>(c1[a][b], c1[a][b + 2], c1[a + 2][b], c1[a + 2][b + 2], j2);
-#pragma unroll
-        for (int j3 = 0; j3 < 7; ++j3) {
-          const word v = winograd_child<word, BSIDE>(c2[0][0], c2[0][1], c2[1][0], c2[1][1], j3);
-          if (NT) __builtin_nontemporal_store(v, &c[(int64_t)(49 * j1 + 7 * j2 + j3) * c_bs]);
-          else c[(int64_t)(49 * j1 + 7 * j2 + j3) * c_bs] = v;
-        }
-      }
-    }
+    // (plain stores: nontemporal stores of the 343 streams measure slower in every down pass)
+    winograd_expand3<BSIDE>(x, [&](int k, word v) { c[(int64_t)k * c_bs] = v; });
   }
 }
 
-template <bool ACC, bool NT>
+template <bool ACC>
 __global__ __launch_bounds__(AUX_THREADS) void winograd_up3_kernel(
     const word *__restrict__ prod, int64_t p_bs,                   // 343 products per ancestor, stride == cw
     word *__restrict__ anc, int64_t o_stride, int64_t o_bs,        // ancestor array
@@ -664,10 +654,10 @@ __global__ __launch_bounds__(AUX_THREADS) void winograd_up3_kernel(
 #pragma unroll
       for (int j2 = 0; j2 < 7; ++j2) {
         word c2[2][2] = {{0, 0}, {0, 0}};
+        // the 343 products are read once: nontemporal loads measure 0.70 -> 0.60 ms for this pass at 65536^3
 #pragma unroll
         for (int j3 = 0; j3 < 7; ++j3)
-          winograd_scatter<word>(NT ? __builtin_nontemporal_load(&q[(int64_t)(49 * j1 + 7 * j2 + j3) * p_bs]) : q[(int64_t)(49 * j1 + 7 * j2 + j3) * p_bs],
-                                 j3, c2[0][0], c2[0][1], c2[1][0], c2[1][1]);
+          winograd_scatter<word>(__builtin_nontemporal_load(&q[(int64_t)(49 * j1 + 7 * j2 + j3) * p_bs]), j3, c2[0][0], c2[0][1], c2[1][0], c2[1][1]);
 #pragma unroll
         for (int a = 0; a < 2; ++a)
 #pragma unroll
@@ -700,7 +690,7 @@ __global__ __launch_bounds__(AUX_THREADS) void winograd_up3_kernel(
 // the writes (16 lanes = the 16 slots of one row) stay conflict-free and 8-byte aligned.
 constexpr int DP3_ROWS = 32, DP3_W = 16, DP3_PITCH = 32, DP3_THREADS = 512;
 
-template <int ROT, bool NT>
+template <int ROT>
 __global__ __launch_bounds__(DP3_THREADS) void winograd_down3_pack_kernel(
     const word *__restrict__ anc, int64_t p_stride, int64_t p_bs,
     uint32_t *__restrict__ a4, int64_t a4_bs,                       // packed great-grandchildren, a4_bs dwords each
@@ -719,45 +709,30 @@ __global__ __launch_bounds__(DP3_THREADS) void winograd_down3_pack_kernel(
     for (int b = 0; b < 8; ++b) x[a][b] = p[(int64_t)a * crows * p_stride + (int64_t)b * cw];
   // write side: thread -> chunk q (0..31 of the tile) and two consecutive rows
   const int q = t >> 4, r2 = (t & 15) * 2;
-  const int64_t orow = rt * DP3_ROWS + r2;  // both rows share the rotation / swap
-  const uint32_t rot = ROT == 1 ? (uint32_t)((orow >> 6) & 3) : ROT == 2 ? (uint32_t)((orow >> 7) & 3) : 0u;
-  const int64_t oq   = (wt * (DP3_W * 2) + q) ^ (ROT == 2 ? ((orow >> 5) & 1) : 0);
+  const int64_t orow = rt * DP3_ROWS + r2;  // both rows share the rotation
+  const uint32_t rot = ROT == 1 ? (uint32_t)((orow >> 6) & 3) : 0u;
+  const int64_t oq   = wt * (DP3_W * 2) + q;
   uint32_t *o = a4 + (pi * 343) * a4_bs + oq * crows + orow;
+  winograd_expand2<false>(x, [&](int g, const word (&c2)[2][2]) {
+    // the seven outputs of (j1, j2) go through seven tiles of one of two sets and ONE barrier: the other set is only rewritten after the
+    // next barrier, when every thread has read this one (49 barriers per workgroup instead of 343: with one 512-thread workgroup per
+    // CU a barrier per 4 KiB of output was a visible part of the pass)
+    uint32_t *set = tile[g & 1];
 #pragma unroll
-  for (int j1 = 0; j1 < 7; ++j1) {
-    word c1[4][4];
+    for (int j3 = 0; j3 < 7; ++j3)
+      *reinterpret_cast<word *>(set + j3 * (DP3_ROWS * DP3_PITCH) + r * DP3_PITCH + 2 * (v ^ ((r >> 1) & 15))) =
+          winograd_child<word, false>(c2[0][0], c2[0][1], c2[1][0], c2[1][1], j3);
+    __syncthreads();
+    const int rs = 2 * ((q >> 1) ^ ((r2 >> 1) & 15)) + (q & 1);  // rows r2 and r2 + 1 share the swizzle
 #pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-      for (int b = 0; b < 4; ++b) c1[a][b] = winograd_child<word, false>(x[a][b], x[a][b + 4], x[a + 4][b], x[a + 4][b + 4], j1);
-#pragma unroll
-    for (int j2 = 0; j2 < 7; ++j2) {
-      word c2[2][2];
-#pragma unroll
-      for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b) c2[a][b] = winograd_child<word, false>(c1[a][b], c1[a][b + 2], c1[a + 2][b], c1[a + 2][b + 2], j2);
-      // the seven outputs of (j1, j2) go through seven tiles of one of two sets and ONE barrier: the other set is only rewritten after the
-      // next barrier, when every thread has read this one (49 barriers per workgroup instead of 343: with one 512-thread workgroup per
-      // CU a barrier per 4 KiB of output was a visible part of the pass)
-      uint32_t *set = tile[(7 * j1 + j2) & 1];
-#pragma unroll
-      for (int j3 = 0; j3 < 7; ++j3)
-        *reinterpret_cast<word *>(set + j3 * (DP3_ROWS * DP3_PITCH) + r * DP3_PITCH + 2 * (v ^ ((r >> 1) & 15))) =
-            winograd_child<word, false>(c2[0][0], c2[0][1], c2[1][0], c2[1][1], j3);
-      __syncthreads();
-      const int rs = 2 * ((q >> 1) ^ ((r2 >> 1) & 15)) + (q & 1);  // rows r2 and r2 + 1 share the swizzle
-#pragma unroll
-      for (int j3 = 0; j3 < 7; ++j3) {
-        const int k        = 49 * j1 + 7 * j2 + j3;
-        const uint32_t *tb = set + j3 * (DP3_ROWS * DP3_PITCH);
-        uint32_t w0 = tb[(r2 + 0) * DP3_PITCH + rs], w1 = tb[(r2 + 1) * DP3_PITCH + rs];
-        if (ROT) { w0 = __builtin_amdgcn_alignbyte(w0, w0, rot); w1 = __builtin_amdgcn_alignbyte(w1, w1, rot); }
-        if (NT) __builtin_nontemporal_store((unsigned long long)w0 | ((unsigned long long)w1 << 32), reinterpret_cast<unsigned long long *>(o + (int64_t)k * a4_bs));
-        else *reinterpret_cast<uint2 *>(o + (int64_t)k * a4_bs) = make_uint2(w0, w1);
-      }
+    for (int j3 = 0; j3 < 7; ++j3) {
+      const int k        = 7 * g + j3;
+      const uint32_t *tb = set + j3 * (DP3_ROWS * DP3_PITCH);
+      uint32_t w0 = tb[(r2 + 0) * DP3_PITCH + rs], w1 = tb[(r2 + 1) * DP3_PITCH + rs];
+      if (ROT) { w0 = __builtin_amdgcn_alignbyte(w0, w0, rot); w1 = __builtin_amdgcn_alignbyte(w1, w1, rot); }
+      *reinterpret_cast<uint2 *>(o + (int64_t)k * a4_bs) = make_uint2(w0, w1);
     }
-  }
+  });
 }
 }  // namespace
 
@@ -766,12 +741,10 @@ static hipError_t gf2_launch_winograd_down3(hipStream_t s, int bside, const word
   const int64_t c_bs = crows * cw;
   if (nparents * c_bs == 0) return hipSuccess;
   const int64_t total = nparents * c_bs;
-#define D3_LAUNCH(BS, NT)                                                                                                      \
-  hipLaunchKernelGGL((winograd_down3_kernel<BS, NT>), dim3(grid_for(total)), dim3(AUX_THREADS), 0, s, anc, p_stride, p_bs, gchild, c_bs, \
-                     nparents, crows, cw)
-  if (pass_nt() & 1) { if (bside) D3_LAUNCH(true, true); else D3_LAUNCH(false, true); }
-  else { if (bside) D3_LAUNCH(true, false); else D3_LAUNCH(false, false); }
-#undef D3_LAUNCH
+  with_bool(bside, [&](auto BS) {
+    hipLaunchKernelGGL((winograd_down3_kernel<decltype(BS)::value>), dim3(grid_for(total)), dim3(AUX_THREADS), 0, s, anc, p_stride, p_bs, gchild,
+                       c_bs, nparents, crows, cw);
+  });
   return hipGetLastError();
 }
 
@@ -780,12 +753,10 @@ static hipError_t gf2_launch_winograd_up3(hipStream_t s, int acc, const word *pr
   const int64_t p_bs = crows * cw;
   if (nparents * p_bs == 0) return hipSuccess;
   const int64_t total = nparents * p_bs;
-#define U3_LAUNCH(AC, NT)                                                                                                            \
-  hipLaunchKernelGGL((winograd_up3_kernel<AC, NT>), dim3(grid_for(total)), dim3(AUX_THREADS), 0, s, prod, p_bs, anc, o_stride, o_bs, nparents, \
-                     crows, cw)
-  if (pass_nt() & 2) { if (acc) U3_LAUNCH(true, true); else U3_LAUNCH(false, true); }
-  else { if (acc) U3_LAUNCH(true, false); else U3_LAUNCH(false, false); }
-#undef U3_LAUNCH
+  with_bool(acc, [&](auto ACC) {
+    hipLaunchKernelGGL((winograd_up3_kernel<decltype(ACC)::value>), dim3(grid_for(total)), dim3(AUX_THREADS), 0, s, prod, p_bs, anc, o_stride, o_bs,
+                       nparents, crows, cw);
+  });
   return hipGetLastError();
 }
 
@@ -802,12 +773,10 @@ static hipError_t gf2_launch_winograd_down3_pack(hipStream_t s, const word *anc,
   const int64_t tiles_r = crows / DP3_ROWS, tiles_w = cw / DP3_W;
   const int64_t grid = nparents * tiles_r * tiles_w;
   if (grid > 0x7fffffffLL) return hipErrorInvalidValue;
-#define DP3_LAUNCH(R, NT)                                                                                              \
-  hipLaunchKernelGGL((winograd_down3_pack_kernel<R, NT>), dim3((unsigned)grid), dim3(DP3_THREADS), 0, s, anc, p_stride, p_bs, \
-                     reinterpret_cast<uint32_t *>(a4), crows * cw * 2, crows, cw, tiles_r, tiles_w)
-  if (pass_nt() & 4) { if (rot == 2) DP3_LAUNCH(2, true); else if (rot == 1) DP3_LAUNCH(1, true); else DP3_LAUNCH(0, true); }
-  else { if (rot == 2) DP3_LAUNCH(2, false); else if (rot == 1) DP3_LAUNCH(1, false); else DP3_LAUNCH(0, false); }
-#undef DP3_LAUNCH
+  with_bool(rot == 1, [&](auto ROT) {
+    hipLaunchKernelGGL((winograd_down3_pack_kernel<decltype(ROT)::value>), dim3((unsigned)grid), dim3(DP3_THREADS), 0, s, anc, p_stride, p_bs,
+                       reinterpret_cast<uint32_t *>(a4), crows * cw * 2, crows, cw, tiles_r, tiles_w);
+  });
   return hipGetLastError();
 }
 
@@ -861,7 +830,7 @@ __device__ __forceinline__ word load_top_child(const word *q11, int64_t qr, int6
 
 // (Tried and measured, profiles/r04_depth4_fused/: ONE workgroup of seven waves per 64 positions, wave = j0, so that the siblings'
 // loads are issued at the same moment -- slower, down4 1.37 -> 1.46 ms, up4 1.34 -> 1.61 ms: one 448-thread workgroup per CU.)
-template <bool BSIDE, bool NT>
+template <bool BSIDE>
 __global__ __launch_bounds__(AUX_THREADS) void winograd_down4_kernel(
     const word *__restrict__ anc, int64_t p_stride, int64_t p_bs,  // ancestor array: 16 * crows rows x 16 * cw words each
     word *__restrict__ gchild, int64_t c_bs,                       // 2401 descendants per ancestor, stride == cw
@@ -879,28 +848,7 @@ __global__ __launch_bounds__(AUX_THREADS) void winograd_down4_kernel(
 #pragma unroll
     for (int b = 0; b < 8; ++b) x[a][b] = load_top_child<BSIDE>(p + (int64_t)a * crows * p_stride + (int64_t)b * cw, 8 * crows * p_stride, 8 * cw, j0);
   word *c = gchild + (pi * 2401 + 343 * j0) * c_bs + r * cw + w;
-#pragma unroll
-  for (int j1 = 0; j1 < 7; ++j1) {
-    word c1[4][4];
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-      for (int b = 0; b < 4; ++b) c1[a][b] = winograd_child<word, BSIDE>(x[a][b], x[a][b + 4], x[a + 4][b], x[a + 4][b + 4], j1);
-#pragma unroll
-    for (int j2 = 0; j2 < 7; ++j2) {
-      word c2[2][2];
-#pragma unroll
-      for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b) c2[a][b] = winograd_child<word, BSIDE>(c1[a][b], c1[a][b + 2], c1[a + 2][b], c1[a + 2][b + 2], j2);
-#pragma unroll
-      for (int j3 = 0; j3 < 7; ++j3) {
-        const word v = winograd_child<word, BSIDE>(c2[0][0], c2[0][1], c2[1][0], c2[1][1], j3);
-        if (NT) __builtin_nontemporal_store(v, &c[(int64_t)(49 * j1 + 7 * j2 + j3) * c_bs]);
-        else c[(int64_t)(49 * j1 + 7 * j2 + j3) * c_bs] = v;
-      }
-    }
-  }
+  winograd_expand3<BSIDE>(x, [&](int k, word v) { c[(int64_t)k * c_bs] = v; });
 }
 
 // out[a][b] ^-> block (a, b) of the quadrants T11 ... T22 of the ancestor (no-return L2 atomics)
@@ -919,7 +867,6 @@ __device__ __forceinline__ void up4_scatter(const word (&out)[8][8], char *ob, u
     }
 }
 
-template <bool NT>
 __global__ __launch_bounds__(AUX_THREADS) void winograd_up4_kernel(
     const word *__restrict__ prod, int64_t p_bs,            // 2401 products per ancestor, stride == cw
     word *__restrict__ anc, int64_t o_stride, int64_t o_bs, // ancestor array, zeroed (or holding the matrix to accumulate onto)
@@ -938,11 +885,12 @@ __global__ __launch_bounds__(AUX_THREADS) void winograd_up4_kernel(
     for (int b = 0; b < 8; ++b) out[a][b] = 0;
   // The 343 products are consumed in 49 groups of 7 (one j2 each), software-pipelined by hand: group g + 1 is loaded, then group g
   // folded.  The scheduling barriers keep the memory operations in this order -- left alone, the compiler issues all 343 loads up
-  // front and spills most of them (it does not in the three-level kernel, whose tail is plain stores)
+  // front and spills most of them (it does not in the three-level kernel, whose tail is plain stores).  Nontemporal loads, as in the
+  // three-level kernel: every product is read once
   word buf[2][7];
   auto load_group = [&](int g, word (&dst)[7]) {
 #pragma unroll
-    for (int j3 = 0; j3 < 7; ++j3) dst[j3] = NT ? __builtin_nontemporal_load(&q[(int64_t)(7 * g + j3) * p_bs]) : q[(int64_t)(7 * g + j3) * p_bs];
+    for (int j3 = 0; j3 < 7; ++j3) dst[j3] = __builtin_nontemporal_load(&q[(int64_t)(7 * g + j3) * p_bs]);
   };
   load_group(0, buf[0]);
 #pragma unroll
@@ -993,11 +941,40 @@ __global__ __launch_bounds__(AUX_THREADS) void winograd_up4_kernel(
   }
 }
 
+// The LDS forms of the four-level down passes share their first half.  load_grid16: the 256 threads of a workgroup load the 16 x 16 grid
+// of blocks of their 32 positions into LDS (p: the thread's position in block (0, 0); thread (pp, g) loads blocks g, g + 8, ...).
+// grid_top_child: block (a, b), a, b < 8, of top-level child j0 from the up to four grid blocks it is made of (winograd_child's table),
+// chosen by all-ones / zero masks per lane.
+__device__ __forceinline__ void load_grid16(word *grid, const word *p, int64_t crows, int64_t p_stride, int64_t cw, int pp, int g) {
+#pragma unroll 8
+  for (int k = 0; k < 32; ++k) {
+    const int blk = k * 8 + g;
+    grid[blk * 32 + pp] = p[(int64_t)(blk >> 4) * crows * p_stride + (int64_t)(blk & 15) * cw];
+  }
+}
+
+template <bool BSIDE>
+__device__ __forceinline__ void grid_top_child(const word *grid, int pp, int j0, word (&x)[8][8]) {
+  bool u11, u12, u21, u22;
+  if (!BSIDE) {  // [A11, A12, S4, A22, S1, S2, S3]
+    u11 = j0 == 0 || j0 == 2 || j0 == 5 || j0 == 6; u12 = j0 == 1 || j0 == 2; u21 = j0 == 2 || j0 == 4 || j0 == 5 || j0 == 6; u22 = j0 >= 2 && j0 <= 5;
+  } else {       // [B11, B21, B22, T4, T1, T2, T3]
+    u11 = j0 == 0 || j0 == 3 || j0 == 4 || j0 == 5; u12 = j0 >= 3; u21 = j0 == 1 || j0 == 3; u22 = j0 == 2 || j0 == 3 || j0 == 5 || j0 == 6;
+  }
+  const word m11 = u11 ? ~(word)0 : 0, m12 = u12 ? ~(word)0 : 0, m21 = u21 ? ~(word)0 : 0, m22 = u22 ? ~(word)0 : 0;
+#pragma unroll
+  for (int a = 0; a < 8; ++a)
+#pragma unroll
+    for (int b = 0; b < 8; ++b)
+      x[a][b] = (grid[(a * 16 + b) * 32 + pp] & m11) ^ (grid[(a * 16 + b + 8) * 32 + pp] & m12) ^ (grid[((a + 8) * 16 + b) * 32 + pp] & m21) ^
+                (grid[((a + 8) * 16 + b + 8) * 32 + pp] & m22);
+}
+
 // Down, with the ancestor read ONCE: a workgroup owns 32 word positions, loads their 16 x 16 grid into LDS (64 KiB, every load 256
 // contiguous bytes), and after one barrier half-wave g (of 8; the last idles) forms top-level child g from the grid -- up to four
 // LDS reads per word, chosen by per-lane masks -- and expands it through the three levels in registers.  (The form above leaves the
 // siblings' re-reads to the L2, which absorbs half of them: 0.97 GB read for a 0.54 GB ancestor.)
-template <bool BSIDE, bool NT>
+template <bool BSIDE>
 __global__ __launch_bounds__(AUX_THREADS) void winograd_down4_lds_kernel(
     const word *__restrict__ anc, int64_t p_stride, int64_t p_bs,  // ancestor array: 16 * crows rows x 16 * cw words each
     word *__restrict__ gchild, int64_t c_bs,                       // 2401 descendants per ancestor, stride == cw
@@ -1006,53 +983,14 @@ __global__ __launch_bounds__(AUX_THREADS) void winograd_down4_lds_kernel(
   const int tid = threadIdx.x, pp = tid & 31, g = tid >> 5;
   const int64_t i = (int64_t)blockIdx.x * 32 + pp, pi = blockIdx.y;
   const int64_t r = i / cw, w = i - r * cw;
-  const word *p   = anc + pi * p_bs + r * p_stride + w;
-#pragma unroll 8
-  for (int k = 0; k < 32; ++k) {
-    const int blk = k * 8 + g;
-    grid[blk * 32 + pp] = p[(int64_t)(blk >> 4) * crows * p_stride + (int64_t)(blk & 15) * cw];
-  }
+  load_grid16(grid, anc + pi * p_bs + r * p_stride + w, crows, p_stride, cw, pp, g);
   __syncthreads();
   if (g >= 7) return;
-  // which quadrants top-level child g is made of (winograd_child's table), as all-ones / zero masks per lane
   const int j0 = g;
-  bool u11, u12, u21, u22;
-  if (!BSIDE) {  // [A11, A12, S4, A22, S1, S2, S3]
-    u11 = j0 == 0 || j0 == 2 || j0 == 5 || j0 == 6; u12 = j0 == 1 || j0 == 2; u21 = j0 == 2 || j0 == 4 || j0 == 5 || j0 == 6; u22 = j0 >= 2 && j0 <= 5;
-  } else {       // [B11, B21, B22, T4, T1, T2, T3]
-    u11 = j0 == 0 || j0 == 3 || j0 == 4 || j0 == 5; u12 = j0 >= 3; u21 = j0 == 1 || j0 == 3; u22 = j0 == 2 || j0 == 3 || j0 == 5 || j0 == 6;
-  }
-  const word m11 = u11 ? ~(word)0 : 0, m12 = u12 ? ~(word)0 : 0, m21 = u21 ? ~(word)0 : 0, m22 = u22 ? ~(word)0 : 0;
   word x[8][8];
-#pragma unroll
-  for (int a = 0; a < 8; ++a)
-#pragma unroll
-    for (int b = 0; b < 8; ++b)
-      x[a][b] = (grid[(a * 16 + b) * 32 + pp] & m11) ^ (grid[(a * 16 + b + 8) * 32 + pp] & m12) ^ (grid[((a + 8) * 16 + b) * 32 + pp] & m21) ^
-                (grid[((a + 8) * 16 + b + 8) * 32 + pp] & m22);
+  grid_top_child<BSIDE>(grid, pp, j0, x);
   word *c = gchild + (pi * 2401 + 343 * j0) * c_bs + r * cw + w;
-#pragma unroll
-  for (int j1 = 0; j1 < 7; ++j1) {
-    word c1[4][4];
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-      for (int b = 0; b < 4; ++b) c1[a][b] = winograd_child<word, BSIDE>(x[a][b], x[a][b + 4], x[a + 4][b], x[a + 4][b + 4], j1);
-#pragma unroll
-    for (int j2 = 0; j2 < 7; ++j2) {
-      word c2[2][2];
-#pragma unroll
-      for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b) c2[a][b] = winograd_child<word, BSIDE>(c1[a][b], c1[a][b + 2], c1[a + 2][b], c1[a + 2][b + 2], j2);
-#pragma unroll
-      for (int j3 = 0; j3 < 7; ++j3) {
-        const word v = winograd_child<word, BSIDE>(c2[0][0], c2[0][1], c2[1][0], c2[1][1], j3);
-        if (NT) __builtin_nontemporal_store(v, &c[(int64_t)(49 * j1 + 7 * j2 + j3) * c_bs]);
-        else c[(int64_t)(49 * j1 + 7 * j2 + j3) * c_bs] = v;
-      }
-    }
-  }
+  winograd_expand3<BSIDE>(x, [&](int k, word v) { c[(int64_t)k * c_bs] = v; });
 }
 
 // The A side in the leaf's packed form, the same way -- and without the transpose.  A workgroup owns ONE word column and 32 consecutive
@@ -1061,7 +999,7 @@ __global__ __launch_bounds__(AUX_THREADS) void winograd_down4_lds_kernel(
 // paid where it is cheap: the grid is LOADED 8 bytes per row (32 lines touched per block), and the other 15 words of every line belong
 // to the workgroups of the neighbouring word columns, which are numbered 8 apart so that they run on the same XCD next to each other and
 // find the line in its L2.
-template <int ROT, bool NT>
+template <int ROT>
 __global__ __launch_bounds__(AUX_THREADS) void winograd_down4_pack_lds_kernel(
     const word *__restrict__ anc, int64_t p_stride, int64_t p_bs,
     uint32_t *__restrict__ a4, int64_t a4_bs,       // packed descendants, a4_bs dwords each
@@ -1074,51 +1012,21 @@ __global__ __launch_bounds__(AUX_THREADS) void winograd_down4_pack_lds_kernel(
   const int64_t rb = (grp / wgroups) * 8 + xcd, wc = (grp % wgroups) * 16 + slot;
   if (rb * 32 >= crows) return;                      // (whole workgroups: the row blocks of the last group may not all exist)
   const int64_t r = rb * 32 + pp, pi = blockIdx.y;
-  const word *p   = anc + pi * p_bs + r * p_stride + wc;
-#pragma unroll 8
-  for (int k = 0; k < 32; ++k) {
-    const int blk = k * 8 + g;
-    grid[blk * 32 + pp] = p[(int64_t)(blk >> 4) * crows * p_stride + (int64_t)(blk & 15) * cw];
-  }
+  load_grid16(grid, anc + pi * p_bs + r * p_stride + wc, crows, p_stride, cw, pp, g);
   __syncthreads();
   if (g >= 7) return;
-  const int j0 = g;   // [A11, A12, S4, A22, S1, S2, S3]
-  const bool u11 = j0 == 0 || j0 == 2 || j0 == 5 || j0 == 6, u12 = j0 == 1 || j0 == 2, u21 = j0 == 2 || j0 == 4 || j0 == 5 || j0 == 6, u22 = j0 >= 2 && j0 <= 5;
-  const word m11 = u11 ? ~(word)0 : 0, m12 = u12 ? ~(word)0 : 0, m21 = u21 ? ~(word)0 : 0, m22 = u22 ? ~(word)0 : 0;
+  const int j0 = g;
   word x[8][8];
-#pragma unroll
-  for (int a = 0; a < 8; ++a)
-#pragma unroll
-    for (int bb = 0; bb < 8; ++bb)
-      x[a][bb] = (grid[(a * 16 + bb) * 32 + pp] & m11) ^ (grid[(a * 16 + bb + 8) * 32 + pp] & m12) ^ (grid[((a + 8) * 16 + bb) * 32 + pp] & m21) ^
-                 (grid[((a + 8) * 16 + bb + 8) * 32 + pp] & m22);
+  grid_top_child<false>(grid, pp, j0, x);
   const uint32_t rot = ROT == 1 ? (uint32_t)((r >> 6) & 3) : 0u;   // generation 4's byte rotation of the index dwords (m4rm8q_leaf.hip)
   uint32_t *o = a4 + (pi * 2401 + 343 * j0) * a4_bs + (2 * wc) * crows + r;
-#pragma unroll
-  for (int j1 = 0; j1 < 7; ++j1) {
-    word c1[4][4];
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-      for (int bb = 0; bb < 4; ++bb) c1[a][bb] = winograd_child<word, false>(x[a][bb], x[a][bb + 4], x[a + 4][bb], x[a + 4][bb + 4], j1);
-#pragma unroll
-    for (int j2 = 0; j2 < 7; ++j2) {
-      word c2[2][2];
-#pragma unroll
-      for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int bb = 0; bb < 2; ++bb) c2[a][bb] = winograd_child<word, false>(c1[a][bb], c1[a][bb + 2], c1[a + 2][bb], c1[a + 2][bb + 2], j2);
-#pragma unroll
-      for (int j3 = 0; j3 < 7; ++j3) {
-        const word v = winograd_child<word, false>(c2[0][0], c2[0][1], c2[1][0], c2[1][1], j3);
-        uint32_t w0 = (uint32_t)v, w1 = (uint32_t)(v >> 32);
-        if (ROT) { w0 = __builtin_amdgcn_alignbyte(w0, w0, rot); w1 = __builtin_amdgcn_alignbyte(w1, w1, rot); }
-        uint32_t *oo = o + (int64_t)(49 * j1 + 7 * j2 + j3) * a4_bs;
-        if (NT) { __builtin_nontemporal_store(w0, oo); __builtin_nontemporal_store(w1, oo + crows); }
-        else { oo[0] = w0; oo[crows] = w1; }
-      }
-    }
-  }
+  winograd_expand3<false>(x, [&](int k, word v) {
+    uint32_t w0 = (uint32_t)v, w1 = (uint32_t)(v >> 32);
+    if (ROT) { w0 = __builtin_amdgcn_alignbyte(w0, w0, rot); w1 = __builtin_amdgcn_alignbyte(w1, w1, rot); }
+    uint32_t *oo = o + (int64_t)k * a4_bs;
+    oo[0]     = w0;
+    oo[crows] = w1;
+  });
 }
 
 // The same pass with the seven top-level products of a word meeting in LDS instead of in HBM: a workgroup owns 32 word positions,
@@ -1128,7 +1036,7 @@ __global__ __launch_bounds__(AUX_THREADS) void winograd_down4_pack_lds_kernel(
 // writes 3.5 x the result (every atomic reaches HBM) on top of the clear.
 constexpr int U4_POS = 32;
 
-template <bool ACC, bool NT>
+template <bool ACC>
 __global__ __launch_bounds__(AUX_THREADS) void winograd_up4_lds_kernel(
     const word *__restrict__ prod, int64_t p_bs,  // 2401 products per ancestor, stride == cw
     word *anc, int64_t o_stride, int64_t o_bs,    // ancestor array
@@ -1147,9 +1055,11 @@ __global__ __launch_bounds__(AUX_THREADS) void winograd_up4_lds_kernel(
 #pragma unroll
       for (int b = 0; b < 8; ++b) out[a][b] = 0;
     word buf[2][7];
-    auto load_group = [&](int g, word (&dst)[7]) {
+    // (the fold is written out here and in winograd_up4_kernel: as one shared inline function it compiles to 336 instead of 202 VGPRs
+    // there and 222 instead of 208 here)
+    auto load_group = [&](int g, word (&dst)[7]) {   // nontemporal: every product is read once (see winograd_up3_kernel)
 #pragma unroll
-      for (int j3 = 0; j3 < 7; ++j3) dst[j3] = NT ? __builtin_nontemporal_load(&q[(int64_t)(7 * g + j3) * p_bs]) : q[(int64_t)(7 * g + j3) * p_bs];
+      for (int j3 = 0; j3 < 7; ++j3) dst[j3] = __builtin_nontemporal_load(&q[(int64_t)(7 * g + j3) * p_bs]);
     };
     load_group(0, buf[0]);
 #pragma unroll
@@ -1208,66 +1118,6 @@ __global__ __launch_bounds__(AUX_THREADS) void winograd_up4_lds_kernel(
     *oo           = ACC ? (*oo ^ v) : v;
   }
 }
-
-template <int ROT, bool NT>
-__global__ __launch_bounds__(DP3_THREADS) void winograd_down4_pack_kernel(
-    const word *__restrict__ anc, int64_t p_stride, int64_t p_bs,
-    uint32_t *__restrict__ a4, int64_t a4_bs,                       // packed descendants, a4_bs dwords each
-    int64_t crows, int64_t cw, int64_t tiles_r, int64_t tiles_w) {
-  __shared__ __attribute__((aligned(16))) uint32_t tile[2][7 * DP3_ROWS * DP3_PITCH];  // two sets of seven 4 KiB tiles
-  int64_t tb_;
-  int j0;
-  pass4_block(blockIdx.x, tb_, j0);
-  if (tb_ >= tiles_r * tiles_w) return;   // (whole workgroups leave: no barrier is missed)
-  const int64_t wt = tb_ % tiles_w, rt = tb_ / tiles_w, pi = blockIdx.y;
-  const int t = threadIdx.x, r = t >> 4, v = t & 15;
-  const word *p = anc + pi * p_bs + (rt * DP3_ROWS + r) * p_stride + (wt * DP3_W + v);
-  word x[8][8];
-#pragma unroll
-  for (int a = 0; a < 8; ++a)
-#pragma unroll
-    for (int b = 0; b < 8; ++b) x[a][b] = load_top_child<false>(p + (int64_t)a * crows * p_stride + (int64_t)b * cw, 8 * crows * p_stride, 8 * cw, j0);
-  const int q = t >> 4, r2 = (t & 15) * 2;
-  const int64_t orow = rt * DP3_ROWS + r2;
-  const uint32_t rot = ROT == 1 ? (uint32_t)((orow >> 6) & 3) : ROT == 2 ? (uint32_t)((orow >> 7) & 3) : 0u;
-  const int64_t oq   = (wt * (DP3_W * 2) + q) ^ (ROT == 2 ? ((orow >> 5) & 1) : 0);
-  uint32_t *o = a4 + (pi * 2401 + 343 * j0) * a4_bs + oq * crows + orow;
-#pragma unroll
-  for (int j1 = 0; j1 < 7; ++j1) {
-    word c1[4][4];
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-      for (int b = 0; b < 4; ++b) c1[a][b] = winograd_child<word, false>(x[a][b], x[a][b + 4], x[a + 4][b], x[a + 4][b + 4], j1);
-#pragma unroll
-    for (int j2 = 0; j2 < 7; ++j2) {
-      word c2[2][2];
-#pragma unroll
-      for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b) c2[a][b] = winograd_child<word, false>(c1[a][b], c1[a][b + 2], c1[a + 2][b], c1[a + 2][b + 2], j2);
-      // the seven outputs of (j1, j2) go through seven tiles of one of two sets and ONE barrier: the other set is only rewritten after the
-      // next barrier, when every thread has read this one (49 barriers per workgroup instead of 343: with one 512-thread workgroup per
-      // CU a barrier per 4 KiB of output was a visible part of the pass)
-      uint32_t *set = tile[(7 * j1 + j2) & 1];
-#pragma unroll
-      for (int j3 = 0; j3 < 7; ++j3)
-        *reinterpret_cast<word *>(set + j3 * (DP3_ROWS * DP3_PITCH) + r * DP3_PITCH + 2 * (v ^ ((r >> 1) & 15))) =
-            winograd_child<word, false>(c2[0][0], c2[0][1], c2[1][0], c2[1][1], j3);
-      __syncthreads();
-      const int rs = 2 * ((q >> 1) ^ ((r2 >> 1) & 15)) + (q & 1);  // rows r2 and r2 + 1 share the swizzle
-#pragma unroll
-      for (int j3 = 0; j3 < 7; ++j3) {
-        const int k        = 49 * j1 + 7 * j2 + j3;
-        const uint32_t *tb = set + j3 * (DP3_ROWS * DP3_PITCH);
-        uint32_t w0 = tb[(r2 + 0) * DP3_PITCH + rs], w1 = tb[(r2 + 1) * DP3_PITCH + rs];
-        if (ROT) { w0 = __builtin_amdgcn_alignbyte(w0, w0, rot); w1 = __builtin_amdgcn_alignbyte(w1, w1, rot); }
-        if (NT) __builtin_nontemporal_store((unsigned long long)w0 | ((unsigned long long)w1 << 32), reinterpret_cast<unsigned long long *>(o + (int64_t)k * a4_bs));
-        else *reinterpret_cast<uint2 *>(o + (int64_t)k * a4_bs) = make_uint2(w0, w1);
-      }
-    }
-  }
-}
 }  // namespace
 
 // Descendant 343 * j0 + 49 * j1 + 7 * j2 + j3 of ancestor i is stored at index 2401 * i + that; descendants are crows x cw words,
@@ -1276,43 +1126,37 @@ static hipError_t gf2_launch_winograd_down4(hipStream_t s, int bside, const word
                                             word *gchild, int64_t nparents, int64_t crows, int64_t cw) {
   const int64_t c_bs = crows * cw;
   if (nparents * c_bs == 0) return hipSuccess;
-  // the form that reads the ancestor once through LDS needs the 32 positions of a workgroup inside one descendant row: 0.92 ms against
-  // 1.26 ... 1.38 ms for the B side of 65536^3 (M4RI_AMD_DOWN4=direct selects the other form, for measurements)
-  static const bool want_lds = !(getenv("M4RI_AMD_DOWN4") && getenv("M4RI_AMD_DOWN4")[0] == 'd');
-  if (want_lds && cw % 32 == 0 && c_bs / 32 <= 0x7fffffffLL && nparents <= 65535) {
+  // the form that reads the ancestor once through LDS wherever the 32 positions of a workgroup lie inside one descendant row: 0.92 ms
+  // against 1.26 ... 1.38 ms of the direct form for the B side of 65536^3.  Other widths take the direct form
+  if (cw % 32 == 0 && c_bs / 32 <= 0x7fffffffLL && nparents <= 65535) {
     const dim3 g((unsigned)(c_bs / 32), (unsigned)nparents);
-#define D4L_LAUNCH(BS, NT) hipLaunchKernelGGL((winograd_down4_lds_kernel<BS, NT>), g, dim3(AUX_THREADS), 0, s, anc, p_stride, p_bs, gchild, c_bs, crows, cw)
-    if (pass_nt() & 1) { if (bside) D4L_LAUNCH(true, true); else D4L_LAUNCH(false, true); }
-    else { if (bside) D4L_LAUNCH(true, false); else D4L_LAUNCH(false, false); }
-#undef D4L_LAUNCH
+    with_bool(bside, [&](auto BS) {
+      hipLaunchKernelGGL((winograd_down4_lds_kernel<decltype(BS)::value>), g, dim3(AUX_THREADS), 0, s, anc, p_stride, p_bs, gchild, c_bs, crows, cw);
+    });
     return hipGetLastError();
   }
   const int64_t nposblocks = (c_bs + AUX_THREADS - 1) / AUX_THREADS, grid = pass4_grid(nposblocks);
   if (grid > 0x7fffffffLL || nparents > 65535) return hipErrorInvalidValue;
-#define D4_LAUNCH(BS, NT)                                                                                                             \
-  hipLaunchKernelGGL((winograd_down4_kernel<BS, NT>), dim3((unsigned)grid, (unsigned)nparents), dim3(AUX_THREADS), 0, s, anc, p_stride, p_bs, gchild, \
-                     c_bs, crows, cw, nposblocks)
-  if (pass_nt() & 1) { if (bside) D4_LAUNCH(true, true); else D4_LAUNCH(false, true); }
-  else { if (bside) D4_LAUNCH(true, false); else D4_LAUNCH(false, false); }
-#undef D4_LAUNCH
+  with_bool(bside, [&](auto BS) {
+    hipLaunchKernelGGL((winograd_down4_kernel<decltype(BS)::value>), dim3((unsigned)grid, (unsigned)nparents), dim3(AUX_THREADS), 0, s, anc, p_stride,
+                       p_bs, gchild, c_bs, crows, cw, nposblocks);
+  });
   return hipGetLastError();
 }
 
-// anc (+)= the recombination of the 2401 products per ancestor.  acc == 0: the ancestor's 16 crows x 16 cw words are zeroed first (the
-// seven top-level products of a word meet in it by atomic XOR); acc != 0: they are added onto what is there.
+// anc (+)= the recombination of the 2401 products per ancestor.  In the atomic form, acc == 0: the ancestor's 16 crows x 16 cw words are
+// zeroed first (the seven top-level products of a word meet in it by atomic XOR); acc != 0: they are added onto what is there.
 static hipError_t gf2_launch_winograd_up4(hipStream_t s, int acc, const word *prod, word *anc, int64_t o_stride, int64_t o_bs,
                                           int64_t nparents, int64_t crows, int64_t cw) {
   const int64_t p_bs = crows * cw;
   if (nparents * p_bs == 0) return hipSuccess;
-  // the form that combines the seven top-level products in LDS needs the 32 positions of a workgroup inside one row
-  // (M4RI_AMD_UP4=atomic selects the other form: products meeting in HBM by atomic XOR, for measurements)
-  static const bool want_lds = !(getenv("M4RI_AMD_UP4") && getenv("M4RI_AMD_UP4")[0] == 'a');
-  if (want_lds && cw % U4_POS == 0 && p_bs / U4_POS <= 0x7fffffffLL && nparents <= 65535) {
+  // the form that combines the seven top-level products in LDS wherever the 32 positions of a workgroup lie inside one row; other
+  // widths take the form whose products meet in HBM by atomic XOR
+  if (cw % U4_POS == 0 && p_bs / U4_POS <= 0x7fffffffLL && nparents <= 65535) {
     const dim3 g((unsigned)(p_bs / U4_POS), (unsigned)nparents);
-#define U4L_LAUNCH(AC, NT) hipLaunchKernelGGL((winograd_up4_lds_kernel<AC, NT>), g, dim3(AUX_THREADS), 0, s, prod, p_bs, anc, o_stride, o_bs, crows, cw)
-    if (pass_nt() & 2) { if (acc) U4L_LAUNCH(true, true); else U4L_LAUNCH(false, true); }
-    else { if (acc) U4L_LAUNCH(true, false); else U4L_LAUNCH(false, false); }
-#undef U4L_LAUNCH
+    with_bool(acc, [&](auto ACC) {
+      hipLaunchKernelGGL((winograd_up4_lds_kernel<decltype(ACC)::value>), g, dim3(AUX_THREADS), 0, s, prod, p_bs, anc, o_stride, o_bs, crows, cw);
+    });
     return hipGetLastError();
   }
   const int64_t nposblocks = (p_bs + AUX_THREADS - 1) / AUX_THREADS, grid = pass4_grid(nposblocks);
@@ -1322,42 +1166,24 @@ static hipError_t gf2_launch_winograd_up4(hipStream_t s, int acc, const word *pr
       const hipError_t e = gf2_launch_rowwise(s, 2, anc + i * o_bs, o_stride, nullptr, 0, nullptr, 0, 16 * crows, 16 * cw);
       if (e != hipSuccess) return e;
     }
-  if (pass_nt() & 2)
-    hipLaunchKernelGGL((winograd_up4_kernel<true>), dim3((unsigned)grid, (unsigned)nparents), dim3(AUX_THREADS), 0, s, prod, p_bs, anc, o_stride, o_bs, crows,
-                       cw, nposblocks);
-  else
-    hipLaunchKernelGGL((winograd_up4_kernel<false>), dim3((unsigned)grid, (unsigned)nparents), dim3(AUX_THREADS), 0, s, prod, p_bs, anc, o_stride, o_bs, crows,
-                       cw, nposblocks);
+  hipLaunchKernelGGL(winograd_up4_kernel, dim3((unsigned)grid, (unsigned)nparents), dim3(AUX_THREADS), 0, s, prod, p_bs, anc, o_stride, o_bs, crows, cw,
+                     nposblocks);
   return hipGetLastError();
 }
 
 static hipError_t gf2_launch_winograd_down4_pack(hipStream_t s, const word *anc, int64_t p_stride, int64_t p_bs, word *a4,
                                                  int64_t nparents, int64_t crows, int64_t cw, int rot) {
   if (nparents * crows * cw == 0) return hipSuccess;
-  if (!gf2_winograd_down3_pack_ok(a4, crows, cw)) return hipErrorInvalidValue;
-  // the form without the transpose (one word column x 32 rows per workgroup, the grid through LDS) wherever the shape allows it:
-  // 1.13 against 1.33 ms at 65536^3; M4RI_AMD_DOWN4_PACK=transpose keeps the other
-  static const bool want_lds = !(getenv("M4RI_AMD_DOWN4_PACK") && getenv("M4RI_AMD_DOWN4_PACK")[0] == 't');
-  if (want_lds && rot != 2 && crows % 32 == 0 && cw % 16 == 0 && nparents <= 65535) {
-    const int64_t groups = ((crows / 32 + 7) / 8) * (cw / 16);
-    if (groups * 128 <= 0x7fffffffLL) {
-      const dim3 g((unsigned)(groups * 128), (unsigned)nparents);
-#define DP4L_LAUNCH(R, NT) hipLaunchKernelGGL((winograd_down4_pack_lds_kernel<R, NT>), g, dim3(AUX_THREADS), 0, s, anc, p_stride, p_bs, reinterpret_cast<uint32_t *>(a4), crows * cw * 2, crows, cw)
-      if (pass_nt() & 4) { if (rot == 1) DP4L_LAUNCH(1, true); else DP4L_LAUNCH(0, true); }
-      else { if (rot == 1) DP4L_LAUNCH(1, false); else DP4L_LAUNCH(0, false); }
-#undef DP4L_LAUNCH
-      return hipGetLastError();
-    }
-  }
-  const int64_t tiles_r = crows / DP3_ROWS, tiles_w = cw / DP3_W;
-  const int64_t grid = pass4_grid(tiles_r * tiles_w);
-  if (grid > 0x7fffffffLL || nparents > 65535) return hipErrorInvalidValue;
-#define DP4_LAUNCH(R, NT)                                                                                                                     \
-  hipLaunchKernelGGL((winograd_down4_pack_kernel<R, NT>), dim3((unsigned)grid, (unsigned)nparents), dim3(DP3_THREADS), 0, s, anc, p_stride, p_bs, \
-                     reinterpret_cast<uint32_t *>(a4), crows * cw * 2, crows, cw, tiles_r, tiles_w)
-  if (pass_nt() & 4) { if (rot == 2) DP4_LAUNCH(2, true); else if (rot == 1) DP4_LAUNCH(1, true); else DP4_LAUNCH(0, true); }
-  else { if (rot == 2) DP4_LAUNCH(2, false); else if (rot == 1) DP4_LAUNCH(1, false); else DP4_LAUNCH(0, false); }
-#undef DP4_LAUNCH
+  // one form, without a transpose (one word column x 32 rows per workgroup, the grid through LDS): 1.13 ms at 65536^3 against 1.33 ms
+  // of a form that tiled and transposed like the three-level pack pass.  Its shape rule is gf2_winograd_down3_pack_ok's
+  if (!gf2_winograd_down3_pack_ok(a4, crows, cw) || nparents > 65535) return hipErrorInvalidValue;
+  const int64_t groups = ((crows / 32 + 7) / 8) * (cw / 16);
+  if (groups * 128 > 0x7fffffffLL) return hipErrorInvalidValue;
+  const dim3 g((unsigned)(groups * 128), (unsigned)nparents);
+  with_bool(rot == 1, [&](auto ROT) {
+    hipLaunchKernelGGL((winograd_down4_pack_lds_kernel<decltype(ROT)::value>), g, dim3(AUX_THREADS), 0, s, anc, p_stride, p_bs,
+                       reinterpret_cast<uint32_t *>(a4), crows * cw * 2, crows, cw);
+  });
   return hipGetLastError();
 }
 
@@ -1368,25 +1194,17 @@ static hipError_t gf2_launch_winograd_down2(hipStream_t s, int bside, const word
                                             int64_t p_bs, word *gchild, int64_t nparents, int64_t crows, int64_t cw) {
   const int64_t c_bs = crows * cw;
   if (nparents * c_bs == 0) return hipSuccess;
-  if (vec_ok(gparent, p_stride, p_bs, cw, cw) && vec_ok(gchild, cw, c_bs, cw, cw)) {
-    const int64_t total = nparents * crows * (cw / 2);
-    if (bside)
-      hipLaunchKernelGGL((winograd_down2_kernel<word2, true>), dim3(grid_for(total)), dim3(AUX_THREADS), 0, s,
-                         reinterpret_cast<const word2 *>(gparent), p_stride / 2, p_bs / 2, reinterpret_cast<word2 *>(gchild),
-                         c_bs / 2, nparents, crows, cw / 2);
-    else
-      hipLaunchKernelGGL((winograd_down2_kernel<word2, false>), dim3(grid_for(total)), dim3(AUX_THREADS), 0, s,
-                         reinterpret_cast<const word2 *>(gparent), p_stride / 2, p_bs / 2, reinterpret_cast<word2 *>(gchild),
-                         c_bs / 2, nparents, crows, cw / 2);
-  } else {
-    const int64_t total = nparents * crows * cw;
-    if (bside)
-      hipLaunchKernelGGL((winograd_down2_kernel<word, true>), dim3(grid_for(total)), dim3(AUX_THREADS), 0, s, gparent,
-                         p_stride, p_bs, gchild, c_bs, nparents, crows, cw);
-    else
-      hipLaunchKernelGGL((winograd_down2_kernel<word, false>), dim3(grid_for(total)), dim3(AUX_THREADS), 0, s, gparent,
-                         p_stride, p_bs, gchild, c_bs, nparents, crows, cw);
-  }
+  with_bool(vec_ok(gparent, p_stride, p_bs, cw, cw) && vec_ok(gchild, cw, c_bs, cw, cw), [&](auto VEC) {
+    using V = lane_t<decltype(VEC)>;
+    constexpr int64_t per = sizeof(V) / sizeof(word);
+    const V *src = reinterpret_cast<const V *>(gparent);
+    V *dst       = reinterpret_cast<V *>(gchild);
+    const int64_t w = cw / per;
+    with_bool(bside, [&](auto BS) {
+      hipLaunchKernelGGL((winograd_down2_kernel<V, decltype(BS)::value>), dim3(grid_for(nparents * crows * w)), dim3(AUX_THREADS), 0, s, src,
+                         p_stride / per, p_bs / per, dst, c_bs / per, nparents, crows, w);
+    });
+  });
   return hipGetLastError();
 }
 
@@ -1394,25 +1212,17 @@ static hipError_t gf2_launch_winograd_up2(hipStream_t s, int acc, const word *pr
                                           int64_t o_bs, int64_t nparents, int64_t crows, int64_t cw) {
   const int64_t p_bs = crows * cw;
   if (nparents * p_bs == 0) return hipSuccess;
-  if (vec_ok(prod, cw, p_bs, cw, cw) && vec_ok(gparent, o_stride, o_bs, cw, cw)) {
-    const int64_t total = nparents * crows * (cw / 2);
-    if (acc)
-      hipLaunchKernelGGL((winograd_up2_kernel<word2, true>), dim3(grid_for(total)), dim3(AUX_THREADS), 0, s,
-                         reinterpret_cast<const word2 *>(prod), p_bs / 2, reinterpret_cast<word2 *>(gparent), o_stride / 2,
-                         o_bs / 2, nparents, crows, cw / 2);
-    else
-      hipLaunchKernelGGL((winograd_up2_kernel<word2, false>), dim3(grid_for(total)), dim3(AUX_THREADS), 0, s,
-                         reinterpret_cast<const word2 *>(prod), p_bs / 2, reinterpret_cast<word2 *>(gparent), o_stride / 2,
-                         o_bs / 2, nparents, crows, cw / 2);
-  } else {
-    const int64_t total = nparents * crows * cw;
-    if (acc)
-      hipLaunchKernelGGL((winograd_up2_kernel<word, true>), dim3(grid_for(total)), dim3(AUX_THREADS), 0, s, prod, p_bs,
-                         gparent, o_stride, o_bs, nparents, crows, cw);
-    else
-      hipLaunchKernelGGL((winograd_up2_kernel<word, false>), dim3(grid_for(total)), dim3(AUX_THREADS), 0, s, prod, p_bs,
-                         gparent, o_stride, o_bs, nparents, crows, cw);
-  }
+  with_bool(vec_ok(prod, cw, p_bs, cw, cw) && vec_ok(gparent, o_stride, o_bs, cw, cw), [&](auto VEC) {
+    using V = lane_t<decltype(VEC)>;
+    constexpr int64_t per = sizeof(V) / sizeof(word);
+    const V *src = reinterpret_cast<const V *>(prod);
+    V *dst       = reinterpret_cast<V *>(gparent);
+    const int64_t w = cw / per;
+    with_bool(acc, [&](auto ACC) {
+      hipLaunchKernelGGL((winograd_up2_kernel<V, decltype(ACC)::value>), dim3(grid_for(nparents * crows * w)), dim3(AUX_THREADS), 0, s, src,
+                         p_bs / per, dst, o_stride / per, o_bs / per, nparents, crows, w);
+    });
+  });
   return hipGetLastError();
 }
 
@@ -1437,6 +1247,7 @@ extern "C" int gf2_pass_down_pack_ok(int levels, const word *src, int64_t stride
 extern "C" hipError_t gf2_launch_pass_down_pack(hipStream_t s, int levels, int scheme, const word *src, int64_t stride, int64_t bs,
                                                 word *a4, int64_t nparents, int64_t crows, int64_t cw, int rot) {
   if (scheme) return gf2_launch_scheme_down_pack(s, levels, src, stride, bs, a4, nparents, crows, cw);
+  if (rot != 0 && rot != 1) return hipErrorInvalidValue;
   switch (levels) {
     case 4: return gf2_launch_winograd_down4_pack(s, src, stride, bs, a4, nparents, crows, cw, rot);
     case 3: return gf2_launch_winograd_down3_pack(s, src, stride, bs, a4, nparents, crows, cw, rot);

@@ -7,6 +7,7 @@
 // map lists only include/m4ri_amd.h).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <type_traits>
 #include "gf2_common.h"
 
 // return the HIP error of `expr` (a hipError_t or an int status) from the enclosing int-returning function
@@ -15,6 +16,15 @@
     hipError_t e_ = (hipError_t)(expr);               \
     if (e_ != hipSuccess) return (int)e_;             \
   } while (0)
+
+// A run-time flag as a template argument: calls f(std::true_type{}) or f(std::false_type{}).  With a generic lambda,
+//   with_bool(acc, [&](auto ACC) { hipLaunchKernelGGL((kernel<decltype(ACC)::value>), ...); });
+// instantiates and launches the kernel for both values of the flag from one launch statement.  The launchers nest it for two flags.
+template <typename F>
+inline void with_bool(bool flag, F &&f) {
+  if (flag) f(std::true_type{});
+  else f(std::false_type{});
+}
 
 extern "C" {
 
@@ -36,8 +46,9 @@ hipError_t gf2_launch_m4rm8q(hipStream_t stream, LeafArgs a, word *a4_ws);
 // levels 1 ... 4 through the Winograd passes, or (scheme != 0, levels 2 ... 4) through the rank-R scheme of the 4 x 4 x 4 block
 // product (scheme_passes.hip).  Down: nparents parents of 2^levels crows rows x 2^levels cw words (row stride `stride`, `bs` words
 // apart) -> their descendants, crows x cw words each, back to back; bside selects the B side's operand sums.  Down_pack: the A side
-// written straight into generation 4's packed form at a4 (rot: the Winograd passes' index-byte rotation).  Up: the products back
-// into the parents (acc != 0: added onto them).
+// written straight into generation 4's packed form at a4.  rot: the index-byte rotation of the Winograd passes, 0 (plain chunk-major) or 1
+// (generation 4's); with any other value they return hipErrorInvalidValue and write nothing.  The scheme passes ignore rot (they always
+// write generation 4's rotation).  Up: the products back into the parents (acc != 0: added onto them).
 hipError_t gf2_launch_pass_down(hipStream_t s, int levels, int scheme, int bside, const word *src, int64_t stride, int64_t bs, word *dst,
                                 int64_t nparents, int64_t crows, int64_t cw);
 hipError_t gf2_launch_pass_down_pack(hipStream_t s, int levels, int scheme, const word *src, int64_t stride, int64_t bs, word *a4,

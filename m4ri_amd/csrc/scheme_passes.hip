@@ -244,12 +244,14 @@ extern "C" int gf2_scheme444_ok(int levels, int64_t a_rows, int64_t a_cw, int64_
   return 1;
 }
 
-#define SP_DISPATCH(LEVELS, CALL4, CALL2, CALL1) \
-  do {                                           \
-    if ((LEVELS) == 4) { CALL4; }                \
-    else if ((LEVELS) == 3) { CALL2; }           \
-    else { CALL1; }                              \
-  } while (0)
+// The inner grid G of a `levels`-level pass (levels 2 ... 4: 1, 2, 4) as a template argument, the way with_bool hands over a flag:
+// f(std::integral_constant<int, G>{}).  The launchers derive the positions and units of a workgroup from it.
+template <typename F>
+static void with_inner_grid(int levels, F &&f) {
+  if (levels == 4) f(std::integral_constant<int, 4>{});
+  else if (levels == 3) f(std::integral_constant<int, 2>{});
+  else f(std::integral_constant<int, 1>{});
+}
 
 // Descendant r1 * R + r2 of ancestor i is stored at index leaves * i + that; descendants are crows x cw words, contiguous; an ancestor is
 // 2^levels * crows rows x 2^levels * cw words with row stride p_stride.
@@ -266,10 +268,12 @@ extern "C" hipError_t gf2_launch_scheme_down(hipStream_t s, int levels, int bsid
     const word *an = anc + p0 * p_bs;
     word *ch       = child + p0 * leaves * c_bs;
     const dim3 g((unsigned)(c_bs / 64), (unsigned)np);
-#define L_(G, T, BS) hipLaunchKernelGGL((scheme_down_kernel<G, 64, T / 64, BS>), g, dim3(T), 0, s, an, p_stride, p_bs, ch, c_bs, crows, cw, o)
-    if (bside) SP_DISPATCH(levels, L_(4, 512, true), L_(2, 448, true), L_(1, 64, true));
-    else SP_DISPATCH(levels, L_(4, 512, false), L_(2, 448, false), L_(1, 64, false));
-#undef L_
+    with_inner_grid(levels, [&](auto G_) {
+      constexpr int G = decltype(G_)::value, UNITS = G == 4 ? 8 : G == 2 ? 7 : 1;   // 512, 448, 64 threads
+      with_bool(bside, [&](auto BS) {
+        hipLaunchKernelGGL((scheme_down_kernel<G, 64, UNITS, decltype(BS)::value>), g, dim3(64 * UNITS), 0, s, an, p_stride, p_bs, ch, c_bs, crows, cw, o);
+      });
+    });
   }
   return hipGetLastError();
 }
@@ -288,9 +292,10 @@ extern "C" hipError_t gf2_launch_scheme_down_pack(hipStream_t s, int levels, con
     const word *an = anc + p0 * p_bs;
     uint32_t *pk   = reinterpret_cast<uint32_t *>(a4) + p0 * leaves * crows * cw * 2;
     const dim3 g((unsigned)(groups * 128), (unsigned)np);
-#define L_(G, P, T) hipLaunchKernelGGL((scheme_down_pack_kernel<G, P, T / P>), g, dim3(T), 0, s, an, p_stride, p_bs, pk, crows * cw * 2, crows, cw, o)
-    SP_DISPATCH(levels, L_(4, 32, 256), L_(2, 32, 256), L_(1, 64, 64));
-#undef L_
+    with_inner_grid(levels, [&](auto G_) {
+      constexpr int G = decltype(G_)::value, POS = G == 1 ? 64 : 32, UNITS = G == 1 ? 1 : 8;   // 64 or 256 threads
+      hipLaunchKernelGGL((scheme_down_pack_kernel<G, POS, UNITS>), g, dim3(POS * UNITS), 0, s, an, p_stride, p_bs, pk, crows * cw * 2, crows, cw, o);
+    });
   }
   return hipGetLastError();
 }
@@ -309,10 +314,12 @@ extern "C" hipError_t gf2_launch_scheme_up(hipStream_t s, int levels, int acc, c
     const word *pr = prod + p0 * leaves * p_bs;
     word *an       = anc + p0 * o_bs;
     const dim3 g((unsigned)(p_bs / pos), (unsigned)np);
-#define L_(G, P, T, AC) hipLaunchKernelGGL((scheme_up_kernel<G, P, T / P, AC>), g, dim3(T), 0, s, pr, p_bs, an, o_stride, o_bs, crows, cw, o)
-    if (acc) SP_DISPATCH(levels, L_(4, 32, 256, true), L_(2, 32, 256, true), L_(1, 64, 64, true));
-    else SP_DISPATCH(levels, L_(4, 32, 256, false), L_(2, 32, 256, false), L_(1, 64, 64, false));
-#undef L_
+    with_inner_grid(levels, [&](auto G_) {
+      constexpr int G = decltype(G_)::value, POS = G == 1 ? 64 : 32, UNITS = G == 1 ? 1 : 8;   // 64 or 256 threads
+      with_bool(acc, [&](auto ACC) {
+        hipLaunchKernelGGL((scheme_up_kernel<G, POS, UNITS, decltype(ACC)::value>), g, dim3(POS * UNITS), 0, s, pr, p_bs, an, o_stride, o_bs, crows, cw, o);
+      });
+    });
   }
   return hipGetLastError();
 }

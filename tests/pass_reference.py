@@ -22,8 +22,8 @@ descendants are crows x cw words each, contiguous, descendant d of parent i at i
     followed by the scheme on each of its children: leaf (r1, r2) at index r1 * R + r2.
   * Packed A: descendant d as 32-bit dwords, chunk-major: dword q of row r at a4[d * (2 crows cw) + q * m_pad + r] (m_pad = crows in a
     pass), rows m .. m_pad - 1 zero; for rot = 1 every dword rotated right by 8 * ((r >> 6) & 3) bits, i.e. byte i of what is stored is
-    byte (i + (r >> 6)) & 3 of the plain dword (v_alignbyte_b32 of the dword with itself).  rot = 2 (a retired leaf's rotation + chunk
-    swap) has no caller in the library -- engine.hip passes 0 or 1 -- and is left out here and in the tests.
+    byte (i + (r >> 6)) & 3 of the plain dword (v_alignbyte_b32 of the dword with itself).  The pass launchers take rot 0 or 1 and refuse every
+    other value (engine.hip passes 0 or 1).
 """
 from __future__ import annotations
 
@@ -207,7 +207,7 @@ def _rotr_bytes(v: np.ndarray, s: np.ndarray) -> np.ndarray:
 def pack_a4(D: np.ndarray, rot: int, m_pad: int | None = None) -> np.ndarray:
     """(N, m, w) uint64 matrices -> (N, 2 w, m_pad) uint32: dword q of row r at [n, q, r], rows m .. m_pad - 1 zero; rot = 1: each dword
     rotated right by 8 * ((r >> 6) & 3) bits."""
-    assert rot in (0, 1), "rot = 2 has no caller in the library and no reference here"
+    assert rot in (0, 1), "the pass launchers take rot 0 or 1 only"
     N, m, w = D.shape
     m_pad = m if m_pad is None else m_pad
     dw = np.ascontiguousarray(D).view("<u4").reshape(N, m, 2 * w)     # dword 2 k = low half of word k

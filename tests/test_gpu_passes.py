@@ -13,14 +13,12 @@ reached through the test-only library tests/pass_lib.py binds.  Every case check
     acc = 1 onto random content;
   * the launcher's answer: success, or hipErrorInvalidValue for a shape it documents as not taken -- and then nothing written.
 
-ROWS below is the parameter table as data: per row the kernel instantiation it is meant to reach in a process without switches (`reach`),
-the launcher's condition that routes there (`why`) and what it reaches instead under each switch (`alt`).  The switches
-M4RI_AMD_PASS_NT, M4RI_AMD_UP4, M4RI_AMD_DOWN4, M4RI_AMD_DOWN4_PACK are read once per process, so test_forms_behind_a_switch re-runs the
-rows a setting re-routes in one child process per setting, one at a time.  `python tools/pass_coverage.py` prints the table and compares
-it with the kernel names of rocprofv3 traces of those processes (profiles/passes_kernel_coverage.txt).
+ROWS below is the parameter table as data: per row the kernel instantiation it is meant to reach (`reach`) and the launcher's condition
+that routes there (`why`).  The shape and the flags alone select the form, so one process reaches every instantiation.
+`python tools/pass_coverage.py` prints the table and compares it with the kernel names of a rocprofv3 trace of this module
+(profiles/passes_kernel_coverage.txt).
 
 Not in scope:
-  * rot = 2 of the pack passes: no caller in the library (engine.hip passes 0 or 1);
   * the nparents > 65535 loop of the scheme launchers and the matching refusal of the four-level Winograd launchers: the smallest legal
     case writes tens of GiB, and what that costs on a shared machine has not been measured.  Its argument arithmetic (p0 * p_bs,
     p0 * leaves * c_bs) is checked by reading only;
@@ -31,9 +29,7 @@ Not in scope:
   * nparents = 50 at four levels is run on the small leaf shapes only (the packed forms take up to 7 parents there: 50 would be 0.5 GiB).
 """
 import os
-import re
 import subprocess
-import sys
 from collections import namedtuple
 
 import numpy as np
@@ -45,26 +41,19 @@ import pass_reference as ref
 
 GUARD = 32            # words of poison before and after every destination (a multiple of 2: the base stays 16-byte aligned)
 POISON = np.uint64(0xFFFFFFFFFFFFFFFF)
-SWITCHES = ("M4RI_AMD_PASS_NT", "M4RI_AMD_UP4", "M4RI_AMD_DOWN4", "M4RI_AMD_DOWN4_PACK")
 
 # op: "down" (flag = bside), "pack" (flag = rot), "up" (flag = acc).  soff / doff: word offset of the source / destination base pointer
 # (1: only 8-byte aligned).  spad: words of row padding of the ancestor (stride = 2^L cw + spad).  gap: words between parents beyond
 # rows * stride; None: bs = 0 (one parent, what multi.hip and engine.hip pass for a single product).  rc: the launcher's answer.
-Row = namedtuple("Row", "kind L op flag crows cw np soff doff spad gap rc reach why alt tags")
-
-NT7, NT0 = "M4RI_AMD_PASS_NT=7", "M4RI_AMD_PASS_NT=0"
-UP4A, DOWN4D, PACK4T = "M4RI_AMD_UP4=atomic", "M4RI_AMD_DOWN4=direct", "M4RI_AMD_DOWN4_PACK=transpose"
-PACK4T_NT7 = PACK4T + " " + NT7
-# setting -> the tag of the rows it re-routes
-SETTINGS = {NT0: "swnt0", NT7: "swnt7", UP4A: "swup4", DOWN4D: "swdown4", PACK4T: "swpack4", PACK4T_NT7: "swpack4"}
+Row = namedtuple("Row", "kind L op flag crows cw np soff doff spad gap rc reach why")
 
 
 def _b(x):
     return "true" if x else "false"
 
 
-def _row(kind, L, op, flag, crows, cw, np_, soff=0, doff=0, spad=0, gap=0, rc=0, reach="", why="", alt=None, tags=()):
-    return Row(kind, L, op, flag, crows, cw, np_, soff, doff, spad, gap, rc, reach, why, dict(alt or {}), tuple(tags))
+def _row(kind, L, op, flag, crows, cw, np_, soff=0, doff=0, spad=0, gap=0, rc=0, reach="", why=""):
+    return Row(kind, L, op, flag, crows, cw, np_, soff, doff, spad, gap, rc, reach, why)
 
 
 # ---- one and two Winograd levels: word2 where vec_ok() holds on both sides, the scalar instantiation otherwise --------------------------
@@ -113,16 +102,13 @@ def _winograd_pack_rows():
         # three levels: crows % 32 == 0 && cw % 16 == 0 (any source alignment)
         for (crows, cw, np_, soff, doff, spad, gap) in ((32, 16, 1, 0, 0, 0, None), (64, 32, 2, 1, 0, 1, 1), (96, 16, 7, 0, 0, 0, 0), (288, 16, 1, 0, 0, 0, 0),
                                                         (32, 48, 2, 0, 0, 2, 0), (32, 16, 50, 0, 0, 0, 0)):
-            rows.append(_row("w", 3, "pack", rot, crows, cw, np_, soff, doff, spad, gap, 0, f"winograd_down3_pack_kernel<{rot},false>",
-                             "down3_pack_ok: crows % DP3_ROWS == 0, cw % DP3_W == 0" + ("; 8-byte source, odd stride and bs" if soff else ""),
-                             {NT7: f"winograd_down3_pack_kernel<{rot},true>"}, ("swnt7",)))
-        # four levels: the same rule; the form without the transpose unless M4RI_AMD_DOWN4_PACK=transpose
+            rows.append(_row("w", 3, "pack", rot, crows, cw, np_, soff, doff, spad, gap, 0, f"winograd_down3_pack_kernel<{rot}>",
+                             "down3_pack_ok: crows % DP3_ROWS == 0, cw % DP3_W == 0" + ("; 8-byte source, odd stride and bs" if soff else "")))
+        # four levels: the same rule (the form without the transpose is the only one)
         for (crows, cw, np_, soff, doff, spad, gap) in ((32, 16, 1, 0, 0, 0, None), (64, 32, 2, 1, 0, 1, 1), (96, 16, 1, 0, 0, 0, 0), (32, 48, 2, 0, 0, 2, 0),
                                                         (32, 16, 7, 0, 0, 0, 0)) + (((288, 16, 1, 0, 0, 0, 0),) if rot == 1 else ()):
-            rows.append(_row("w", 4, "pack", rot, crows, cw, np_, soff, doff, spad, gap, 0, f"winograd_down4_pack_lds_kernel<{rot},false>",
-                             "down3_pack_ok and want_lds" + ("; nine row blocks: the second group of eight is partly filled" if crows == 288 else ""),
-                             {NT7: f"winograd_down4_pack_lds_kernel<{rot},true>", PACK4T: f"winograd_down4_pack_kernel<{rot},false>",
-                              PACK4T_NT7: f"winograd_down4_pack_kernel<{rot},true>"}, ("swnt7", "swpack4")))
+            rows.append(_row("w", 4, "pack", rot, crows, cw, np_, soff, doff, spad, gap, 0, f"winograd_down4_pack_lds_kernel<{rot}>",
+                             "down3_pack_ok" + ("; nine row blocks: the second group of eight is partly filled" if crows == 288 else "")))
     # refusals: hipErrorInvalidValue and nothing written
     for (L, crows, cw, soff, doff, spad, gap, why) in (
             (2, 7, 16, 0, 0, 0, 0, "crows % 32 != 0"), (2, 32, 20, 0, 0, 0, 0, "cw % 16 != 0"), (2, 32, 8, 0, 0, 0, 0, "cw % 16 != 0"),
@@ -132,6 +118,8 @@ def _winograd_pack_rows():
             (4, 7, 16, 0, 0, 0, 0, "crows % 32 != 0"), (4, 32, 8, 0, 0, 0, 0, "cw % 16 != 0"), (4, 32, 20, 0, 0, 0, 0, "cw % 16 != 0"),
             (1, 32, 16, 0, 0, 0, 0, "no one-level pack pass")):
         rows.append(_row("w", L, "pack", 1, crows, cw, 2, soff, doff, spad, gap, 1, "(refused)", why))
+    for L in (2, 3, 4):   # a shape every depth takes with rot 0 or 1
+        rows.append(_row("w", L, "pack", 2, 32, 16, 2, rc=1, reach="(refused)", why="rot outside {0, 1}"))
     return rows
 
 
@@ -143,25 +131,19 @@ def _winograd34_rows():
              (64, 48, 1, 0, 0, 0, 0, "cw = 48, crows = 64"), (288, 2, 1, 0, 0, 0, 0, "crows = 288")]
     for flag in (0, 1):
         for (crows, cw, np_, soff, doff, spad, gap, why) in small + [(64, 64, 1, 0, 0, 0, 0, "cw = 64"), (3, 128, 7, 0, 0, 0, 0, "cw = 128"), (5, 32, 2, 0, 0, 0, 0, "cw = 32")]:
-            rows.append(_row("w", 3, "down", flag, crows, cw, np_, soff, doff, spad, gap, 0, f"winograd_down3_kernel<{_b(flag)},false>", why,
-                             {NT7: f"winograd_down3_kernel<{_b(flag)},true>"}, ("swnt7",)))
-            rows.append(_row("w", 3, "up", flag, crows, cw, np_, soff, doff, spad, gap, 0, f"winograd_up3_kernel<{_b(flag)},true>", why + "; PASS_NT default 2",
-                             {NT0: f"winograd_up3_kernel<{_b(flag)},false>"}, ("swnt0",)))
+            rows.append(_row("w", 3, "down", flag, crows, cw, np_, soff, doff, spad, gap, 0, f"winograd_down3_kernel<{_b(flag)}>", why))
+            rows.append(_row("w", 3, "up", flag, crows, cw, np_, soff, doff, spad, gap, 0, f"winograd_up3_kernel<{_b(flag)}>", why))
         # four levels: cw % 32 != 0 -> the direct / atomic forms
         for (crows, cw, np_, soff, doff, spad, gap, why) in small + [(3, 100, 1, 0, 0, 0, 0, "crows cw = 300: a partly filled position block")]:
-            rows.append(_row("w", 4, "down", flag, crows, cw, np_, soff, doff, spad, gap, 0, f"winograd_down4_kernel<{_b(flag)},false>", "cw % 32 != 0; " + why,
-                             {NT7: f"winograd_down4_kernel<{_b(flag)},true>"}, ("swnt7",)))
-            rows.append(_row("w", 4, "up", flag, crows, cw, np_, soff, doff, spad, gap, 0, "winograd_up4_kernel<true>" + ("" if flag else " + rowwise_kernel (zero first)"),
-                             "cw % U4_POS != 0; " + why, {NT0: "winograd_up4_kernel<false>"}, ("swnt0",)))
+            rows.append(_row("w", 4, "down", flag, crows, cw, np_, soff, doff, spad, gap, 0, f"winograd_down4_kernel<{_b(flag)}>", "cw % 32 != 0; " + why))
+            rows.append(_row("w", 4, "up", flag, crows, cw, np_, soff, doff, spad, gap, 0, "winograd_up4_kernel" + ("" if flag else " + rowwise_kernel (zero first)"),
+                             "cw % U4_POS != 0; " + why))
         # cw % 32 == 0 -> the forms through LDS
         for (crows, cw, np_, soff, doff, spad, gap, why) in ((1, 32, 1, 0, 0, 0, None, "smallest; bs = 0"), (7, 32, 2, 1, 1, 1, 1, "8-byte bases, odd stride and bs"),
                                                              (1, 64, 7, 0, 0, 0, 0, "cw = 64"), (2, 128, 1, 0, 0, 2, 0, "cw = 128"), (32, 64, 1, 0, 0, 0, 0, "32 x 64"),
                                                              (1, 32, 50, 0, 0, 0, 6, "50 parents on gridDim.y")):
-            rows.append(_row("w", 4, "down", flag, crows, cw, np_, soff, doff, spad, gap, 0, f"winograd_down4_lds_kernel<{_b(flag)},false>", "cw % 32 == 0 and want_lds; " + why,
-                             {NT7: f"winograd_down4_lds_kernel<{_b(flag)},true>", DOWN4D: f"winograd_down4_kernel<{_b(flag)},false>"}, ("swnt7", "swdown4")))
-            rows.append(_row("w", 4, "up", flag, crows, cw, np_, soff, doff, spad, gap, 0, f"winograd_up4_lds_kernel<{_b(flag)},true>", "cw % U4_POS == 0 and want_lds; " + why,
-                             {NT0: f"winograd_up4_lds_kernel<{_b(flag)},false>", UP4A: "winograd_up4_kernel<true>" + ("" if flag else " + rowwise_kernel (zero first)")},
-                             ("swnt0", "swup4")))
+            rows.append(_row("w", 4, "down", flag, crows, cw, np_, soff, doff, spad, gap, 0, f"winograd_down4_lds_kernel<{_b(flag)}>", "cw % 32 == 0; " + why))
+            rows.append(_row("w", 4, "up", flag, crows, cw, np_, soff, doff, spad, gap, 0, f"winograd_up4_lds_kernel<{_b(flag)}>", "cw % U4_POS == 0; " + why))
     return rows
 
 
@@ -212,12 +194,22 @@ def _zero_rows():
 ROWS = _winograd12_rows() + _winograd_pack_rows() + _winograd34_rows() + _scheme_rows() + _zero_rows()
 
 
+def _id_tail(r: Row) -> str:
+    """The ids of the three- and four-level Winograd rows end in the tags they carried while developer switches could re-route them to a
+    second form.  The switches and those forms are gone; the ids stay as they were, so that a row's results remain comparable with the
+    suite's earlier runs."""
+    if r.kind != "w" or r.L < 3 or r.reach.startswith("("):
+        return ""
+    lds = "_lds_" in r.reach
+    return {"down": "-swnt7" + ("-swdown4" if lds else ""), "up": "-swnt0" + ("-swup4" if lds else ""), "pack": "-swnt7" + ("-swpack4" if r.L == 4 else "")}[r.op]
+
+
 def row_id(r: Row) -> str:
     gap = "bs0" if r.gap is None else f"gap{r.gap}"
-    return f"{r.kind}{r.L}-{r.op}{r.flag}-r{r.crows}-c{r.cw}-p{r.np}-o{r.soff}{r.doff}-pad{r.spad}-{gap}" + "".join("-" + t for t in r.tags)
+    return f"{r.kind}{r.L}-{r.op}{r.flag}-r{r.crows}-c{r.cw}-p{r.np}-o{r.soff}{r.doff}-pad{r.spad}-{gap}" + _id_tail(r)
 
 
-# every instantiation of a pass kernel a caller in the library can select (rot = 2 excepted): the table must name each of them
+# every instantiation of a pass kernel the launchers can start (rot is 0 or 1): the table must name each of them
 def expected_kernels():
     tf = ("true", "false")
     out = set()
@@ -225,38 +217,33 @@ def expected_kernels():
         out |= {f"{k}<{v},{b}>" for v in ("word", "word2") for b in tf}
     out |= {f"winograd_down2_pack_kernel<{r}>" for r in (0, 1)}
     for k in ("winograd_down3_kernel", "winograd_up3_kernel", "winograd_down4_kernel", "winograd_down4_lds_kernel", "winograd_up4_lds_kernel"):
-        out |= {f"{k}<{a},{b}>" for a in tf for b in tf}
-    out |= {f"winograd_up4_kernel<{b}>" for b in tf}
-    for k in ("winograd_down3_pack_kernel", "winograd_down4_pack_lds_kernel", "winograd_down4_pack_kernel"):
-        out |= {f"{k}<{r},{b}>" for r in (0, 1) for b in tf}
+        out |= {f"{k}<{b}>" for b in tf}
+    out.add("winograd_up4_kernel")
+    for k in ("winograd_down3_pack_kernel", "winograd_down4_pack_lds_kernel"):
+        out |= {f"{k}<{r}>" for r in (0, 1)}
     for g, gu in (("1,64,1", "1,64,1"), ("2,64,7", "2,32,8"), ("4,64,8", "4,32,8")):
         out |= {f"scheme_down_kernel<{g},{b}>" for b in tf} | {f"scheme_up_kernel<{gu},{b}>" for b in tf} | {f"scheme_down_pack_kernel<{gu}>"}
     out.add("a4_pack_kernel")
     return out
 
 
-def kernels_named(setting=None):
-    """The instantiations the table means to reach in a process without switches (setting None) or in the child of `setting`."""
-    names = set()
-    for r in ROWS:
-        name = r.reach if setting is None else r.alt.get(setting)
-        if name and not name.startswith("("):
-            names.add(name.split(" + ")[0])
-    if setting is None:
-        names.add("a4_pack_kernel")   # the second opinion of every pack row, and test_a4_pack_kernel_alone
+def kernels_named():
+    """The instantiations the table means to reach."""
+    names = {r.reach.split(" + ")[0] for r in ROWS if not r.reach.startswith("(")}
+    names.add("a4_pack_kernel")   # the second opinion of every pack row, and test_a4_pack_kernel_alone
     return names
 
 
 def test_the_table_names_every_instantiation():
-    """No GPU needed: the table, over the process without switches and the children, names every instantiation of a pass kernel that a
-    caller in the library can select (expected_kernels: written out from the launchers, rot = 2 excepted) and nothing else."""
-    named = set().union(*(kernels_named(s) for s in (None,) + tuple(SETTINGS)))
+    """No GPU needed: the table names every instantiation of a pass kernel that the launchers can start (expected_kernels: written out
+    from the launchers, rot 0 and 1) and nothing else."""
+    named = kernels_named()
     assert named == expected_kernels(), sorted(named ^ expected_kernels())
     ids = [row_id(r) for r in ROWS]
     assert len(ids) == len(set(ids)), [i for i in ids if ids.count(i) > 1]
-    for r in ROWS:   # a row carries a switch's tag exactly when a setting with that tag re-routes it
-        assert {SETTINGS[s] for s in r.alt} == set(r.tags), row_id(r)
-        assert r.rc == 0 or not r.alt
+    for r in ROWS:
+        assert r.why and r.rc in (0, 1), row_id(r)
+        assert (r.rc == 1) == (r.reach == "(refused)"), row_id(r)
 
 
 def test_the_pass_library_exports_what_the_binding_binds():
@@ -280,15 +267,6 @@ def _host(t: torch.Tensor) -> np.ndarray:
     return t.cpu().numpy().view(np.uint64)
 
 
-def current_setting():
-    """The switches of this process as a key of SETTINGS ("" without any; the plain text of other combinations)."""
-    here = {k: os.environ[k] for k in SWITCHES if k in os.environ}
-    for s in SETTINGS:
-        if dict(kv.split("=") for kv in s.split()) == here:
-            return s
-    return " ".join(f"{k}={v}" for k, v in here.items())
-
-
 def _digits(r: Row, d: int) -> str:
     parts = []
     for s in reversed(ref.pass_steps(r.L, r.kind == "s")):
@@ -300,10 +278,7 @@ def _digits(r: Row, d: int) -> str:
 
 def _what(r: Row) -> str:
     side = {"down": f"{'B' if r.flag else 'A'} side", "pack": f"packed A, rot {r.flag}", "up": f"acc {r.flag}"}[r.op]
-    setting = current_setting()
-    reach = r.alt.get(setting, r.reach) if setting else r.reach
-    return (f"pass_{'down_pack' if r.op == 'pack' else r.op}, {'scheme' if r.kind == 's' else 'Winograd'}, {r.L} levels, {side}; form {reach}"
-            + (f" under {setting}" if setting else "") + f"; row {row_id(r)}")
+    return f"pass_{'down_pack' if r.op == 'pack' else r.op}, {'scheme' if r.kind == 's' else 'Winograd'}, {r.L} levels, {side}; form {r.reach}; row {row_id(r)}"
 
 
 def _mismatch_descendants(r: Row, got: np.ndarray, want: np.ndarray, unit: str) -> str:
@@ -503,32 +478,3 @@ def test_a4_pack_kernel_alone(rot, m, l, batch, spad, gap):
     bad = np.argwhere(g != want)
     assert bad.size == 0, (f"a4_pack_kernel, rot {rot}, {m} x {l} bits, batch {batch}: {len(bad)} dwords differ, first: matrix {bad[0][0]}, chunk {bad[0][1]}, "
                            f"row {bad[0][2]}: got {int(g[tuple(bad[0])]):#x}, want {int(want[tuple(bad[0])]):#x}")
-
-
-# ---- the forms behind the switches: one child process per setting, one at a time ---------------------------------------------------------------
-_child_died = []
-
-
-@gpu
-@pytest.mark.parametrize("setting", list(SETTINGS), ids=[s.replace(" ", "+") for s in SETTINGS])
-def test_forms_behind_a_switch(setting):
-    """The switches are static in the library and read once, so every setting gets a process of its own: this module again, under pytest -k,
-    with the rows the setting re-routes (SETTINGS, Row.alt).  A child that dies on a signal or runs into its time limit fails this test and
-    every later setting at once, unstarted: nothing more goes onto a device after a fault."""
-    if any(k in os.environ for k in SWITCHES):
-        pytest.fail("run the parent without " + ", ".join(k for k in SWITCHES if k in os.environ) + ": the table's `reach` column describes a process without switches")
-    if _child_died:
-        pytest.fail(f"not started: the child of {_child_died[0]} died or ran out of time")
-    tag = SETTINGS[setting]
-    n = sum(1 for r in ROWS if tag in r.tags)
-    assert n > 0
-    env = dict(os.environ, **dict(kv.split("=") for kv in setting.split()))
-    cmd = [sys.executable, "-m", "pytest", os.path.abspath(__file__), "-x", "-q", "-m", "gpu", "-p", "no:cacheprovider", "-k", f"test_pass_matches_reference and {tag}"]
-    try:
-        r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=600)
-    except subprocess.TimeoutExpired as e:
-        _child_died.append(setting)
-        pytest.fail(f"{setting}: the child ran longer than 600 s\n{(e.stdout or b'')[-3000:]}")
-    if r.returncode < 0 or r.returncode in (124, 134, 137, 139):
-        _child_died.append(setting)
-    assert r.returncode == 0 and re.search(rf"(^|\s){n} passed", r.stdout), f"{setting}: exit status {r.returncode}, {n} rows expected\n" + r.stdout[-6000:] + r.stderr[-2000:]

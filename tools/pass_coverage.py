@@ -1,13 +1,13 @@
 #!/usr/bin/env python3
-"""The parameter table of tests/test_gpu_passes.py against what really ran: which pass kernel instantiations a process launched, by the
-rocprofv3 kernel traces of that process, compared with the instantiations the table means to reach there.
+"""The parameter table of tests/test_gpu_passes.py against what really ran: which pass kernel instantiations the module's process
+launched, by its rocprofv3 kernel trace, compared with the instantiations the table means to reach.
 
-    python tools/pass_coverage.py --table                            # the table: row, launcher's answer, form, routing condition, forms under switches
-    python tools/pass_coverage.py none=<results.db> "M4RI_AMD_PASS_NT=7=<results.db>" ...
+    python tools/pass_coverage.py --table          # the table: row, launcher's answer, form, routing condition
+    python tools/pass_coverage.py <results.db>     # the comparison
 
-Each argument is <setting>=<rocpd database of `rocprofv3 --kernel-trace --stats -- python -m pytest tests/test_gpu_passes.py ...`>; the
-setting is `none` for the process without switches or a key of test_gpu_passes.SETTINGS.  An instantiation the table names and the trace
-does not hold is a missing test row; exit status 1 then.  (Kernel trace only: counters belong in a run of their own.)"""
+The argument is the rocpd database of one `rocprofv3 --kernel-trace --stats -- python -m pytest tests/test_gpu_passes.py -m gpu ...` run.
+An instantiation the table names and the trace does not hold is a missing test row; exit status 1 then.  (Kernel trace only: counters
+belong in a run of their own.)"""
 import os
 import re
 import sqlite3
@@ -57,27 +57,18 @@ def main(argv):
     import test_gpu_passes as T
     if argv == ["--table"]:
         for r in T.ROWS:
-            alt = "; ".join(f"{s}: {k}" for s, k in r.alt.items())
-            print(f"{T.row_id(r):64s} rc {r.rc}  {r.reach:62s} {r.why}" + (f"  [{alt}]" if alt else ""))
+            print(f"{T.row_id(r):64s} rc {r.rc}  {r.reach:40s} {r.why}")
         return 0
-    missing_any = False
-    union = set()
-    for arg in argv:
-        setting, path = arg.rsplit("=", 1)
-        want = T.kernels_named(None if setting == "none" else setting)
-        got = traced(path)
-        union |= set(got)
-        print(f"== {'no switch' if setting == 'none' else setting}: {len(got)} distinct pass kernel instantiations in the trace, {len(want)} named by the table")
-        for k in sorted(set(got) | want):
-            mark = "ok     " if k in got and k in want else "MISSING" if k in want else "also   "
-            print(f"  {mark} {k:48s} {got.get(k, 0):6d} launches")
-        missing_any |= bool(want - set(got))
-    expected = T.expected_kernels()
-    print(f"== all processes together: {len(union & expected)} of the {len(expected)} instantiations a caller in the library can select (rot = 2 excepted)")
-    for k in sorted(expected - union):
-        print(f"  MISSING {k}")
-        missing_any = True
-    return 1 if missing_any else 0
+    if len(argv) != 1:
+        print(__doc__)
+        return 2
+    want, got = T.kernels_named(), traced(argv[0])
+    assert want == T.expected_kernels()   # (test_the_table_names_every_instantiation)
+    print(f"== {len(got)} distinct pass kernel instantiations in the trace, {len(want)} named by the table = every one the launchers can start")
+    for k in sorted(set(got) | want):
+        mark = "ok     " if k in got and k in want else "MISSING" if k in want else "also   "
+        print(f"  {mark} {k:48s} {got.get(k, 0):6d} launches")
+    return 1 if want - set(got) else 0
 
 
 if __name__ == "__main__":
