@@ -746,6 +746,15 @@ int m4ri_amd_set_max_fuse(int levels);
    slab k+1 and download of slab k-1 under product k; same bits).  min_bytes: size of A + B + C from which that
    happens (default 64 MiB; 0 = never).  Returns the previous value; negative arguments only query. */
 int64_t m4ri_amd_set_host_pipeline(int64_t min_bytes);
+/* The plan of that pipeline for an m x l x n product (mzd_api.hip run_pipelined executes it and decides nothing itself), pure host
+   arithmetic, callable without a GPU.  min_bytes: the threshold above.  gi, gj, gk: a requested block grid (M4RI_AMD_PIPE_GRID; 0, 0, 0
+   for none); a request the shape has not the rows (gi x 4096), columns (gj x 64) or inner bits (gk x 64) for counts as none.  Returns 0
+   when the product is not pipelined; else 1, with the blocks  C_ij (+)= A_ik * B_kj  lying between the cuts written to rcut[], ccut[],
+   kcut[] (each may be NULL; each list runs from 0 to its dimension), their numbers gi, gj, gk to grid[3] and the words of the staging
+   arena the blocks of A, B and C take to *arena_words; or -1, with only grid[] and *arena_words written, when a list has more than
+   `cap` entries. */
+int m4ri_amd_plan_host_pipeline(int64_t m, int64_t l, int64_t n, int64_t min_bytes, int gi, int gj, int gk, int64_t *rcut, int64_t *ccut,
+                                int64_t *kcut, int cap, int *grid, int64_t *arena_words);
 
 /* Small products.  The reference switches algorithm by size inside the functions this library replaces (_mzd_mul_m4rm -> mzd_mul_naive
    below 54 columns / 16 rows, m4ri/brilliantrussian.c:1063-1068, m4ri/mzd.c:1141-1172); here the switch sits where a call's upload,

@@ -235,6 +235,7 @@ SYMBOLS = {
     "m4ri_amd_model_seconds": (ctypes.c_double, [_I64, _I64, _I64, _I]),
     "m4ri_amd_set_workspace_budget": (_I64, [_I64]),
     "m4ri_amd_set_host_pipeline": (_I64, [_I64]),
+    "m4ri_amd_plan_host_pipeline": (_I, [_I64, _I64, _I64, _I64, _I, _I, _I, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _I, ctypes.c_void_p, ctypes.c_void_p]),
     "m4ri_amd_pin": (_I, [MzdPtr]),
     "m4ri_amd_sync": (_I, [MzdPtr]),
     "m4ri_amd_host_modified": (_I, [MzdPtr]),
@@ -1005,6 +1006,39 @@ def set_workspace_budget(nbytes: int) -> int:
 def set_host_pipeline(min_bytes: int) -> int:
     """A + B + C bytes from which host-memory products are pipelined over row slabs (0 = never); returns the previous value."""
     return int(lib().m4ri_amd_set_host_pipeline(int(min_bytes)))
+
+
+class HostPipelinePlan:
+    """The blocks of a pipelined product from host memory: C_ij (+)= A_ik * B_kj between the cuts, and the staging arena's words."""
+
+    def __init__(self, rcut, ccut, kcut, arena_words):
+        self.rcut, self.ccut, self.kcut, self.arena_words = rcut, ccut, kcut, arena_words
+
+    @property
+    def grid(self):
+        return (len(self.rcut) - 1, len(self.ccut) - 1, len(self.kcut) - 1)
+
+    def __repr__(self):
+        return f"HostPipelinePlan(rcut={self.rcut}, ccut={self.ccut}, kcut={self.kcut}, arena_words={self.arena_words})"
+
+
+def plan_host_pipeline(m: int, l: int, n: int, min_bytes=None, grid=None):
+    """What mzd_mul on m x l and l x n host matrices does (m4ri_amd_plan_host_pipeline; host arithmetic only): None when the product is
+    not pipelined, else its HostPipelinePlan.  min_bytes: the pipeline's threshold (None: the library's current setting); grid: a
+    requested block grid (gi, gj) or (gi, gj, gk), as M4RI_AMD_PIPE_GRID gives one."""
+    if min_bytes is None:
+        min_bytes = lib().m4ri_amd_set_host_pipeline(-1)
+    gi, gj, gk = (0, 0, 0) if grid is None or len(grid) < 2 else (tuple(grid) + (1,))[:3]   # fewer than two numbers: no request
+    cap, counts, words = 64, (ctypes.c_int * 3)(), ctypes.c_int64()
+    while True:
+        cuts = [(ctypes.c_int64 * cap)() for _ in range(3)]
+        r = int(lib().m4ri_amd_plan_host_pipeline(m, l, n, int(min_bytes), gi, gj, gk, *[ctypes.cast(c, ctypes.c_void_p) for c in cuts], cap,
+                                                  ctypes.cast(counts, ctypes.c_void_p), ctypes.cast(ctypes.pointer(words), ctypes.c_void_p)))
+        if r == 0:
+            return None
+        if r > 0:
+            return HostPipelinePlan(*[[int(c[q]) for q in range(k + 1)] for c, k in zip(cuts, counts)], int(words.value))
+        cap = max(counts) + 1
 
 
 def set_max_fuse(levels: int) -> int:

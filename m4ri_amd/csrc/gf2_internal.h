@@ -8,6 +8,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <type_traits>
+#include <vector>
 #include "gf2_common.h"
 
 // return the HIP error of `expr` (a hipError_t or an int status) from the enclosing int-returning function
@@ -25,6 +26,27 @@ inline void with_bool(bool flag, F &&f) {
   if (flag) f(std::true_type{});
   else f(std::false_type{});
 }
+
+// words of the staging arena a device copy of a rows x ncols matrix takes: rows at an even stride, in 256-byte granules
+inline size_t dev_words(int64_t rows, int64_t ncols) {
+  const int64_t w = words_of(ncols), st = (w + 1) & ~(int64_t)1;
+  return (((size_t)(rows > 0 ? rows : 1) * (size_t)(st > 0 ? st : 2)) + 31) & ~(size_t)31;
+}
+
+// host_pipeline_plan.cpp: the plan of the host block pipeline -- blocks C_ij (+)= A_ik * B_kj between the cuts (each list from 0 to its
+// dimension) and the arena words of all blocks of A, B and C.  A requested grid (gi, gj, gk >= 1) the shape refuses counts as none.
+struct HostPipelinePlan {
+  bool pipelined = false;
+  std::vector<int64_t> rcut, ccut, kcut;
+  size_t arena_words = 0;
+  int gi() const { return (int)rcut.size() - 1; }
+  int gj() const { return (int)ccut.size() - 1; }
+  int gk() const { return (int)kcut.size() - 1; }
+  int64_t rows(int i) const { return rcut[(size_t)i + 1] - rcut[(size_t)i]; }
+  int64_t cols(int j) const { return ccut[(size_t)j + 1] - ccut[(size_t)j]; }
+  int64_t inner(int k) const { return kcut[(size_t)k + 1] - kcut[(size_t)k]; }
+};
+HostPipelinePlan gf2_plan_host_pipeline(int64_t m, int64_t l, int64_t n, size_t min_bytes, int gi, int gj, int gk);
 
 extern "C" {
 

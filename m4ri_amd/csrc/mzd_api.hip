@@ -8,7 +8,8 @@
 //   staging           one grow-only device arena per device, re-carved on every call; upload / download; the pinned host buffer
 //   residency         the table of pinned matrices (its entry points, m4ri_amd_pin and friends, are at the end of the file)
 //   HostCall          one host entry point running on the current device, and the placement of its operands
-//   products          mzd_mul, mzd_addmul, _mzd_mul_even ... _mzd_addsqr_even, mzd_mul_m4rm ..., mzd_mul_mp: run(), run_pipelined()
+//   products          mzd_mul, mzd_addmul, _mzd_mul_even ... _mzd_addsqr_even, mzd_mul_m4rm ..., mzd_mul_mp: run(), and run_pipelined(),
+//                     which executes the block plan of host_pipeline_plan.cpp (grid, cuts and arena words are decided there)
 //   solver family     TRSM, PLE / PLUQ, echelon forms, permutations, systems, kernels, inverses, transposes, triangular inverses
 //   table primitives  mzd_make_table, mzd_process_rows{,2..6}
 //
@@ -304,11 +305,6 @@ struct DevMat {
   word *p        = nullptr;
   int64_t stride = 0;
 };
-
-size_t dev_words(int64_t rows, int64_t ncols) {
-  const int64_t w = words_of(ncols), st = (w + 1) & ~(int64_t)1;
-  return (((size_t)(rows > 0 ? rows : 1) * (size_t)(st > 0 ? st : 2)) + 31) & ~(size_t)31;  // 256-byte granules
-}
 
 void dev_alloc(DevMat &d, int64_t rows, int64_t ncols) {
   const int64_t w = words_of(ncols);
@@ -618,13 +614,6 @@ int norm_cutoff(int cutoff, const char *who) {  // strassen.c:348-354
   return cutoff;  // 0 = engine default; >0 normalised inside m4ri_amd_mul_dev
 }
 
-// Large products from host memory, pipelined over blocks:  C_ij (+)= A_ik * B_kj  on a gi x gj x gk grid (2 x 2 x 1 when
-// both m and n allow it, 2 x 2 x 2 from 65536^3 on, four row slabs of A and C for narrow products).  The uploads are
-// blocking calls of this thread, the downloads of a second one (PCIe is full duplex), the products run on a non-blocking
-// stream:  upload A_00, B_00 | P || upload A_01, B_10 | P -> C_00 complete: download || upload B_01 | P || ...
-// so of the 1.5 GiB over PCIe at 65536^3 only the first pair of blocks (256 MiB) and the last block of C (128 MiB) stay
-// exposed.  Same bits as the one-shot schedule (every step is an ordinary product or addmul).  Returns false when the
-// product is too small to pay for it.
 // m * l * n at or below which a product from host memory is computed on the host (m4ri_amd_set_small_product_threshold; the measured
 // crossover against the GPU path on the GPU box, with the small leaf in the engine: 512^3 31 us on the host, 40 through the GPU;
 // 576^3 49 against 47 -- profiles/r06_small_products_host_routine.log).  M4RI_AMD_SMALL_THRESHOLD overrides the default.
@@ -640,285 +629,190 @@ bool small_product_wanted(int64_t m, int64_t l, int64_t n, int64_t threshold) {
   if ((double)m * (double)l * (double)n > (double)threshold) return false;
   return gf2_small_host_cost(m, l, n) <= (double)threshold / 240.0;
 }
+
+// C (+)= A * B on the device: the Strassen-Winograd engine, or a single leaf
+void product_dev(bool strassen, const DevMat &c, const DevMat &a, const DevMat &b, int64_t m, int64_t l, int64_t n, bool add, int cutoff, hipStream_t st) {
+  if (strassen) HIPDIE(m4ri_amd_mul_dev(c.p, c.stride, a.p, a.stride, b.p, b.stride, m, l, n, add ? 1 : 0, cutoff, st));
+  else HIPDIE(m4ri_amd_m4rm_dev(c.p, c.stride, a.p, a.stride, b.p, b.stride, m, l, n, add ? 1 : 0, 0, st));
+}
+
+// ---- large products from host memory, pipelined over blocks -------------------------------------------------------------------------
+// C_ij (+)= A_ik * B_kj  on the gi x gj x gk grid of gf2_plan_host_pipeline (host_pipeline_plan.cpp: 2 x 2 x 1 when both m and n allow it,
+// 2 x 2 x 2 from 65536^3 on, four row slabs of A and C for narrow products).  The uploads are blocking calls of this thread, the
+// downloads of a second one (PCIe is full duplex), the products run on a non-blocking stream:
+//   upload A_00, B_00 | P || upload A_01, B_10 | P -> C_00 complete: download || upload B_01 | P || ...
+// so of the 1.5 GiB over PCIe at 65536^3 only the first pair of blocks (256 MiB) and the last block of C (128 MiB) stay exposed.  Same
+// bits as the one-shot schedule (every step is an ordinary product or addmul).
 std::atomic<size_t> g_pipeline_min_bytes{(size_t)64 << 20};  // A + B + C bytes from which blocks are used (16384^3: 2.62 -> 2.42 ms, 24576^3: 6.3 -> 5.3 ms); 0 disables (m4ri_amd_set_host_pipeline)
 hipStream_t g_compute_stream[GF2_MAX_DEVICES];
 
+// One block of A, B or C on the device.  ready: recorded on the null stream behind the block's upload and tail mask (a block of C that
+// is not uploaded: behind its place in the arena); done (blocks of C only): recorded on the compute stream behind its last product
+struct PipeBlock {
+  DevMat d;
+  hipEvent_t ready = nullptr, done = nullptr;
+  bool issued = false;  // uploaded (or placed), `ready` recorded
+};
+struct PipeBlocks {  // all blocks of one call; their events exist from the start and go with this object
+  std::vector<PipeBlock> A, B, C;
+  PipeBlocks(int gi, int gj, int gk) : A((size_t)gi * gk), B((size_t)gk * gj), C((size_t)gi * gj) {
+    for (auto *v : {&A, &B, &C})
+      for (PipeBlock &b : *v) HIPDIE(hipEventCreateWithFlags(&b.ready, hipEventDisableTiming));
+    for (PipeBlock &c : C) HIPDIE(hipEventCreateWithFlags(&c.done, hipEventDisableTiming));
+  }
+  ~PipeBlocks() {
+    for (auto *v : {&A, &B, &C})
+      for (PipeBlock &b : *v)
+        for (hipEvent_t e : {b.ready, b.done})
+          if (e) (void)hipEventDestroy(e);
+  }
+};
+
+// M4RI_AMD_PIPE_TRACE=1: the timeline of a pipelined call on stderr (host clock for the copies, HIP events for the products; read by
+// tools/host_pipeline_trace.py).  Unset, every member returns at once.
+struct PipeTrace {
+  struct Mark { char what; int a, b; double t0, t1; };
+  struct Product { int t, k; hipEvent_t e0, e1; };
+  const bool on;
+  const hipStream_t cs;
+  timespec origin;
+  std::mutex mu;  // the downloader marks its copies too
+  std::vector<Mark> marks;
+  std::vector<Product> products;
+  hipEvent_t base = nullptr;  // the compute stream's clock ...
+  double base_ms  = 0;        // ... on the host's
+
+  explicit PipeTrace(hipStream_t compute) : on(enabled()), cs(compute) { clock_gettime(CLOCK_MONOTONIC, &origin); }
+  static bool enabled() { static const bool e = getenv("M4RI_AMD_PIPE_TRACE") != nullptr; return e; }
+  double now() const {
+    if (!on) return 0;
+    timespec t;
+    clock_gettime(CLOCK_MONOTONIC, &t);
+    return 1e3 * (double)(t.tv_sec - origin.tv_sec) + 1e-6 * (double)(t.tv_nsec - origin.tv_nsec);
+  }
+  void copied(char what, int a, int b, double t0) {  // a copy that began at t0 = now() has returned
+    if (!on) return;
+    std::lock_guard<std::mutex> g(mu);
+    marks.push_back({what, a, b, t0, now()});
+  }
+  hipEvent_t stamp() const {  // a timing event on the compute stream, here
+    hipEvent_t e;
+    HIPDIE(hipEventCreate(&e));
+    HIPDIE(hipEventRecord(e, cs));
+    return e;
+  }
+  void tie_clocks() { if (on) { base = stamp(); HIPDIE(hipEventSynchronize(base)); base_ms = now(); } }
+  void product_begins(int t, int k) { if (on) products.push_back({t, k, stamp(), nullptr}); }
+  void product_issued() { if (on) products.back().e1 = stamp(); }
+  void print(int64_t m, int64_t l, int64_t n, const HostPipelinePlan &plan) {  // after the device has been synchronised
+    if (!on) return;
+    const double t_end = now();
+    for (const Product &p : products) {
+      float a = 0, b = 0;
+      HIPDIE(hipEventElapsedTime(&a, base, p.e0));
+      HIPDIE(hipEventElapsedTime(&b, base, p.e1));
+      marks.push_back({'P', p.t, p.k, base_ms + a, base_ms + b});
+      (void)hipEventDestroy(p.e0);
+      (void)hipEventDestroy(p.e1);
+    }
+    (void)hipEventDestroy(base);
+    std::sort(marks.begin(), marks.end(), [](const Mark &x, const Mark &y) { return x.t0 < y.t0; });
+    fprintf(stderr, "m4ri_amd pipeline %lld x %lld x %lld, grid %d x %d x %d: %.2f ms (A/B = upload of block (i,k)/(k,j), P = product (block of C, slice), D = download)\n",
+            (long long)m, (long long)l, (long long)n, plan.gi(), plan.gj(), plan.gk(), t_end);
+    for (const Mark &k : marks) fprintf(stderr, "  %c(%d,%d) %8.2f .. %8.2f  (%6.2f ms)\n", k.what, k.a, k.b, k.t0, k.t1, k.t1 - k.t0);
+  }
+};
+
+mzd_t block_of(const mzd_t *M, int64_t r0, int64_t r1, int64_t c0, int64_t c1) {  // mzd_init_window, mzd.c:159-177
+  mzd_t S = *M;
+  S.data  = M->data + r0 * M->rowstride + c0 / 64;
+  S.nrows = (rci_t)(r1 - r0);
+  S.ncols = (rci_t)(c1 - c0);
+  S.width = (S.ncols + 63) / 64;
+  S.high_bitmask = (~(word)0) >> ((64 - S.ncols % 64) % 64);
+  // the block is a window unless it reaches M's own last column of a non-window M (then whole last words may be written)
+  if ((M->flags & FLAG_WINDOW) || c1 != M->ncols) S.flags |= FLAG_WINDOW;
+  return S;
+}
+
+// Executes the plan; returns false when the plan is not to pipeline (the product is too small to pay for it).  Step s = (block t of C in
+// row-major order, inner slice k) is one product on the compute stream; a block of A, B or C goes up (C for C += A * B only) the first
+// time a step needs it, and the blocks take their places in the arena in that order.
 bool run_pipelined(mzd_t *C, const mzd_t *A, const mzd_t *B, bool add, int cutoff, LateC *late) {
   const int64_t m = A->nrows, l = A->ncols, n = B->ncols;
-  const size_t bytes = ((size_t)m * A->width + (size_t)B->nrows * B->width + (size_t)m * (size_t)words_of(n)) * 8;
-  auto Cget = [&]() -> mzd_t * { return late ? late->get() : C; };  // a result still being allocated: first needed by the first download
-  if (g_pipeline_min_bytes == 0 || bytes < g_pipeline_min_bytes || m < 4 * 4096) return false;
-  // cuts: rows of A / C on whole 4096-row tiles, columns and the inner dimension on whole words
-  std::vector<int64_t> rcut, ccut, kcut;
-  static const char *grid_env = getenv("M4RI_AMD_PIPE_GRID");  // "gi,gj[,gk]": developer override of the block grid
+  static const char *grid_env = getenv("M4RI_AMD_PIPE_GRID");  // "gi,gj[,gk]": developer request for a block grid
   int egi = 0, egj = 0, egk = 1;
-  const int nenv = grid_env ? sscanf(grid_env, "%d,%d,%d", &egi, &egj, &egk) : 0;
-  if (nenv >= 2 && egi >= 1 && egj >= 1 && egk >= 1 && m >= (int64_t)egi * 4096 && n >= (int64_t)egj * 64 && l >= (int64_t)egk * 64) {
-    if (nenv < 3) egk = 1;
-  } else if (n >= 16384) {
-    egi = 2; egj = 2;
-    // from 65536^3 on also two slices of the inner dimension: the blocks stay cubes (full Strassen depth) and the first
-    // product waits for half as many bytes (43.1 instead of 46.0 ms; at 32768^3 the plain 2 x 2 is 3 % faster)
-    egk = (l >= 65536 && m >= 65536 && n >= 65536) ? 2 : 1;
-  } else {
-    egi = (int)((m + ((m / 4 + 4095) / 4096) * 4096 - 1) / (((m / 4 + 4095) / 4096) * 4096)); egj = 1; egk = 1;
-  }
-  // cut number i of `parts` through `total`: on the coarsest grid of unit * 2^j (j <= 5) that moves it by at most 8 % of a part, else
-  // on whole tiles of rows / whole words
-  auto coarse_cut = [](int64_t total, int parts, int i, int64_t unit0, int64_t prev, bool rows) -> int64_t {
-    const int64_t target = total * i / parts, fine = rows ? ((target + 4095) / 4096) * 4096 : (target / 64) * 64;
-    for (int j = 5; j >= 1; --j) {
-      const int64_t unit = unit0 << j, c = ((target + unit / 2) / unit) * unit;
-      const int64_t off = c > target ? c - target : target - c;
-      if (c > prev && c < total && off * 100 <= 8 * (total / parts)) return c;
-    }
-    return fine;
-  };
-  if (n >= 16384 || nenv >= 2) {
-    // rows are cut on the coarsest grid of 4096 * 2^j rows that moves the cut by at most 8 % of a block: the engine gives a block of
-    // k * 4096 * 2^L rows its full Strassen depth (engine.hip plan_row_blocks) -- 65664 rows cut 32768 + 32896, not 36864 + 28800
-    rcut.push_back(0);
-    for (int i = 1; i < egi; ++i) rcut.push_back(coarse_cut(m, egi, i, 4096, rcut.back(), true));
-    rcut.push_back(m);
-  } else {
-    const int64_t srows = ((m / 4 + 4095) / 4096) * 4096;
-    for (int64_t r = 0; r < m; r += srows) rcut.push_back(r);
-    rcut.push_back(m);
-  }
-  // columns and inner bits likewise, on 1024 * 2^j bits (whole words at every Strassen level the block will use): no strips in the
-  // blocks before the last
-  ccut.push_back(0);
-  for (int j = 1; j < egj; ++j) ccut.push_back(coarse_cut(n, egj, j, 1024, ccut.back(), false));
-  ccut.push_back(n);
-  kcut.push_back(0);
-  for (int k = 1; k < egk; ++k) kcut.push_back(coarse_cut(l, egk, k, 1024, kcut.back(), false));
-  kcut.push_back(l);
-  const int gi = (int)rcut.size() - 1, gj = (int)ccut.size() - 1, gk = (int)kcut.size() - 1;
+  if (!grid_env || sscanf(grid_env, "%d,%d,%d", &egi, &egj, &egk) < 2) egi = 0;
+  const HostPipelinePlan plan = gf2_plan_host_pipeline(m, l, n, g_pipeline_min_bytes, egi, egj, egk);
+  if (!plan.pipelined) return false;
+  const std::vector<int64_t> &rcut = plan.rcut, &ccut = plan.ccut, &kcut = plan.kcut;
+  const int gj = plan.gj(), gk = plan.gk(), nt = plan.gi() * gj, steps = nt * gk;
   int dev = 0;
   HIPDIE(hipGetDevice(&dev));
   hipStream_t &cs = g_compute_stream[dev];
   if (!cs) HIPDIE(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
-  auto R = [&](int i) { return rcut[(size_t)i + 1] - rcut[(size_t)i]; };
-  auto Cc = [&](int j) { return ccut[(size_t)j + 1] - ccut[(size_t)j]; };
-  auto K = [&](int k) { return kcut[(size_t)k + 1] - kcut[(size_t)k]; };
-  size_t need = 0;
-  for (int i = 0; i < gi; ++i)
-    for (int k = 0; k < gk; ++k) need += dev_words(R(i), K(k));
-  for (int k = 0; k < gk; ++k)
-    for (int j = 0; j < gj; ++j) need += dev_words(K(k), Cc(j));
-  for (int i = 0; i < gi; ++i)
-    for (int j = 0; j < gj; ++j) need += dev_words(R(i), Cc(j));
-  // M4RI_AMD_PIPE_W7=1: the top level as Strassen-Winograd over the 2 x 2 x 2 grid (7 block products instead of 8) when the halves are
-  // equal and whole -- the schedule below.  Built on the round-4 review's suggestion, bit-exact, and measured SLOWER than the 8 classical
-  // block products (65536^3: 44.6 against 41.7 ms, same box, alternating; profiles/r05_host_pipeline_timeline_65536.log): its third
-  // product needs seven of the eight quadrants, which the PCIe link delivers at 16.8 ms at the earliest, while the classical order
-  // never waits.  It stays an option for hosts with a faster link, not the default.
-  static const bool w7_on = getenv("M4RI_AMD_PIPE_W7") && atoi(getenv("M4RI_AMD_PIPE_W7")) == 1;
-  const bool w7 = w7_on && !add && gi == 2 && gj == 2 && gk == 2 && R(0) == R(1) && K(0) == K(1) && Cc(0) == Cc(1) && K(0) % 64 == 0 && Cc(0) % 64 == 0;
-  if (w7) need += dev_words(R(0), K(0)) + dev_words(K(0), Cc(0)) + dev_words(R(0), Cc(0));
-  arena_reserve(need);
-  auto block_of = [&](const mzd_t *M, int64_t r0, int64_t r1, int64_t c0, int64_t c1) {  // mzd_init_window, mzd.c:159-177
-    mzd_t S = *M;
-    S.data  = M->data + r0 * M->rowstride + c0 / 64;
-    S.nrows = (rci_t)(r1 - r0);
-    S.ncols = (rci_t)(c1 - c0);
-    S.width = (S.ncols + 63) / 64;
-    S.high_bitmask = (~(word)0) >> ((64 - S.ncols % 64) % 64);
-    // the block is a window unless it reaches M's own last column of a non-window M (then whole last words may be written)
-    if ((M->flags & FLAG_WINDOW) || c1 != M->ncols) S.flags |= FLAG_WINDOW;
-    return S;
+  arena_reserve(plan.arena_words);
+  PipeTrace trace(cs);
+  PipeBlocks blk(plan.gi(), gj, gk);
+  auto c_block = [&](int t) {  // of a result still being allocated: first needed by the first download
+    return block_of(late ? late->get() : C, rcut[(size_t)(t / gj)], rcut[(size_t)(t / gj) + 1], ccut[(size_t)(t % gj)], ccut[(size_t)(t % gj) + 1]);
   };
-  const int nt = gi * gj;
-  // M4RI_AMD_PIPE_TRACE=1: the timeline of this call on stderr (host clock for the copies, HIP events for the products)
-  static const bool trace = getenv("M4RI_AMD_PIPE_TRACE") != nullptr;
-  struct Mark { char what; int a, b; double t0, t1; };
-  std::vector<Mark> marks;
-  std::mutex marks_mu;
-  timespec tl0;
-  clock_gettime(CLOCK_MONOTONIC, &tl0);
-  auto now_ms = [&]() { timespec t; clock_gettime(CLOCK_MONOTONIC, &t); return 1e3 * (double)(t.tv_sec - tl0.tv_sec) + 1e-6 * (double)(t.tv_nsec - tl0.tv_nsec); };
-  auto mark = [&](char what, int a, int b, double t0) { if (trace) { std::lock_guard<std::mutex> g(marks_mu); marks.push_back({what, a, b, t0, now_ms()}); } };
-  hipEvent_t tr_base = nullptr;
-  std::vector<hipEvent_t> tr_p0, tr_p1;
-  double tr_base_ms = 0;
-  std::vector<DevMat> dA((size_t)gi * gk), dB((size_t)gk * gj), dC((size_t)nt);
-  std::vector<hipEvent_t> upA((size_t)gi * gk, nullptr), upB((size_t)gk * gj, nullptr), upC((size_t)nt, nullptr), done((size_t)nt, nullptr);
-  auto ev = [](hipEvent_t &e) { HIPDIE(hipEventCreateWithFlags(&e, hipEventDisableTiming)); };
-  auto upload_a = [&](int i, int k) {  // host rows -> device (blocking), tail masks on the null stream, then the event the products wait for
-    hipEvent_t &e = upA[(size_t)i * gk + k];
-    if (e) return;
-    const mzd_t S = block_of(A, rcut[(size_t)i], rcut[(size_t)i + 1], kcut[(size_t)k], kcut[(size_t)k + 1]);
-    const double t0 = trace ? now_ms() : 0;
-    upload(dA[(size_t)i * gk + k], &S);
-    mark('A', i, k, t0);
-    ev(e);
-    HIPDIE(hipEventRecord(e, nullptr));
+  auto ready = [](PipeBlock &b) { HIPDIE(hipEventRecord(b.ready, nullptr)); b.issued = true; };
+  auto send = [&](PipeBlock &b, const mzd_t &S, char what, int x, int y) {  // host rows -> device (blocking), tail masks on the null stream
+    const double t0 = trace.now();
+    upload(b.d, &S);
+    trace.copied(what, x, y, t0);
+    ready(b);
   };
-  auto upload_b = [&](int k, int j) {
-    hipEvent_t &e = upB[(size_t)k * gj + j];
-    if (e) return;
-    const mzd_t S = block_of(B, kcut[(size_t)k], kcut[(size_t)k + 1], ccut[(size_t)j], ccut[(size_t)j + 1]);
-    const double t0 = trace ? now_ms() : 0;
-    upload(dB[(size_t)k * gj + j], &S);
-    mark('B', k, j, t0);
-    ev(e);
-    HIPDIE(hipEventRecord(e, nullptr));
+  auto need_for = [&](int s) {
+    const int t = s / gk, k = s % gk, i = t / gj, j = t % gj;
+    PipeBlock &a = blk.A[(size_t)i * gk + k], &b = blk.B[(size_t)k * gj + j], &c = blk.C[(size_t)t];
+    if (!a.issued) send(a, block_of(A, rcut[(size_t)i], rcut[(size_t)i + 1], kcut[(size_t)k], kcut[(size_t)k + 1]), 'A', i, k);
+    if (!b.issued) send(b, block_of(B, kcut[(size_t)k], kcut[(size_t)k + 1], ccut[(size_t)j], ccut[(size_t)j + 1]), 'B', k, j);
+    if (!c.issued) {
+      if (add) { const mzd_t S = c_block(t); upload(c.d, &S); }
+      else dev_alloc(c.d, plan.rows(i), plan.cols(j));
+      ready(c);
+    }
   };
-  auto c_block = [&](int i, int j) { return block_of(Cget(), rcut[(size_t)i], rcut[(size_t)i + 1], ccut[(size_t)j], ccut[(size_t)j + 1]); };
-  auto prepare_c = [&](int t) {
-    if (upC[(size_t)t]) return;
-    if (add) { const mzd_t S = c_block(t / gj, t % gj); upload(dC[(size_t)t], &S); }
-    else dev_alloc(dC[(size_t)t], R(t / gj), Cc(t % gj));
-    ev(upC[(size_t)t]);
-    HIPDIE(hipEventRecord(upC[(size_t)t], nullptr));
+  auto product = [&](int s) {  // on the compute stream, behind the three blocks' events
+    const int t = s / gk, k = s % gk, i = t / gj, j = t % gj;
+    const PipeBlock &a = blk.A[(size_t)i * gk + k], &b = blk.B[(size_t)k * gj + j], &c = blk.C[(size_t)t];
+    for (const PipeBlock *x : {&a, &b, &c}) HIPDIE(hipStreamWaitEvent(cs, x->ready, 0));
+    trace.product_begins(t, k);
+    product_dev(true, c.d, a.d, b.d, plan.rows(i), plan.inner(k), plan.cols(j), add || k > 0, cutoff, cs);
+    trace.product_issued();
   };
   // The downloads run on a second host thread: a blocking copy holds its thread, and the blocks of C can travel down
   // while the next operands travel up (PCIe is full duplex: 53 GiB/s each way on this box, tools/pcie_probe_2d.py).
   std::mutex dl_mu;
   std::condition_variable dl_cv;
-  int issued = 0;  // entries of dl_order whose `done` event exists
-  std::vector<int> dl_order((size_t)nt);  // the blocks of C in the order they are computed (and complete)
-  // M4RI_AMD_PIPE_ORDER=c (developer): block columns of C outermost -- the first gi blocks need only the first block column of B
-  static const bool col_major = getenv("M4RI_AMD_PIPE_ORDER") && getenv("M4RI_AMD_PIPE_ORDER")[0] == 'c';
-  for (int q = 0; q < nt; ++q) dl_order[(size_t)q] = col_major ? (q % gi) * gj + (q / gi) : q;
-  if (w7) { dl_order[0] = 0; dl_order[1] = 3; dl_order[2] = 1; dl_order[3] = 2; }  // C11, C22, C12, C21
+  int complete = 0;  // blocks of C, in order, whose `done` event has been recorded
   std::thread downloader([&]() {
     HIPDIE(hipSetDevice(dev));
-    for (int q = 0; q < nt; ++q) {
-      {
-        std::unique_lock<std::mutex> lk(dl_mu);
-        dl_cv.wait(lk, [&] { return issued > q; });
-      }
-      const int t = dl_order[(size_t)q];
-      HIPDIE(hipEventSynchronize(done[(size_t)t]));
-      mzd_t S = c_block(t / gj, t % gj);
-      const double t0 = trace ? now_ms() : 0;
-      download(dC[(size_t)t], &S);
-      mark('D', t / gj, t % gj, t0);
+    for (int t = 0; t < nt; ++t) {
+      { std::unique_lock<std::mutex> lk(dl_mu); dl_cv.wait(lk, [&] { return complete > t; }); }
+      HIPDIE(hipEventSynchronize(blk.C[(size_t)t].done));
+      mzd_t S = c_block(t);
+      const double t0 = trace.now();
+      download(blk.C[(size_t)t].d, &S);
+      trace.copied('D', t / gj, t % gj, t0);
     }
   });
-  if (trace) {
-    HIPDIE(hipEventCreate(&tr_base));
-    HIPDIE(hipEventRecord(tr_base, cs));
-    HIPDIE(hipEventSynchronize(tr_base));
-    tr_base_ms = now_ms();
-  }
-  auto block_done = [&](int t) {  // block t of C is complete once everything issued on the compute stream so far has run: tell the downloader
-    ev(done[(size_t)t]);
-    HIPDIE(hipEventRecord(done[(size_t)t], cs));
-    {
-      std::lock_guard<std::mutex> lk(dl_mu);
-      issued += 1;
-    }
-    dl_cv.notify_one();
-  };
-  // products in the order (block of C, inner slice); the uploads of step s + 1 are issued right after product s
-  const int steps = w7 ? 0 : nt * gk;
-  auto need_for = [&](int s) {
-    const int t = dl_order[(size_t)(s / gk)], k = s % gk;
-    upload_a(t / gj, k);
-    upload_b(k, t % gj);
-    prepare_c(t);
-  };
-  if (w7) {
-    // Strassen-Winograd at the top (strassen.c:111-150 in the product form of engine.hip: A-side [A11, A12, S4, A22, S1, S2, S3], B-side
-    // [B11, B21, B22, T4, T1, T2, T3]; P0 goes to all four quadrants, P1 to C11, P2 to C12, P3 to C21, P4 to C12 and C22, P5 to all but
-    // C11, P6 to C21 and C22), in the order the quadrants ARRIVE: P0 and P1 need one quadrant of each operand, P6 seven of the eight,
-    // the rest all.  The quadrants of C accumulate on the device (single-target products as addmul straight into their quadrant, the
-    // others through one temporary), and each is downloaded when its last term has landed: C11 after P1, C22 after P5, C12 after P2,
-    // C21 after P3.  The operand sums are chains in two temporaries: X = S3, S1, S2 (+= A11), S4 (+= A12); Y = T3, T1, T2 (+= B22), T4 (+= B21).
-    const int64_t hm = R(0), hl = K(0), hn = Cc(0);
-    DevMat X, Y, P;
-    dev_alloc(X, hm, hl);
-    dev_alloc(Y, hl, hn);
-    dev_alloc(P, hm, hn);
-    for (int t = 0; t < 4; ++t) prepare_c(t);
-    auto qa = [&](int i, int k) -> const DevMat & { return dA[(size_t)i * gk + k]; };
-    auto qb = [&](int k, int j) -> const DevMat & { return dB[(size_t)k * gj + j]; };
-    auto wait_a = [&](int i, int k) { HIPDIE(hipStreamWaitEvent(cs, upA[(size_t)i * gk + k], 0)); };
-    auto wait_b = [&](int k, int j) { HIPDIE(hipStreamWaitEvent(cs, upB[(size_t)k * gj + j], 0)); };
-    auto xor3 = [&](const DevMat &D, const DevMat &U, const DevMat &V, int64_t rows, int64_t ncols) {
-      HIPDIE(m4ri_amd_xor_dev(D.p, D.stride, U.p, U.stride, V.p, V.stride, rows, ncols, cs));
-    };
-    int pno = 0;
-    auto product = [&](const DevMat &c, const DevMat &a, const DevMat &b, bool acc) {
-      if (trace) { hipEvent_t e; HIPDIE(hipEventCreate(&e)); HIPDIE(hipEventRecord(e, cs)); tr_p0.push_back(e); }
-      HIPDIE(m4ri_amd_mul_dev(c.p, c.stride, a.p, a.stride, b.p, b.stride, hm, hl, hn, acc ? 1 : 0, cutoff, cs));
-      if (trace) { hipEvent_t e; HIPDIE(hipEventCreate(&e)); HIPDIE(hipEventRecord(e, cs)); tr_p1.push_back(e); }
-      ++pno;
-    };
-    const size_t cq_bytes = (size_t)hm * (size_t)dC[0].stride * 8;
-    for (int t = 0; t < 4; ++t) HIPDIE(hipStreamWaitEvent(cs, upC[(size_t)t], 0));
-    upload_a(0, 0); upload_b(0, 0);                       // A11, B11
-    wait_a(0, 0); wait_b(0, 0);
-    product(dC[0], qa(0, 0), qb(0, 0), false);            // P0 -> C11, and the start of the other three
-    for (int t = 1; t < 4; ++t) HIPDIE(hipMemcpyAsync(dC[(size_t)t].p, dC[0].p, cq_bytes, hipMemcpyDeviceToDevice, cs));
-    upload_a(0, 1); upload_b(1, 0);                       // A12, B21
-    wait_a(0, 1); wait_b(1, 0);
-    product(dC[0], qa(0, 1), qb(1, 0), true);             // P1: C11 += A12 * B21
-    block_done(0);
-    upload_a(1, 0); upload_b(0, 1); upload_b(1, 1);       // A21, B12, B22
-    wait_a(1, 0); wait_b(0, 1); wait_b(1, 1);
-    xor3(X, qa(0, 0), qa(1, 0), hm, hl);                  // S3 = A11 + A21
-    xor3(Y, qb(1, 1), qb(0, 1), hl, hn);                  // T3 = B22 + B12
-    product(P, X, Y, false);                              // P6 -> C21, C22
-    xor3(dC[3], dC[3], P, hm, hn);
-    xor3(dC[2], dC[2], P, hm, hn);
-    upload_a(1, 1);                                       // A22
-    wait_a(1, 1);
-    xor3(X, qa(1, 0), qa(1, 1), hm, hl);                  // S1 = A21 + A22
-    xor3(Y, qb(0, 1), qb(0, 0), hl, hn);                  // T1 = B12 + B11
-    product(P, X, Y, false);                              // P4 -> C12, C22
-    xor3(dC[3], dC[3], P, hm, hn);
-    xor3(dC[1], dC[1], P, hm, hn);
-    xor3(X, X, qa(0, 0), hm, hl);                         // S2 = S1 + A11
-    xor3(Y, Y, qb(1, 1), hl, hn);                         // T2 = T1 + B22
-    product(P, X, Y, false);                              // P5 -> C12, C21, C22
-    xor3(dC[3], dC[3], P, hm, hn);
-    block_done(3);
-    xor3(dC[2], dC[2], P, hm, hn);
-    xor3(dC[1], dC[1], P, hm, hn);
-    xor3(X, X, qa(0, 1), hm, hl);                         // S4 = S2 + A12
-    product(dC[1], X, qb(1, 1), true);                    // P2: C12 += S4 * B22
-    block_done(1);
-    xor3(Y, Y, qb(1, 0), hl, hn);                         // T4 = T2 + B21
-    product(dC[2], qa(1, 1), Y, true);                    // P3: C21 += A22 * T4
-    block_done(2);
-  } else need_for(0);
+  trace.tie_clocks();
+  need_for(0);
   for (int s = 0; s < steps; ++s) {
-    const int t = dl_order[(size_t)(s / gk)], k = s % gk, i = t / gj, j = t % gj;
-    HIPDIE(hipStreamWaitEvent(cs, upA[(size_t)i * gk + k], 0));
-    HIPDIE(hipStreamWaitEvent(cs, upB[(size_t)k * gj + j], 0));
-    HIPDIE(hipStreamWaitEvent(cs, upC[(size_t)t], 0));
-    const DevMat &a = dA[(size_t)i * gk + k], &b = dB[(size_t)k * gj + j];
-    if (trace) { hipEvent_t e; HIPDIE(hipEventCreate(&e)); HIPDIE(hipEventRecord(e, cs)); tr_p0.push_back(e); }
-    HIPDIE(m4ri_amd_mul_dev(dC[(size_t)t].p, dC[(size_t)t].stride, a.p, a.stride, b.p, b.stride, R(i), K(k), Cc(j), (add || k > 0) ? 1 : 0, cutoff, cs));
-    if (trace) { hipEvent_t e; HIPDIE(hipEventCreate(&e)); HIPDIE(hipEventRecord(e, cs)); tr_p1.push_back(e); }
-    if (k == gk - 1) block_done(t);
+    product(s);
+    if (s % gk == gk - 1) {  // the block's last inner slice: complete once everything issued on the compute stream so far has run
+      HIPDIE(hipEventRecord(blk.C[(size_t)(s / gk)].done, cs));
+      { std::lock_guard<std::mutex> lk(dl_mu); complete += 1; }
+      dl_cv.notify_one();
+    }
     if (s + 1 < steps) need_for(s + 1);  // overlaps product s
   }
   downloader.join();
   HIPDIE(hipDeviceSynchronize());
-  if (trace) {
-    const double t_end = now_ms();
-    for (size_t s = 0; s < tr_p0.size(); ++s) {
-      float a = 0, b = 0;
-      HIPDIE(hipEventElapsedTime(&a, tr_base, tr_p0[s]));
-      HIPDIE(hipEventElapsedTime(&b, tr_base, tr_p1[s]));
-      marks.push_back({'P', w7 ? (int)s : dl_order[s / (size_t)gk], w7 ? 0 : (int)s % gk, tr_base_ms + a, tr_base_ms + b});
-      (void)hipEventDestroy(tr_p0[s]);
-      (void)hipEventDestroy(tr_p1[s]);
-    }
-    (void)hipEventDestroy(tr_base);
-    std::sort(marks.begin(), marks.end(), [](const Mark &x, const Mark &y) { return x.t0 < y.t0; });
-    fprintf(stderr, "m4ri_amd pipeline %lld x %lld x %lld, grid %d x %d x %d%s: %.2f ms (A/B = upload of block (i,k)/(k,j), P = product (block of C, slice)%s, D = download)\n",
-            (long long)m, (long long)l, (long long)n, gi, gj, gk, w7 ? ", Strassen-Winograd at the top" : "", t_end,
-            w7 ? " -- here the seven in the order P0 P1 P6 P4 P5 P2 P3" : "");
-    for (const Mark &k : marks) fprintf(stderr, "  %c(%d,%d) %8.2f .. %8.2f  (%6.2f ms)\n", k.what, k.a, k.b, k.t0, k.t1, k.t1 - k.t0);
-  }
-  for (auto *v : {&upA, &upB, &upC, &done})
-    for (hipEvent_t e : *v)
-      if (e) (void)hipEventDestroy(e);
+  trace.print(m, l, n, plan);
   return true;
 }
 
@@ -954,10 +848,7 @@ mzd_t *run(mzd_t *C, const mzd_t *A, const mzd_t *B, bool add, bool strassen, in
       if (add) pack_rows(hs + wa + wb, dC.stride, C);
       const size_t up = (wa + wb + (add ? wc : 0)) * 8;
       HIPDIE(hipMemcpyAsync(dA.p, hs, up, hipMemcpyHostToDevice, nullptr));   // dA, dB, dC are consecutive in the arena, like hs
-      if (strassen)
-        HIPDIE(m4ri_amd_mul_dev(dC.p, dC.stride, dA.p, dA.stride, dB.p, dB.stride, A->nrows, A->ncols, B->ncols, add, cutoff, nullptr));
-      else
-        HIPDIE(m4ri_amd_m4rm_dev(dC.p, dC.stride, dA.p, dA.stride, dB.p, dB.stride, A->nrows, A->ncols, B->ncols, add, 0, nullptr));
+      product_dev(strassen, dC, dA, dB, A->nrows, A->ncols, B->ncols, add, cutoff, nullptr);
       HIPDIE(hipMemcpyAsync(hs + wa + wb, dC.p, wc * 8, hipMemcpyDeviceToHost, nullptr));
       HIPDIE(hipStreamSynchronize(nullptr));
       unpack_rows(C, hs + wa + wb, dC.stride);
@@ -970,11 +861,8 @@ mzd_t *run(mzd_t *C, const mzd_t *A, const mzd_t *B, bool add, bool strassen, in
   Operand &a = call.in(A), &b = same ? a : call.in(B);
   Operand &c = late ? call.space(cm, cn) : add ? call.inout(C) : call.out(C);
   call.stage();
-  const DevMat dA = a.d, dB = b.d, dC = c.d;
-  if (strassen)
-    HIPDIE(m4ri_amd_mul_dev(dC.p, dC.stride, dA.p, dA.stride, dB.p, dB.stride, A->nrows, A->ncols, B->ncols, add, cutoff, nullptr));
-  else
-    HIPDIE(m4ri_amd_m4rm_dev(dC.p, dC.stride, dA.p, dA.stride, dB.p, dB.stride, A->nrows, A->ncols, B->ncols, add, 0, nullptr));
+  const DevMat dC = c.d;
+  product_dev(strassen, dC, a.d, b.d, A->nrows, A->ncols, B->ncols, add, cutoff, nullptr);
   // a B that is a window of a pinned parent carries its neighbours' bits in the last word, and they
   // land in C's excess columns: clear them before the result leaves the staging buffer
   // (an unstaged pinned C spans its parent's full width, so its excess bits must be zero anyway:

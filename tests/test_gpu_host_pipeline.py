@@ -1,8 +1,10 @@
-"""The host entry points' slab pipeline (mzd_api.hip: run_pipelined; m4ri_amd_set_host_pipeline): large products
-from host memory are cut into a 2 x 2 grid of blocks of C (or four row slabs when n is small) so that PCIe copies run under the
-products.  A block is an
-ordinary product, so every bit must equal the one-shot schedule's and the oracle's -- ragged last slabs, windows
-with non-zero excess (parent bits outside the window untouched), accumulate."""
+"""The host entry points' block pipeline (mzd_api.hip run_pipelined executing the plan of host_pipeline_plan.cpp;
+m4ri_amd_set_host_pipeline, m4ri_amd.plan_host_pipeline): large products from host memory are cut into a grid of blocks
+C_ij (+)= A_ik * B_kj -- 2 x 2 blocks of C when n >= 16384, row slabs of 4096 rows and more when n is smaller, two inner slices from
+65536^3 on or where M4RI_AMD_PIPE_GRID asks for them -- so that PCIe copies run under the products.  A product with fewer than 16384
+rows is never pipelined, whatever the threshold and the requested grid.  A block is an ordinary product, so every bit must equal the
+one-shot schedule's and the oracle's -- ragged last blocks, windows with non-zero excess (parent bits outside the window untouched),
+accumulate.  The tests that force a grid ask the plan which of their shapes pipeline and count the pipeline's trace headers."""
 import numpy as np
 import pytest
 
@@ -25,6 +27,9 @@ def _gpu():
                                    (16384, 300, 16384), (20001, 700, 17000 + 13), (16500, 64, 30000),
                                    (33000, 300, 16384 + 1)])   # n >= 16384: the 2 x 2 grid; 33000 rows cut at 16384 (the coarse grid), 20001 at 12288
 def test_pipelined_products_match_oracle(oracle, m, l, n):
+    """Every shape has 16384 rows or more and the threshold is 1 byte, so all of them pipeline: the first five over row slabs
+    (n < 16384), the last four over 2 x 2 blocks of C (tests/test_host_pipeline_plan.py pins the cuts)."""
+    assert m4ri_amd.plan_host_pipeline(m, l, n, min_bytes=1) is not None
     A, B = Mzd.random(m, l, 1), Mzd.random(l, n, 2)
     want = oracle.mul(None, A, B, 0)
     assert m4ri_amd.mzd_mul(None, A, B, 0).equal(want)
@@ -117,38 +122,90 @@ def _child(code, env_extra, timeout=900):
     return r.stdout, r.stderr
 
 
-@pytest.mark.parametrize("w7", ["1", "0"])
-def test_winograd_at_the_top_of_the_block_pipeline(w7):
-    """The 2 x 2 x 2 block grid of the host pipeline run as Strassen-Winograd (7 block products in the order their quadrants arrive,
-    the quadrants of C accumulated on the device; mzd_api.hip run_pipelined) against the oracle, at sizes the oracle finishes in
-    seconds (the grid forced with M4RI_AMD_PIPE_GRID; by itself it is chosen from 65536^3 on; the schedule is opt-in, M4RI_AMD_PIPE_W7=1:
-    it measured slower than the 8 classical block products, which is what =0 and the default run): same bits.  Unequal halves and C += A*B keep the classical grid; C == NULL and C given both covered."""
-    code = '''
+FORCED_SHAPES = {
+    # five shapes of which only 16384 x 4096 x 8192 has the rows to pipeline (the others take the one-shot path, whatever grid is asked
+    # for); then the smallest blocks the grid rule allows (64 inner bits, 64 columns); a ragged last row block, a ragged last word in
+    # the last column block and inner slices 64 + 136; row blocks 12288 + 8192
+    "2,2,2": [(8192, 2048, 2048), (16384, 4096, 8192), (8192, 1280, 1152), (8192 + 4096, 2048, 2048), (8192, 2048 + 64, 2048),
+              (16384, 128, 128), (16421, 200, 130), (16384 + 4096, 192, 192)],
+    # sixteen blocks of C, two slices each: the longest queue of downloads
+    "8,2,2": [(32768, 640, 256)],
+}
+HEADER = r"m4ri_amd pipeline (\d+) x (\d+) x (\d+), grid (\d+) x (\d+) x (\d+):"
+
+
+def _headers(err):
+    import re
+    return [tuple(int(x) for x in h) for h in re.findall(HEADER, err)]
+
+
+@pytest.mark.parametrize("grid", sorted(FORCED_SHAPES))
+def test_forced_grids_of_the_block_pipeline(grid):
+    """Block grids with inner slices (by itself the pipeline slices the inner dimension from 65536^3 on) forced with M4RI_AMD_PIPE_GRID
+    at sizes the oracle finishes in seconds: mzd_mul(NULL), mzd_mul(C) and mzd_addmul against the oracle, C's excess bits clean.  Which
+    shapes pipeline is the plan's answer (m4ri_amd.plan_host_pipeline), and the trace must show exactly that: three headers naming the
+    plan's grid for every shape that pipelines, none for the others."""
+    shapes, req = FORCED_SHAPES[grid], tuple(int(x) for x in grid.split(","))
+    code = f'''
 import m4ri_amd, cpu_libs
 from m4ri_amd.mzd import Mzd
 m4ri_amd.init(0); m4ri_amd.set_host_pipeline(1); m4ri_amd.set_small_product_threshold(0)
 orc = cpu_libs.oracle()
-for (m, l, n) in [(8192, 2048, 2048), (16384, 4096, 8192), (8192, 1280, 1152), (8192 + 4096, 2048, 2048), (8192, 2048 + 64, 2048)]:
+for (m, l, n) in {shapes!r}:
     A, B = Mzd.random(m, l, 1), Mzd.random(l, n, 2)
     want = orc.mul(None, A, B, 0)
     assert m4ri_amd.mzd_mul(None, A, B, 0).equal(want), (m, l, n)
     C = Mzd.random(m, n, 3)
     assert m4ri_amd.mzd_mul(C, A, B, 0).equal(want), (m, l, n)
+    assert not (C.valid_words()[:, -1] & ~np.uint64(C.high_bitmask)).any(), (m, l, n)
     C0 = Mzd.random(m, n, 4)
     assert m4ri_amd.mzd_addmul(C0.copy(), A, B, 0).equal(orc.addmul(C0.copy(), A, B, 0)), (m, l, n)
 print("ok")
 '''
-    out, err = _child(code, {"M4RI_AMD_PIPE_GRID": "2,2,2", "M4RI_AMD_PIPE_W7": w7, "M4RI_AMD_PIPE_TRACE": "1"})
+    out, err = _child(code, {"M4RI_AMD_PIPE_GRID": grid, "M4RI_AMD_PIPE_TRACE": "1"})
     assert "ok" in out
-    assert ("Strassen-Winograd at the top" in err) == (w7 == "1")          # the schedule really ran (equal halves), and the switch switches it off
-    assert "grid 2 x 2 x 2:" in err or w7 == "1"                          # unequal halves / addmul: the classical grid
+    want = []
+    for shape in shapes:
+        p = m4ri_amd.plan_host_pipeline(*shape, min_bytes=1, grid=req)
+        assert (p is not None) == (shape[0] >= 16384) and (p is None or p.grid == req), (shape, p)
+        want += [shape + req] * (3 if p is not None else 0)   # mzd_mul(NULL), mzd_mul(C), mzd_addmul
+    assert _headers(err) == want
+    assert "Strassen-Winograd" not in err
 
 
-@pytest.mark.parametrize("w7", ["0", "1"])
-def test_config3_through_the_host_entry_point_matches_the_reference_sha256(w7):
+def test_forced_grid_on_windows_keeps_the_parents():
+    """The 2 x 2 x 2 grid on windows: the column cut (bit 128 of 333) and the inner cut (bit 128 of 300) fall inside the windows of B and
+    C, the last row block is ragged, and what the parents hold outside the windows stays as it was."""
+    code = '''
+import m4ri_amd, cpu_libs
+from m4ri_amd.mzd import Mzd
+m4ri_amd.init(0); m4ri_amd.set_host_pipeline(1); m4ri_amd.set_small_product_threshold(0)
+orc = cpu_libs.oracle()
+m, l, n = 16384 + 37, 300, 333
+PA, PB, PC = Mzd.random(m + 30, 448, 5), Mzd.random(l + 20, 600, 6), Mzd.random(m + 25, 520, 7)
+a, b, c = PA.window(10, 64, 10 + m, 64 + l), PB.window(7, 128, 7 + l, 128 + n), PC.window(9, 64, 9 + m, 64 + n)
+PA0, PB0 = PA.buf.copy(), PB.buf.copy()
+PCo = Mzd(m + 25, 520, buf=PC.buf.copy())
+co = PCo.window(9, 64, 9 + m, 64 + n)
+orc.mul(co, a.copy(), b.copy(), 0)
+m4ri_amd.mzd_mul(c, a, b, 0)
+assert np.array_equal(PC.buf, PCo.buf), "mul"
+orc.addmul(co, a.copy(), b.copy(), 0)
+m4ri_amd.mzd_addmul(c, a, b, 0)
+assert np.array_equal(PC.buf, PCo.buf), "addmul"
+assert np.array_equal(PA.buf, PA0) and np.array_equal(PB.buf, PB0)
+print("ok")
+'''
+    out, err = _child(code, {"M4RI_AMD_PIPE_GRID": "2,2,2", "M4RI_AMD_PIPE_TRACE": "1"})
+    assert "ok" in out
+    p = m4ri_amd.plan_host_pipeline(16384 + 37, 300, 333, min_bytes=1, grid=(2, 2, 2))
+    assert (p.rcut, p.ccut, p.kcut) == ([0, 8192, 16421], [0, 128, 333], [0, 128, 300])
+    assert _headers(err) == [(16421, 300, 333, 2, 2, 2)] * 2
+
+
+def test_config3_through_the_host_entry_point_matches_the_reference_sha256():
     """BASELINE.json configs[2] the way the reference's own bench calls it -- mzd_mul(NULL, A, B, 0) on host matrices, 65536^3, seeds
-    3, 4 -- through the block pipeline (the default 8 classical block products, and the optional Strassen-Winograd top level): the
-    SHA-256 of the real reference's product."""
+    3, 4 -- through the block pipeline (2 x 2 x 2: eight block products): the SHA-256 of the real reference's product."""
     code = '''
 import m4ri_amd
 from m4ri_amd.mzd import Mzd
@@ -160,8 +217,9 @@ print("sha", hashlib.sha256(C.masked().tobytes()).hexdigest())
 '''
     import json
     import os
-    out, err = _child(code, {"M4RI_AMD_PIPE_TRACE": "1", "M4RI_AMD_PIPE_W7": w7}, timeout=1500)
+    out, err = _child(code, {"M4RI_AMD_PIPE_TRACE": "1"}, timeout=1500)
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     want = [e["sha256"] for e in json.load(open(os.path.join(root, "tests", "golden", "sha256.json")))
             if (e["op"], e["m"], e["l"], e["n"], e["seed_a"], e["seed_b"]) == ("mul", 65536, 65536, 65536, 3, 4) and not e.get("cutoff")]
-    assert want and ("sha " + want[0]) in out and ("Strassen-Winograd at the top" in err) == (w7 == "1")
+    assert want and ("sha " + want[0]) in out
+    assert _headers(err) == [(65536, 65536, 65536, 2, 2, 2)] and "Strassen-Winograd" not in err
