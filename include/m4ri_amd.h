@@ -453,6 +453,36 @@ int m4ri_amd_row_span_batch_dev(const word *A, int64_t a_stride, int64_t a_bs, i
  * member, clamped to [0, 2^30]; 0 = no path 1) replace them in the routing of a call, read per call; this function does not read
  * them. */
 int m4ri_amd_plan_reduce_batch(int64_t nrows, int64_t ncols);
+/* Weight distributions and minimum weights of the ROW SPACES of `batch` small matrices (rowspace_batch.hip): the table of
+ * mzd_make_table, all 2^k combinations of k rows in Gray order, with a population count in place of the store; nothing of size 2^k
+ * is ever written.  Member b has the generator G_b, k x n at G + b * g_bs words, rows g_stride words apart (g_bs = 0: one shared G),
+ * and an optional word V_b, 1 x n at V + b * v_bs words (V == NULL: zero; v_bs = 0: one shared V).  For every message x in
+ * [0, 2^k) the word is c_b(x) = V_b ^ the XOR of the rows i of G_b with bit i of x set.  Only the n valid bits count: bits at
+ * columns >= n of a last word, the words from the width to the stride and the words between members never influence a result; G and
+ * V are READ ONLY.
+ * hist (DEVICE int64, batch * (n + 1) entries, or NULL): hist[b * (n + 1) + w] = the number of x with wt(c_b(x)) = w.  MESSAGES are
+ * counted, not distinct words: every member's entries sum to 2^k, and a G of rank r counts every word of its span 2^(k - r) times.
+ * lightest (DEVICE int64, batch entries, or NULL): lightest[b] = the minimum over the x with wt(c_b(x)) >= w_min of (wt << 40) | x,
+ * -1 if no x qualifies; among equal weights the smallest x.  w_min = 1 without V: the minimum distance of the code and the smallest
+ * message that attains it, whatever G's rank.  w_min = 0 with V: the distance from V_b to the code and the message of the nearest
+ * codeword.  At least one of the two outputs is required; both are written whole, whatever they held.
+ * Limits: 0 <= k <= 40 (the message fits the key) and 0 <= n <= 1024 (a word fits 32 registers per lane); beyond either the call
+ * returns hipErrorNotSupported (801) before any HIP call.  k = 0 is the one message 0 with c = V; n = 0: every word weighs 0.
+ * Asynchronous on `stream` on both paths of m4ri_amd_plan_rowspace_weights_batch: plain launches (on path 1 an initialisation of the
+ * outputs goes first, on the same stream), no allocation, no copy to the host, no synchronisation, no engine workspace, no engine
+ * lock; capturable.  All results are integer counts and minima: they do not depend on the order the hardware takes the messages in.
+ * hipErrorInvalidValue, before any HIP call, for negative sizes, strides or batch strides or w_min < 0, g_stride < words(n) with
+ * k > 1, a NULL G with non-empty members (batch > 0, k > 0, n > 0), no output at all, or an output array whose bytes meet the span
+ * (first member's start to last member's end) of G, of V or the other output.  batch = 0 succeeds without touching anything. */
+int m4ri_amd_rowspace_weights_batch_dev(const word *G, int64_t g_stride, int64_t g_bs, int64_t k, int64_t n, const word *V, int64_t v_bs,
+                                        int64_t batch, int64_t w_min, int64_t *hist, int64_t *lightest, void *stream);
+/* which path the call above takes for members of this shape (pure host arithmetic; -1 for negative sizes; sizes beyond the call's
+ * limits are answered by the same rule): 0 a wave owns the member, four members per workgroup, plain stores, no global atomics
+ * (k <= K0, or n = 0); 1 the member's messages are spread over 2^(k - s - 6) waves of s-bit Gray walks, s = k - 19 held in [6, 12],
+ * their results combined with global 64-bit integer atomics.  K0 is a measured bound.  The environment variable
+ * M4RI_AMD_ROWSPACE_PATH0_MAX (clamped to [-1, 26]; -1 = no path 0 for members with columns) replaces it in the routing of a call,
+ * read per call; this function does not read it. */
+int m4ri_amd_plan_rowspace_weights_batch(int64_t k, int64_t n);
 /* Assembling, cutting and permuting the members of a batch where they are (assemble_batch.hip).  Conventions of the calls below, as
  * of the other batched calls: member b of X is at X + b * x_bs words, its rows x_stride words apart; a batch stride of 0 on a
  * READ-ONLY operand is one operand shared by all members.  Every call is asynchronous on `stream`: plain launches (several for a

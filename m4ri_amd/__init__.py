@@ -190,6 +190,8 @@ SYMBOLS = {
     "m4ri_amd_mismatch_batch_dev": (_I, [_P, _I64, _I64, _P, _I64, _I64, _I64, _I64, _I64, _P, _P]),
     "m4ri_amd_row_span_batch_dev": (_I, [_P, _I64, _I64, _I64, _I64, _I64, _P, _P, _P]),
     "m4ri_amd_plan_reduce_batch": (_I, [_I64, _I64]),
+    "m4ri_amd_rowspace_weights_batch_dev": (_I, [_P, _I64, _I64, _I64, _I64, _P, _I64, _I64, _I64, _P, _P, _P]),
+    "m4ri_amd_plan_rowspace_weights_batch": (_I, [_I64, _I64]),
     "m4ri_amd_copy_block_batch_dev": (_I, [_P, _I64, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _P]),
     "m4ri_amd_extract_tri_batch_dev": (_I, [_P, _I64, _I64, _P, _I64, _I64, _I64, _I64, _I64, _I, _I, _P, _P]),
     "m4ri_amd_apply_p_left_batch_dev": (_I, [_P, _I64, _I64, _I64, _I64, _I64, _P, _I64, _I64, _I, _P, _P]),
@@ -579,6 +581,22 @@ def plan_reduce_batch(nrows: int, ncols: int) -> int:
     """The path weight_batch_dev, mismatch_batch_dev and row_span_batch_dev take for (nrows, ncols) (0 wave per member, 1 workgroup per
     member, 2 chunks of rows and atomics). Host arithmetic."""
     return int(lib().m4ri_amd_plan_reduce_batch(nrows, ncols))
+
+
+def rowspace_weights_batch_dev(G: int, g_stride: int, g_bs: int, k: int, n: int, V: int, v_bs: int, batch: int, w_min: int = 0, hist: int = 0,
+                               lightest: int = 0, stream: int = 0) -> None:
+    """The weights of all 2^k words c_b(x) = V_b ^ x * G_b of `batch` generators G_b (k x n, k <= 40, n <= 1024; g_bs = 0: one shared G;
+    V = 0: no V; v_bs = 0: one shared V), valid bits only, operands read only.  DEVICE int64 outputs, each 0 = not wanted, not both:
+    hist (batch * (n + 1): the number of messages x per weight), lightest (per member: the minimum of (wt << 40) | x over wt >= w_min,
+    -1 if none).  Asynchronous, lock-free and capturable on both paths of plan_rowspace_weights_batch."""
+    _check(lib().m4ri_amd_rowspace_weights_batch_dev(G or None, g_stride, g_bs, k, n, V or None, v_bs, batch, w_min, hist or None, lightest or None,
+                                                     stream), "m4ri_amd_rowspace_weights_batch_dev")
+
+
+def plan_rowspace_weights_batch(k: int, n: int) -> int:
+    """The path rowspace_weights_batch_dev takes for (k, n) (0 a wave per member, 1 a member's messages spread over many waves and
+    global atomics). Host arithmetic."""
+    return int(lib().m4ri_amd_plan_rowspace_weights_batch(k, n))
 
 
 def copy_block_batch_dev(D: int, d_stride: int, d_bs: int, d_row: int, d_col: int, A: int, a_stride: int, a_bs: int, a_row: int, a_col: int,
