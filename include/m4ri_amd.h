@@ -473,7 +473,8 @@ int m4ri_amd_plan_reduce_batch(int64_t nrows, int64_t ncols);
  * lock; capturable.  All results are integer counts and minima: they do not depend on the order the hardware takes the messages in.
  * hipErrorInvalidValue, before any HIP call, for negative sizes, strides or batch strides or w_min < 0, g_stride < words(n) with
  * k > 1, a NULL G with non-empty members (batch > 0, k > 0, n > 0), no output at all, or an output array whose bytes meet the span
- * (first member's start to last member's end) of G, of V or the other output.  batch = 0 succeeds without touching anything. */
+ * (first member's start to last member's end) of G, of V or the other output.  batch = 0 succeeds without touching anything.
+ * For k > 40 see m4ri_amd_row_sums_weights_batch_dev below: the sums of exactly t rows instead of the whole span. */
 int m4ri_amd_rowspace_weights_batch_dev(const word *G, int64_t g_stride, int64_t g_bs, int64_t k, int64_t n, const word *V, int64_t v_bs,
                                         int64_t batch, int64_t w_min, int64_t *hist, int64_t *lightest, void *stream);
 /* which path the call above takes for members of this shape (pure host arithmetic; -1 for negative sizes; sizes beyond the call's
@@ -483,6 +484,38 @@ int m4ri_amd_rowspace_weights_batch_dev(const word *G, int64_t g_stride, int64_t
  * M4RI_AMD_ROWSPACE_PATH0_MAX (clamped to [-1, 26]; -1 = no path 0 for members with columns) replaces it in the routing of a call,
  * read per call; this function does not read it. */
 int m4ri_amd_plan_rowspace_weights_batch(int64_t k, int64_t n);
+/* The weights of all sums of exactly t ROWS of `batch` small matrices (rowsums_batch.hip): the enumeration of Brouwer-Zimmermann
+ * minimum-distance bounds, of Lee-Brickell and Stern information-set decoding and of "any light combination of few rows?" filters,
+ * for generators far beyond the k = 40 of the call above.  The operands are those of that call: member b has G_b, k x n at
+ * G + b * g_bs words, rows g_stride words apart (g_bs = 0: one shared G), and an optional word V_b, 1 x n at V + b * v_bs words
+ * (V == NULL: zero; v_bs = 0: one shared V); only the n valid bits count, G and V are READ ONLY.  For every set
+ * S = {i_0 < i_1 < ... < i_{t-1}} of t row indices below k the word is c_b(S) = V_b ^ the rows of G_b in S, and the rank of S its
+ * colexicographic rank r(S) = sum_j C(i_j, j + 1), 0 .. C(k, t) - 1.  t = 0 is the one sum c = V with rank 0; k < t: no sums.
+ * hist (DEVICE int64, batch * (n + 1) entries, or NULL): hist[b * (n + 1) + w] = the number of S with wt(c_b(S)) = w.  SETS are
+ * counted, not distinct words: every member's entries sum to C(k, t).
+ * lightest (DEVICE int64, batch entries, or NULL): lightest[b] = the minimum over the S with wt(c_b(S)) >= w_min of
+ * (wt << 40) | r(S), -1 if no S qualifies; among equal weights the smallest rank.  At least one of the two outputs is required; both
+ * are written whole, whatever they held.  Members without columns (n = 0) have hist[0] = C(k, t) and lightest 0 if w_min = 0 and
+ * there is a sum, otherwise -1; members without sums have every bin 0 and lightest -1.
+ * Limits: 0 <= k <= 1024, 0 <= n <= 1024, 0 <= t <= 8 and C(k, t) <= 2^40 (the rank fits the key: C(1024, 4) does, C(1024, 5) does
+ * not); beyond any of them the call returns hipErrorNotSupported (801) before any HIP call.
+ * Asynchronous on `stream` on both paths of m4ri_amd_plan_row_sums_weights_batch: plain launches (on path 1 an initialisation of the
+ * outputs goes first, on the same stream), no allocation, no copy to the host, no synchronisation, no engine workspace, no engine
+ * lock; capturable.  All results are integer counts and minima: they do not depend on the order the hardware takes the sums in.
+ * hipErrorInvalidValue, before any HIP call, for negative sizes, strides or batch strides, t < 0 or w_min < 0, g_stride < words(n)
+ * with k > 1, a NULL G with non-empty members that have sums (batch > 0, k >= t >= 1, n > 0), no output at all, or an output array
+ * whose bytes meet the span (first member's start to last member's end) of G, of V or the other output.  batch = 0 succeeds without
+ * touching anything. */
+int m4ri_amd_row_sums_weights_batch_dev(const word *G, int64_t g_stride, int64_t g_bs, int64_t k, int64_t n, const word *V, int64_t v_bs,
+                                        int64_t batch, int64_t t, int64_t w_min, int64_t *hist, int64_t *lightest, void *stream);
+/* which path the call above takes for members of this shape (pure host arithmetic; -1 for negative sizes; sizes beyond the call's
+ * limits are answered by the same rule): 0 a wave walks all sums of its member, four members per workgroup, plain stores, no global
+ * atomics (C(k, t) <= M0; members without columns or sums, and t = 0, count here: an initialisation kernel answers them); 1 a
+ * member's sums are spread over waves, 64 upper parts {i_1 .. i_{t-1}} by a segment of i_0 each, their results combined with global
+ * 64-bit integer atomics after an initialisation kernel.  M0 is a number of sums per member.  The environment variable
+ * M4RI_AMD_ROW_SUMS_PATH0_MAX (clamped to [-1, 2^24]; -1 = no path 0 for members with columns and sums) replaces it in the routing
+ * of a call, read per call; this function does not read it. */
+int m4ri_amd_plan_row_sums_weights_batch(int64_t k, int64_t n, int64_t t);
 /* Assembling, cutting and permuting the members of a batch where they are (assemble_batch.hip).  Conventions of the calls below, as
  * of the other batched calls: member b of X is at X + b * x_bs words, its rows x_stride words apart; a batch stride of 0 on a
  * READ-ONLY operand is one operand shared by all members.  Every call is asynchronous on `stream`: plain launches (several for a

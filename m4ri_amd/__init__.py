@@ -192,6 +192,8 @@ SYMBOLS = {
     "m4ri_amd_plan_reduce_batch": (_I, [_I64, _I64]),
     "m4ri_amd_rowspace_weights_batch_dev": (_I, [_P, _I64, _I64, _I64, _I64, _P, _I64, _I64, _I64, _P, _P, _P]),
     "m4ri_amd_plan_rowspace_weights_batch": (_I, [_I64, _I64]),
+    "m4ri_amd_row_sums_weights_batch_dev": (_I, [_P, _I64, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I64, _P, _P, _P]),
+    "m4ri_amd_plan_row_sums_weights_batch": (_I, [_I64, _I64, _I64]),
     "m4ri_amd_copy_block_batch_dev": (_I, [_P, _I64, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _P]),
     "m4ri_amd_extract_tri_batch_dev": (_I, [_P, _I64, _I64, _P, _I64, _I64, _I64, _I64, _I64, _I, _I, _P, _P]),
     "m4ri_amd_apply_p_left_batch_dev": (_I, [_P, _I64, _I64, _I64, _I64, _I64, _P, _I64, _I64, _I, _P, _P]),
@@ -597,6 +599,51 @@ def plan_rowspace_weights_batch(k: int, n: int) -> int:
     """The path rowspace_weights_batch_dev takes for (k, n) (0 a wave per member, 1 a member's messages spread over many waves and
     global atomics). Host arithmetic."""
     return int(lib().m4ri_amd_plan_rowspace_weights_batch(k, n))
+
+
+def row_sums_weights_batch_dev(G: int, g_stride: int, g_bs: int, k: int, n: int, V: int, v_bs: int, batch: int, t: int, w_min: int = 0,
+                               hist: int = 0, lightest: int = 0, stream: int = 0) -> None:
+    """The weights of all C(k, t) words c_b(S) = V_b ^ (the sum of the t rows of G_b in S) of `batch` generators G_b (k x n, k <= 1024,
+    n <= 1024, t <= 8, C(k, t) <= 2^40; g_bs = 0: one shared G; V = 0: no V; v_bs = 0: one shared V), valid bits only, operands read
+    only.  DEVICE int64 outputs, each 0 = not wanted, not both: hist (batch * (n + 1): the number of sets S per weight), lightest (per
+    member: the minimum of (wt << 40) | colexicographic rank of S over wt >= w_min, -1 if none; row_subset_unrank gives the rows).
+    Asynchronous, lock-free and capturable on both paths of plan_row_sums_weights_batch."""
+    _check(lib().m4ri_amd_row_sums_weights_batch_dev(G or None, g_stride, g_bs, k, n, V or None, v_bs, batch, t, w_min, hist or None,
+                                                     lightest or None, stream), "m4ri_amd_row_sums_weights_batch_dev")
+
+
+def plan_row_sums_weights_batch(k: int, n: int, t: int) -> int:
+    """The path row_sums_weights_batch_dev takes for (k, n, t) (0 a wave per member, 1 a member's sums spread over many waves and
+    global atomics). Host arithmetic."""
+    return int(lib().m4ri_amd_plan_row_sums_weights_batch(k, n, t))
+
+
+def row_subset_rank(rows) -> int:
+    """The colexicographic rank sum_j C(i_j, j + 1) of the set of distinct row indices `rows` (any order): the low 40 bits of
+    row_sums_weights_batch_dev's lightest."""
+    from math import comb
+    s = sorted(int(i) for i in rows)
+    if any(i < 0 for i in s) or any(a == b for a, b in zip(s, s[1:])):
+        raise ValueError("row_subset_rank: the rows must be distinct and not negative")
+    return sum(comb(i, j + 1) for j, i in enumerate(s))
+
+
+def row_subset_unrank(rank: int, t: int) -> tuple:
+    """The t row indices i_0 < ... < i_{t-1} of colexicographic rank `rank`: the inverse of row_subset_rank."""
+    from math import comb
+    if rank < 0 or t < 0 or (t == 0 and rank != 0):
+        raise ValueError("row_subset_unrank: no such set")
+    out = []
+    for m in range(t, 0, -1):  # the largest i with C(i, m) <= rank
+        lo, hi = m - 1, m
+        while comb(hi, m) <= rank:
+            lo, hi = hi, 2 * hi
+        while hi - lo > 1:
+            mid = (lo + hi) // 2
+            lo, hi = (mid, hi) if comb(mid, m) <= rank else (lo, mid)
+        out.append(lo)
+        rank -= comb(lo, m)
+    return tuple(reversed(out))
 
 
 def copy_block_batch_dev(D: int, d_stride: int, d_bs: int, d_row: int, d_col: int, A: int, a_stride: int, a_bs: int, a_row: int, a_col: int,
