@@ -601,6 +601,54 @@ int m4ri_amd_echelonize_batch_dev(word *A, int64_t stride, int64_t a_bs, int64_t
  * number of words, plus a row index and flags, within 160 KiB); 2 one workgroup per member, in place in global memory (valid words
  * up to 512 KiB); 3 members one by one through m4ri_amd_echelonize_dev (blocking) */
 int m4ri_amd_plan_echelonize_batch(int64_t nrows, int64_t ncols);
+/* `batch` (reduced) row echelon forms on COLUMN ORDERS CHOSEN PER MEMBER, one launch, no column ever moved (echelon_order_batch.hip):
+ * the systematic form of a generator on an information set given by the caller, the step before the enumerations of
+ * m4ri_amd_row_sums_weights_batch_dev in information-set decoding (a random set per iteration) and Brouwer-Zimmermann bounds
+ * (successive disjoint sets).  Member b reads A_b, nrows x ncols at A + b * a_bs words, rows a_stride words apart (a_bs = 0: one A
+ * shared by all members), and writes D_b at D + b * d_bs, rows d_stride apart.  A is READ ONLY unless the call is in place: D == A
+ * with equal strides and batch strides, which is allowed (refused with a_bs = 0 and batch > 1); any other meeting of D's span with A's
+ * is refused.  order (DEVICE int32, or NULL): member b's olen entries at order + b * o_bs (o_bs = 0: one order for all members) are the
+ * columns in the order they are visited; NULL is the natural order 0 .. olen-1; 0 <= olen <= ncols.  Entries need not be distinct: a
+ * column visited twice finds no pivot the second time.  An entry outside 0 ... ncols - 1 cannot be checked on the host: such a member
+ * gets rank[b] = -1 and all its pivots -1, and its D_b is NOT written at all (in place: left untouched); no entry ever leads to an
+ * access outside a member.
+ * The rule.  rank = 0; for j = 0 .. olen-1, while rank < pivot_rows, with c = order[j]: the pivot is the first row i,
+ * rank <= i < pivot_rows, with bit c set; if there is none go on with the next j; else swap it up to row `rank`, add it into every
+ * other row with bit c set -- the rows > rank (full == 0) or all rows (full != 0) -- set pivots[b * pm + rank] = c (the column, not
+ * j) and ++rank.  pm = min(pivot_rows, ncols); pivots (DEVICE int32, batch * pm entries, or NULL) is -1 from rank[b] on; rank (DEVICE
+ * int32, batch entries) is required.  0 <= pivot_rows <= nrows: the rows from pivot_rows on only FOLLOW -- never pivots, never swapped,
+ * reduced like any other row with the bit, and below every rank under full == 0.  A received word y stacked under a generator comes
+ * out under full = 1 as y ^ y_I G', the starting error pattern of Lee-Brickell and the V of m4ri_amd_row_sums_weights_batch_dev.
+ * pivot_rows = 0 copies A_b to D_b with rank 0.
+ * order == NULL, olen == ncols, pivot_rows == nrows, in place: m4ri_amd_echelonize_batch_dev bit for bit, words, rank and pivots.
+ * order a permutation of all columns: gathering the columns in that order, mzd_echelonize, and scattering them back, bit for bit.
+ * Only the valid bits of D_b are written: never the bits at columns >= ncols, the words from the width to the stride or the words
+ * between members.  hipErrorInvalidValue, before any HIP call, for negative sizes, strides or batch strides, pivot_rows > nrows,
+ * olen > ncols, a stride below words(ncols), overlapping D members (batch > 1 and d_bs < (nrows - 1) * d_stride + width), D's span
+ * meeting A's (except exactly in place), order, rank or pivots, rank or pivots meeting each other or order, a NULL rank, or a NULL A or
+ * D with non-empty members.  batch = 0 succeeds without touching anything.  Members beyond path 2 of
+ * m4ri_amd_plan_echelonize_order_batch return hipErrorNotSupported (801), nothing touched: there is no one-by-one path.  Asynchronous
+ * on `stream` on every path: one launch (several for a batch beyond one grid), no allocation, no copy to the host, no
+ * synchronisation, no engine lock; capturable. */
+int m4ri_amd_echelonize_order_batch_dev(word *D, int64_t d_stride, int64_t d_bs, const word *A, int64_t a_stride, int64_t a_bs, int64_t nrows,
+                                        int64_t ncols, int64_t pivot_rows, const int32_t *order, int64_t o_bs, int64_t olen, int64_t batch,
+                                        int full, int32_t *rank, int32_t *pivots, void *stream);
+/* which path the call above takes for members of this shape (pure host arithmetic; -1 for negative sizes): 0 one wave per member, lane
+ * i holds row i and lane j order[j] (nrows, ncols <= 64); 1 one workgroup per member, member in LDS (rows padded to an odd number of
+ * words, a row index, flags, 64 bytes of votes and an order of ncols entries, within 160 KiB); 2 one workgroup per member in place in D_b, which the
+ * kernel fills from A_b first when out of place (valid words up to 512 KiB); 3 above that: the call returns 801.  The environment
+ * variables M4RI_AMD_ECH_ORDER_PATH0_MAX (the largest side of path 0, clamped to [0, 64]) and M4RI_AMD_ECH_ORDER_PATH1_MAX (the LDS
+ * bytes of path 1, clamped to [0, 163840]) replace the bounds in the routing of a call, read per call; this function does not read
+ * them. */
+int m4ri_amd_plan_echelonize_order_batch(int64_t nrows, int64_t ncols);
+/* Seeded random column orders for the call above, made on the device: order + b * o_bs (DEVICE int32) receives a permutation of
+ * 0 .. n-1 for every member, defined so that any host reproduces it (m4ri_amd.random_order in the Python layer).  h_j = output number
+ * b * n + j of the counter-form splitmix64 stream seeded `seed` (the stream of m4ri_amd_fill_dev); key_j = h_j with its low 12 bits
+ * replaced by j; the keys sorted ascending as unsigned 64-bit numbers; order[i] = the low 12 bits of the i-th key.  One workgroup per
+ * member sorts in LDS; one launch, asynchronous on `stream`, no allocation; capturable.  0 <= n <= 4096, beyond that
+ * hipErrorNotSupported (801).  hipErrorInvalidValue for negative n, batch or o_bs, o_bs < n with batch > 1, or a NULL order with
+ * batch > 0 and n > 0. */
+int m4ri_amd_random_orders_batch_dev(int32_t *order, int64_t o_bs, int64_t n, int64_t batch, uint64_t seed, void *stream);
 /* `batch` independent systems A_b X_b = B_b (mzd_solve_left, m4ri/solve.c:30-152; solve_batch.hip).  A_b: the m x n matrix at
  * A + b * a_bs, READ ONLY (a_bs = 0: one A shared by all members).  B_b: the max(m, n) x k matrix at B + b * b_bs.  status[b]
  * (DEVICE int32, required): 0, or -1 when A_b X = B_b has no solution, A_b padded with zero rows to max(m, n).  On status 0, B_b is

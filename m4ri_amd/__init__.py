@@ -210,6 +210,9 @@ SYMBOLS = {
     "m4ri_amd_echelonize_dev": (_I, [_P, _I64, _I64, _I64, _I, _P, _P]),
     "m4ri_amd_echelonize_batch_dev": (_I, [_P, _I64, _I64, _I64, _I64, _I64, _I, _P, _P, _P]),
     "m4ri_amd_plan_echelonize_batch": (_I, [_I64, _I64]),
+    "m4ri_amd_echelonize_order_batch_dev": (_I, [_P, _I64, _I64, _P, _I64, _I64, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I, _P, _P, _P]),
+    "m4ri_amd_plan_echelonize_order_batch": (_I, [_I64, _I64]),
+    "m4ri_amd_random_orders_batch_dev": (_I, [_P, _I64, _I64, _I64, ctypes.c_uint64, _P]),
     "m4ri_amd_solve_left_batch_dev": (_I, [_P, _I64, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I64, _P, _P, _P]),
     "m4ri_amd_inv_batch_dev": (_I, [_P, _I64, _I64, _P, _I64, _I64, _I64, _I64, _P, _P]),
     "m4ri_amd_plan_solve_batch": (_I, [_I64, _I64, _I64]),
@@ -722,6 +725,38 @@ def echelonize_batch_dev(A: int, stride: int, a_bs: int, nrows: int, ncols: int,
 def plan_echelonize_batch(nrows: int, ncols: int) -> int:
     """The path echelonize_batch_dev takes for members of this shape (0 wave, 1 LDS, 2 global, 3 one by one). Host arithmetic."""
     return int(lib().m4ri_amd_plan_echelonize_batch(nrows, ncols))
+
+
+def echelonize_order_batch_dev(D: int, d_stride: int, d_bs: int, A: int, a_stride: int, a_bs: int, nrows: int, ncols: int, pivot_rows: int,
+                               order: int, o_bs: int, olen: int, batch: int, full: int, rank: int, pivots: int = 0, stream: int = 0) -> None:
+    """`batch` (reduced) row echelon forms on column orders chosen per member, no column moved: D_b <- the form of A_b (a_bs = 0: one
+    shared A; D == A with equal strides: in place) with the columns visited in the order of member b's olen DEVICE int32 entries at
+    order + b * o_bs (o_bs = 0: one order; order 0: the natural order).  Rows from pivot_rows on only follow.  rank / pivots: DEVICE
+    int32 arrays (pivots 0 = not wanted, else batch * min(pivot_rows, ncols) pivot COLUMNS); a member with an entry out of range has
+    rank -1 and is not written.  Asynchronous, lock-free and capturable on paths 0-2 of plan_echelonize_order_batch; path 3: 801."""
+    _check(lib().m4ri_amd_echelonize_order_batch_dev(D or None, d_stride, d_bs, A or None, a_stride, a_bs, nrows, ncols, pivot_rows, order or None, o_bs,
+                                                     olen, batch, int(full), rank or None, pivots or None, stream), "m4ri_amd_echelonize_order_batch_dev")
+
+
+def plan_echelonize_order_batch(nrows: int, ncols: int) -> int:
+    """The path echelonize_order_batch_dev takes for members of this shape (0 wave, 1 LDS, 2 global, 3 not supported). Host
+    arithmetic."""
+    return int(lib().m4ri_amd_plan_echelonize_order_batch(nrows, ncols))
+
+
+def random_orders_batch_dev(order: int, o_bs: int, n: int, batch: int, seed: int, stream: int = 0) -> None:
+    """order + b * o_bs (DEVICE int32) <- random_order(seed, b, n) for every member, n <= 4096.  Asynchronous and capturable."""
+    _check(lib().m4ri_amd_random_orders_batch_dev(order or None, o_bs, n, batch, seed & 0xFFFFFFFFFFFFFFFF, stream), "m4ri_amd_random_orders_batch_dev")
+
+
+def random_order(seed: int, b: int, n: int):
+    """The permutation of 0 .. n-1 (NumPy int32) that random_orders_batch_dev gives member b: outputs b * n .. b * n + n - 1 of the
+    splitmix64 stream seeded `seed`, the low 12 bits of output j replaced by j, sorted ascending; the low 12 bits of the sorted keys."""
+    import numpy as np
+    if not 0 <= n <= 4096:
+        raise ValueError("random_order: 0 <= n <= 4096")
+    keys = (splitmix_words(seed, b * n, n) & ~np.uint64(4095)) | np.arange(n, dtype=np.uint64)
+    return (np.sort(keys) & np.uint64(4095)).astype(np.int32)
 
 
 def solve_left_batch_dev(A: int, a_stride: int, a_bs: int, m: int, n: int, B: int, b_stride: int, b_bs: int, k: int, batch: int, status: int,
