@@ -516,6 +516,50 @@ int m4ri_amd_row_sums_weights_batch_dev(const word *G, int64_t g_stride, int64_t
  * M4RI_AMD_ROW_SUMS_PATH0_MAX (clamped to [-1, 2^24]; -1 = no path 0 for members with columns and sums) replaces it in the routing
  * of a call, read per call; this function does not read it. */
 int m4ri_amd_plan_row_sums_weights_batch(int64_t k, int64_t n, int64_t t);
+/* The collision step of Stern's / Dumer's information-set decoding on `batch` small matrices (rowsums_collide_batch.hip): of the
+ * pairs (t1 rows of one half, t2 rows of the other) only those whose sum vanishes on a window of ell chosen columns are weighed.
+ * G, V, the stride and batch strides, sharing with a batch stride of 0, "only the n valid bits count" and READ ONLY are those of
+ * m4ri_amd_row_sums_weights_batch_dev above.  Rows 0 .. k1-1 of a member are its LEFT rows, rows k1 .. k-1 its RIGHT rows,
+ * k2 = k - k1.  S1 is a set of t1 left rows, r1 its colexicographic rank; S2 a set of t2 right rows, r2 the colexicographic rank
+ * of {i - k1 : i in S2}; N1 = C(k1, t1), N2 = C(k2, t2), the empty set the one set of rank 0.  The word of the pair is
+ * c_b(S1, S2) = V_b ^ the rows of G_b in S1 ^ those in S2.
+ * cols (DEVICE int32, or NULL): member b's window, ell column indices at cols + b * c_bs entries (c_bs = 0: one window for all
+ * members; NULL: the columns 0 .. ell-1); the entries need not be sorted, distinct or adjacent.  The pair COLLIDES iff c is 0 at
+ * every window column; with ell = 0 every pair collides.
+ * hist (DEVICE int64, batch * (n + 1) entries, or NULL): hist[b * (n + 1) + w] = the number of colliding pairs with wt(c) = w, the
+ * weight over all n columns: a member's entries sum to its number of collisions.
+ * lightest (DEVICE int64, batch entries, or NULL): lightest[b] = the minimum over the colliding pairs with wt(c) >= w_min of
+ * (wt << 40) | (r1 * N2 + r2), -1 if there is none.  At least one of the two outputs is required; both are written whole.
+ * A window entry outside 0 .. n-1 cannot be seen by the host, so the device decides: that member is REFUSED, every one of its hist
+ * entries is -1 and its lightest -2, whatever pairs it has; nothing outside the member is read, the other members are unaffected.
+ * Members without pairs (N1 = 0 or N2 = 0: t1 > k1 or t2 > k2) have every bin 0 and lightest -1; n = 0 with ell = 0 puts all
+ * N1 * N2 pairs into bin 0 (lightest 0 if w_min = 0 and there is a pair); batch = 0 succeeds without touching anything.
+ * Limits: k <= 1024, n <= 1024, t1, t2 <= 8, ell <= 64, N1 * N2 <= 2^40 (the pair rank fits the key) and N1 <= 8192 (the left list
+ * is tabled in one workgroup's LDS: C(128, 2) = 8128 fits, C(129, 2) = 8256 does not); beyond any of them the call returns
+ * hipErrorNotSupported (801) before any HIP call.  Every workgroup tables the left list and walks the right one: THE HALF WITH FEWER
+ * SUMS BELONGS FIRST.
+ * Asynchronous on `stream` on both paths of m4ri_amd_plan_row_sums_collide_batch: plain launches (on path 1 an initialisation of the
+ * outputs goes first, on the same stream), no allocation, no copy to the host, no synchronisation, no engine workspace, no engine
+ * lock; capturable.  All results are integer counts and minima: they do not depend on the order the hardware takes the pairs in.
+ * hipErrorInvalidValue, before any HIP call, for negative sizes, strides or batch strides, k1 > k, t1, t2, ell or w_min < 0, a NULL
+ * cols with ell > n, g_stride < words(n) with k > 1, a NULL G where rows are read (batch > 0, n > 0, pairs, t1 + t2 >= 1), no output
+ * at all, or an output array whose bytes meet the span (first member's start to last member's end) of G, of V, of cols or the other
+ * output. */
+int m4ri_amd_row_sums_collide_batch_dev(const word *G, int64_t g_stride, int64_t g_bs, int64_t k, int64_t n, const word *V, int64_t v_bs,
+                                        int64_t batch, int64_t k1, int64_t t1, int64_t t2, const int32_t *cols, int64_t c_bs, int64_t ell,
+                                        int64_t w_min, int64_t *hist, int64_t *lightest, void *stream);
+/* which path the call above takes for members of this shape (pure host arithmetic; -1 for negative sizes or k1 > k; sizes beyond the
+ * call's limits are answered by the same rule): 0 one workgroup takes the member's whole right list and writes its outputs with
+ * plain stores, no global atomics (N1 * N2 <= P0; members without pairs or columns count here: an initialisation kernel answers
+ * them); 1 the right list is cut into slices, a workgroup each, every one with its own left table, their results combined with
+ * global 64-bit integer atomics after an initialisation kernel.  P0 is a number of pairs per member.  The environment variable
+ * M4RI_AMD_ROW_SUMS_COLLIDE_PATH0_MAX (clamped to [-1, 2^32 - 1]; -1 = no path 0 for members with columns and pairs) replaces it in
+ * the routing of a call, read per call; this function does not read it. */
+int m4ri_amd_plan_row_sums_collide_batch(int64_t k, int64_t n, int64_t k1, int64_t t1, int64_t t2, int64_t ell);
+/* the workgroups per member of the call above on path 1, whichever path the shape is routed to: the right list in slices of at least
+ * max(N1, 256) sums, as many as bring the call to 1024 workgroups, a slice times N1 below 2^32.  0 for members without pairs or
+ * columns or with N1 > 8192, -1 for negative sizes. */
+int64_t m4ri_amd_row_sums_collide_slices(int64_t k, int64_t n, int64_t k1, int64_t t1, int64_t t2, int64_t ell, int64_t batch);
 /* Assembling, cutting and permuting the members of a batch where they are (assemble_batch.hip).  Conventions of the calls below, as
  * of the other batched calls: member b of X is at X + b * x_bs words, its rows x_stride words apart; a batch stride of 0 on a
  * READ-ONLY operand is one operand shared by all members.  Every call is asynchronous on `stream`: plain launches (several for a

@@ -194,6 +194,9 @@ SYMBOLS = {
     "m4ri_amd_plan_rowspace_weights_batch": (_I, [_I64, _I64]),
     "m4ri_amd_row_sums_weights_batch_dev": (_I, [_P, _I64, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I64, _P, _P, _P]),
     "m4ri_amd_plan_row_sums_weights_batch": (_I, [_I64, _I64, _I64]),
+    "m4ri_amd_row_sums_collide_batch_dev": (_I, [_P, _I64, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I64, _I64, _P, _I64, _I64, _I64, _P, _P, _P]),
+    "m4ri_amd_plan_row_sums_collide_batch": (_I, [_I64, _I64, _I64, _I64, _I64, _I64]),
+    "m4ri_amd_row_sums_collide_slices": (_I64, [_I64, _I64, _I64, _I64, _I64, _I64, _I64]),
     "m4ri_amd_copy_block_batch_dev": (_I, [_P, _I64, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _P]),
     "m4ri_amd_extract_tri_batch_dev": (_I, [_P, _I64, _I64, _P, _I64, _I64, _I64, _I64, _I64, _I, _I, _P, _P]),
     "m4ri_amd_apply_p_left_batch_dev": (_I, [_P, _I64, _I64, _I64, _I64, _I64, _P, _I64, _I64, _I, _P, _P]),
@@ -647,6 +650,52 @@ def row_subset_unrank(rank: int, t: int) -> tuple:
         out.append(lo)
         rank -= comb(lo, m)
     return tuple(reversed(out))
+
+
+def row_sums_collide_batch_dev(G: int, g_stride: int, g_bs: int, k: int, n: int, V: int, v_bs: int, batch: int, k1: int, t1: int, t2: int,
+                               cols: int = 0, c_bs: int = 0, ell: int = 0, w_min: int = 0, hist: int = 0, lightest: int = 0, stream: int = 0) -> None:
+    """Stern's collision step on `batch` generators G_b (k x n; operands as in row_sums_weights_batch_dev): of the N1 * N2 pairs (S1: t1
+    of the left rows 0 .. k1-1, rank r1 < N1 = C(k1, t1); S2: t2 of the right rows k1 .. k-1, rank r2 < N2 = C(k - k1, t2) of {i - k1})
+    those whose word V_b ^ rows S1 ^ rows S2 is 0 at the ell window columns (cols: DEVICE int32, member b's at cols + b * c_bs entries,
+    c_bs = 0: one window, cols = 0: columns 0 .. ell-1) are weighed over all n columns.  DEVICE int64 outputs, each 0 = not wanted, not
+    both: hist (batch * (n + 1): the number of colliding pairs per weight), lightest (per member: the minimum of
+    (wt << 40) | (r1 * N2 + r2) over wt >= w_min, -1 if none; row_pair_unrank gives the rows).  A member with a window entry outside
+    0 .. n-1 is refused on the device: hist all -1, lightest -2.  k, n <= 1024, t1, t2 <= 8, ell <= 64, N1 <= 8192, N1 * N2 <= 2^40: the
+    half with fewer sums belongs first.  Asynchronous, lock-free and capturable on both paths of plan_row_sums_collide_batch."""
+    _check(lib().m4ri_amd_row_sums_collide_batch_dev(G or None, g_stride, g_bs, k, n, V or None, v_bs, batch, k1, t1, t2, cols or None, c_bs, ell,
+                                                     w_min, hist or None, lightest or None, stream), "m4ri_amd_row_sums_collide_batch_dev")
+
+
+def plan_row_sums_collide_batch(k: int, n: int, k1: int, t1: int, t2: int, ell: int) -> int:
+    """The path row_sums_collide_batch_dev takes (0 one workgroup per member, plain stores; 1 the right list in slices, a workgroup each,
+    and global atomics). Host arithmetic."""
+    return int(lib().m4ri_amd_plan_row_sums_collide_batch(k, n, k1, t1, t2, ell))
+
+
+def row_sums_collide_slices(k: int, n: int, k1: int, t1: int, t2: int, ell: int, batch: int) -> int:
+    """The workgroups per member of row_sums_collide_batch_dev on path 1: the slices of the right list. Host arithmetic."""
+    return int(lib().m4ri_amd_row_sums_collide_slices(k, n, k1, t1, t2, ell, batch))
+
+
+def row_pair_rank(S1, S2, k1: int, k: int, t2: int) -> int:
+    """The pair rank r1 * N2 + r2 of row_sums_collide_batch_dev's lightest: S1 of the rows 0 .. k1-1, S2 (t2 of them) of the rows
+    k1 .. k-1, both as absolute row indices in any order; N2 = C(k - k1, t2)."""
+    from math import comb
+    S1, S2 = [int(i) for i in S1], [int(i) for i in S2]
+    if not 0 <= k1 <= k or len(S2) != t2 or any(not 0 <= i < k1 for i in S1) or any(not k1 <= i < k for i in S2):
+        raise ValueError("row_pair_rank: S1 lies in the rows below k1, S2 has t2 of the rows k1 .. k-1")
+    return row_subset_rank(S1) * comb(k - k1, t2) + row_subset_rank(i - k1 for i in S2)
+
+
+def row_pair_unrank(rank: int, k1: int, k: int, t1: int, t2: int) -> tuple:
+    """The inverse of row_pair_rank: (S1, S2), the absolute row indices of both sets, each ascending."""
+    from math import comb
+    if not 0 <= k1 <= k or t1 < 0 or t2 < 0:
+        raise ValueError("row_pair_unrank: no such pair")
+    n1, n2 = comb(k1, t1), comb(k - k1, t2)
+    if not 0 <= rank < n1 * n2:
+        raise ValueError("row_pair_unrank: no such pair")
+    return row_subset_unrank(rank // n2, t1), tuple(i + k1 for i in row_subset_unrank(rank % n2, t2))
 
 
 def copy_block_batch_dev(D: int, d_stride: int, d_bs: int, d_row: int, d_col: int, A: int, a_stride: int, a_bs: int, a_row: int, a_col: int,

@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "csrc", "_obj")
 LIB = os.path.join(HERE, "libm4ri_amd.so")
-SOURCES = ["m4rm_leaf.hip", "a4_pack.hip", "m4rm8q_leaf.hip", "m4rm_small.hip", "aux_kernels.hip", "scheme_passes.hip", "engine.hip", "mzd_api.hip", "multi.hip", "trsm.hip", "ple.hip", "elim.hip", "echelon.hip", "echelon_batch.hip", "echelon_order_batch.hip", "solve.hip", "solve_batch.hip", "ple_batch.hip", "mul_small_batch.hip", "transpose.hip", "transpose_batch.hip", "reduce_batch.hip", "rowspace_batch.hip", "rowsums_batch.hip", "assemble_batch.hip", "io.cpp", "small_host.cpp", "host_pipeline_plan.cpp"]
+SOURCES = ["m4rm_leaf.hip", "a4_pack.hip", "m4rm8q_leaf.hip", "m4rm_small.hip", "aux_kernels.hip", "scheme_passes.hip", "engine.hip", "mzd_api.hip", "multi.hip", "trsm.hip", "ple.hip", "elim.hip", "echelon.hip", "echelon_batch.hip", "echelon_order_batch.hip", "solve.hip", "solve_batch.hip", "ple_batch.hip", "mul_small_batch.hip", "transpose.hip", "transpose_batch.hip", "reduce_batch.hip", "rowspace_batch.hip", "rowsums_batch.hip", "rowsums_collide_batch.hip", "assemble_batch.hip", "io.cpp", "small_host.cpp", "host_pipeline_plan.cpp"]
 # The test-only library of the fused passes (tests/pass_lib.py binds it; it is not API and not part of the product): the objects of the
 # pass sources linked a second time, with the internal launchers the pass tests call as its only exports.  libm4ri_amd.so keeps them local.
 PASS_LIB = os.path.join(HERE, "libm4ri_amd_passes.so")
@@ -91,7 +91,7 @@ def _stale(target: str, deps: list[str]) -> bool:
 def build(force: bool = False, verbose: bool = True) -> str:
     hipcc = _hipcc()
     os.makedirs(OBJ, exist_ok=True)
-    headers = [os.path.join(CSRC, "gf2_common.h"), os.path.join(CSRC, "gf2_internal.h"), os.path.join(CSRC, "batch_common.h"), os.path.join(CSRC, "dev_scratch.h"), os.path.join(CSRC, "row_gather.h"), os.path.join(CSRC, "transpose_block.h"), os.path.join(CSRC, "scheme444.h"), os.path.join(HERE, "..", "include", "m4ri_amd.h")]
+    headers = [os.path.join(CSRC, "gf2_common.h"), os.path.join(CSRC, "gf2_internal.h"), os.path.join(CSRC, "batch_common.h"), os.path.join(CSRC, "dev_scratch.h"), os.path.join(CSRC, "row_gather.h"), os.path.join(CSRC, "subset_rank.h"), os.path.join(CSRC, "transpose_block.h"), os.path.join(CSRC, "scheme444.h"), os.path.join(HERE, "..", "include", "m4ri_amd.h")]
     jobs = []
     for src in SOURCES:
         s = os.path.join(CSRC, src)

@@ -35,14 +35,11 @@
 #include <limits.h>
 #include <stdlib.h>
 #include "batch_common.h"
+#include "subset_rank.h"  // the limits RS_*_MAX, binom_capped, binom_elem, unrank_step
 #include "../../include/m4ri_amd.h"
 
 namespace {
 
-constexpr int64_t RS_K_MAX    = 1024;  // a row index in the 10 low bits of the lane's 32-bit minimum
-constexpr int64_t RS_N_MAX    = 1024;  // a word in at most 16 register words (32 VGPRs) per lane
-constexpr int64_t RS_T_MAX    = 8;
-constexpr int64_t RS_SUMS_MAX = (int64_t)1 << 40;  // the rank fits the key's low 40 bits
 // Path 0 up to this many sums per member.  Measured (tools/bench_row_sums_weights.py, profiles/row_sums_weights_bench.txt)
 // at about 2^24 sums per call and n = 256, t = 2 and 3, with and without hist, the spreads of these rows under 1 %: path 0 is ahead of
 // path 1 by 11 % ... 4.1x at 120 ... 16 471 sums per member (k = 182, t = 2: 1.11x and 1.27x), each time by more than the spread, and
@@ -55,38 +52,6 @@ constexpr int RS_ROW_WORDS    = 1024;  // the staged rows of a wave: 8 KiB, a se
 constexpr int64_t RS_BIN_WORDS = 2048; // the bins of a wave, all copies: 8 KiB
 constexpr int RS_SEG_MIN       = 16;   // path 1 halves its segments down to this many rows ...
 constexpr int64_t RS_BLOCKS_MIN = 1024; // ... while the call has fewer workgroups than this: four per compute unit
-
-// C(c, m) for m = 1 .. 8 and c < 1024, held at 2^62 where it is larger: a rank below 2^40 never meets such an entry
-struct BinomTable {
-  unsigned long long c[RS_T_MAX][RS_K_MAX];
-};
-constexpr BinomTable make_binom_table() {
-  BinomTable t{};
-  const unsigned long long cap = 1ull << 62;
-  for (int i = 0; i < RS_K_MAX; ++i) t.c[0][i] = (unsigned long long)i;
-  for (int m = 1; m < RS_T_MAX; ++m) {
-    t.c[m][0] = 0;
-    for (int i = 1; i < RS_K_MAX; ++i) {  // Pascal: C(i, m + 1) = C(i - 1, m + 1) + C(i - 1, m)
-      const unsigned long long s = t.c[m][i - 1] + t.c[m - 1][i - 1];
-      t.c[m][i]                  = s > cap ? cap : s;
-    }
-  }
-  return t;
-}
-__device__ const BinomTable rs_binom = make_binom_table();
-
-// C(k, t) on the host, held at 2^41 from the first partial product above 2^40 on (the partial products C(k - t + j, j) only grow)
-int64_t binom_capped(int64_t k, int64_t t) {
-  if (t < 0 || k < t) return 0;
-  if (t > k - t) t = k - t;
-  int64_t r = 1;
-  for (int64_t j = 1; j <= t; ++j) {
-    const __int128 x = (__int128)r * (k - t + j) / j;
-    if (x > RS_SUMS_MAX) return RS_SUMS_MAX * 2;
-    r = (int64_t)x;
-  }
-  return r;
-}
 
 struct RsArgs {
   const word *G, *V;  // V may be NULL
@@ -105,15 +70,6 @@ struct RsArgs {
   int64_t *hist, *lightest;
   int64_t u0, units;   // this launch: from u0 on, of `units`; path 0: waves, a member each; path 1: batch * n_ucg * n_seg workgroups
 };
-
-// C(e, j) of an element e < 1024: j <= 3 is arithmetic (so t <= 3 reads no table), above from the table
-__device__ __forceinline__ unsigned long long binom_elem(int e, int j) {
-  const uint32_t x = (uint32_t)e;
-  if (j == 1) return x;
-  if (j == 2) return (x * (x - 1)) >> 1;                                        // e = 0: 0 * (2^32 - 1) = 0
-  if (j == 3) return e < 3 ? 0 : (unsigned long long)((x * (x - 1)) >> 1) * (x - 2) / 3;
-  return rs_binom.c[j - 1][e];
-}
 
 // Path 0: wave u is member u, stages its own segments and takes every (segment, chunk) of its member.  Path 1: workgroup u is
 // (member, four consecutive chunks, segment); its waves share one staged segment, four times as long, and take a chunk each.
@@ -178,24 +134,7 @@ __global__ __launch_bounds__(BATCH_WAVE_THREADS) void rs_kernel(RsArgs p) {
       int e = k;  // the element above the one looked for; after the loop, the smallest element: i_1 (t = 1: the row)
       if (valid) {
         for (int m = tu; m >= 1; --m) {  // the largest e' < e with C(e', m) <= rest
-          int lo = m - 1, hi = e;        // C(m - 1, m) = 0
-          if (m == 1) lo = (int)rest;
-          else if (m == 2) {  // C(lo, 2) <= rest < C(lo + 1, 2): the root in double (8 rest + 1 < 2^44 is exact), then made sure of
-            lo = (int)((1.0 + sqrt(8.0 * (double)rest + 1.0)) * 0.5);
-            lo = lo < 1 ? 1 : lo > hi - 1 ? hi - 1 : lo;
-            while (binom_elem(lo, 2) > rest) --lo;
-            while (lo + 1 < hi && binom_elem(lo + 1, 2) <= rest) ++lo;
-            rest -= binom_elem(lo, 2);
-          } else {
-            const unsigned long long *col = rs_binom.c[m - 1];
-            while (hi - lo > 1) {
-              const int mid = (lo + hi) >> 1;
-              if (col[mid] <= rest) lo = mid;
-              else hi = mid;
-            }
-            rest -= col[lo];
-          }
-          e = lo;
+          e = unrank_step(rest, m, e);
           base += binom_elem(e, m + boff);
           const word *r = g + (int64_t)e * p.g_stride;
 #pragma unroll
