@@ -560,6 +560,56 @@ int m4ri_amd_plan_row_sums_collide_batch(int64_t k, int64_t n, int64_t k1, int64
  * max(N1, 256) sums, as many as bring the call to 1024 workgroups, a slice times N1 below 2^32.  0 for members without pairs or
  * columns or with N1 > 8192, -1 for negative sizes. */
 int64_t m4ri_amd_row_sums_collide_slices(int64_t k, int64_t n, int64_t k1, int64_t t1, int64_t t2, int64_t ell, int64_t batch);
+/* m4ri_amd_row_sums_collide_batch_dev with a LIST of the light colliding pairs beside its two outputs.  Every name, stride, sharing
+ * rule (a batch stride of 0), "only the n valid bits count", READ ONLY, the limits, the ranks, the window, the refused members, the
+ * paths, the slices and the routing variable are those of that call; hist and lightest (each may be NULL) mean what they mean there,
+ * and lightest ignores w_max.  A colliding pair QUALIFIES iff w_min <= wt(c) <= w_max; a w_max above n is n.
+ * count (DEVICE int64, batch entries): count[b] = the number of qualifying pairs of member b, the TRUE total however small cap is, so
+ * that the caller sees an overflow and can come back with a larger list.  With hist given it is the sum of hist over w_min .. w_max.
+ * list (DEVICE int64, member b's entries at list + b * l_bs, cap of them): the entries i < min(count[b], cap) are DISTINCT keys
+ * (wt << 40) | (r1 * N2 + r2) of qualifying pairs, in no particular order.  count[b] <= cap: they are all of them.  count[b] > cap:
+ * some cap of them; which ones is not specified and may differ from run to run.  The entries from min(count[b], cap) on are NOT
+ * written.  m4ri_amd_row_sums_words_batch_dev below turns the keys into words.  ell = 0, t2 = 0, k1 = k lists the sums of
+ * m4ri_amd_row_sums_weights_batch_dev in a weight band.
+ * list and count come together; list may be NULL only with cap = 0, and then count alone is a filtered count.  At least one of hist,
+ * lightest and count is required.
+ * A REFUSED member has count -1 and no list entry written (hist and lightest in their refused forms); a member without pairs count 0;
+ * n = 0 with ell = 0: count = N1 * N2 if w_min = 0, else 0, and the first min(count, cap) entries are the keys 0, 1, ... (weight 0,
+ * the pair ranks in order); batch = 0 succeeds without touching anything.
+ * Asynchronous on `stream` and capturable on both paths, as the call above: no allocation, no copy to the host, no synchronisation,
+ * no engine lock.  Path 0 takes the slots from a counter in the workgroup's LDS and writes count[b] once, with a plain store: no
+ * global atomic.  Path 1 sets count in its initialisation kernel and takes every slot with one returning 64-bit global atomic add,
+ * which bounds the rate where nearly every pair qualifies; the call is meant for ell >= log2 N1 and a w_max at the
+ * target weight, where a member lists a handful of keys.
+ * hipErrorInvalidValue, before any HIP call, for whatever the call above refuses, a negative w_max, cap or l_bs, l_bs < cap with
+ * batch > 1 (count given), a list without a count, a count without a list at cap > 0, none of the three outputs, or an output (hist,
+ * lightest, count, the list's span from its first member's start to the last member's cap-th entry) whose bytes meet another output
+ * or the span of G, of V or of cols.  hipErrorNotSupported as above.  cap is otherwise unbounded; the indexing is 64-bit. */
+int m4ri_amd_row_sums_collide_list_batch_dev(const word *G, int64_t g_stride, int64_t g_bs, int64_t k, int64_t n, const word *V, int64_t v_bs,
+                                             int64_t batch, int64_t k1, int64_t t1, int64_t t2, const int32_t *cols, int64_t c_bs, int64_t ell,
+                                             int64_t w_min, int64_t w_max, int64_t *hist, int64_t *lightest, int64_t *list, int64_t l_bs,
+                                             int64_t cap, int64_t *count, void *stream);
+/* The words behind listed keys, on the device (rowsums_words_batch.hip).  G, V, k, n, k1, t1, t2, the strides and the ranks are those
+ * of m4ri_amd_row_sums_collide_batch_dev; t2 = 0, k1 = k serves the keys of m4ri_amd_row_sums_weights_batch_dev, which are ranks of
+ * t-sets.  keys (DEVICE int64): member b's at keys + b * l_bs entries.  count (DEVICE int64, batch entries, or NULL): member b has
+ * m_b = min(max(count[b], 0), cap) keys, so a refused member's -1 reads as 0 and a count beyond cap as cap; NULL: cap keys per member.
+ * W: member b's rows at W + b * w_bs words, w_stride words apart.  For i < m_b let r = keys[b * l_bs + i] & (2^40 - 1): the weight
+ * bits above are ignored.  Row i of W_b becomes V_b ^ rows S1 ^ rows S2 of the pair of rank r = r1 * N2 + r2.  Only the n valid bits
+ * are written: bits at columns >= n, padding words, the rows from m_b on and the gaps keep what they held.
+ * A key cannot be seen by the host, so the device decides: if keys[...] < 0 or r >= N1 * N2 the row is SKIPPED, it is not written and
+ * no row index is formed from the key.  skipped (DEVICE int32, batch entries, or NULL): skipped[b] = the number of such rows, written
+ * whole, 0 for a clean member.
+ * Limits: k, n <= 1024, t1, t2 <= 8, N1 * N2 <= 2^40; there is no bound on N1, nothing is tabled.  Beyond them hipErrorNotSupported
+ * (801) before any HIP call.
+ * Asynchronous on `stream`: a memset of skipped and plain launches, no allocation, no copy to the host, no synchronisation, no engine
+ * lock; capturable.  count and keys are read on the device, so they may come from a call still in flight on the same stream.
+ * hipErrorInvalidValue, before any HIP call, for negative sizes, strides or batch strides, k1 > k, g_stride < words(n) with k > 1,
+ * w_stride < words(n) with cap > 1, with batch > 1 and cap > 0 an l_bs < cap or a w_bs below (cap - 1) * w_stride + words(n), a NULL
+ * keys, W (n > 0) or G (where rows are read) with batch > 0 and cap > 0, or a W or skipped whose bytes meet the span of G, V, keys,
+ * count or each other.  batch = 0 succeeds without touching anything; cap = 0 writes skipped only. */
+int m4ri_amd_row_sums_words_batch_dev(const word *G, int64_t g_stride, int64_t g_bs, int64_t k, int64_t n, const word *V, int64_t v_bs,
+                                      int64_t batch, int64_t k1, int64_t t1, int64_t t2, const int64_t *keys, int64_t l_bs, int64_t cap,
+                                      const int64_t *count, word *W, int64_t w_stride, int64_t w_bs, int32_t *skipped, void *stream);
 /* Assembling, cutting and permuting the members of a batch where they are (assemble_batch.hip).  Conventions of the calls below, as
  * of the other batched calls: member b of X is at X + b * x_bs words, its rows x_stride words apart; a batch stride of 0 on a
  * READ-ONLY operand is one operand shared by all members.  Every call is asynchronous on `stream`: plain launches (several for a

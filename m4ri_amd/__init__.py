@@ -195,6 +195,9 @@ SYMBOLS = {
     "m4ri_amd_row_sums_weights_batch_dev": (_I, [_P, _I64, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I64, _P, _P, _P]),
     "m4ri_amd_plan_row_sums_weights_batch": (_I, [_I64, _I64, _I64]),
     "m4ri_amd_row_sums_collide_batch_dev": (_I, [_P, _I64, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I64, _I64, _P, _I64, _I64, _I64, _P, _P, _P]),
+    "m4ri_amd_row_sums_collide_list_batch_dev": (_I, [_P, _I64, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I64, _P, _P, _P,
+                                                      _I64, _I64, _P, _P]),
+    "m4ri_amd_row_sums_words_batch_dev": (_I, [_P, _I64, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I64, _I64, _P, _I64, _I64, _P, _P, _I64, _I64, _P, _P]),
     "m4ri_amd_plan_row_sums_collide_batch": (_I, [_I64, _I64, _I64, _I64, _I64, _I64]),
     "m4ri_amd_row_sums_collide_slices": (_I64, [_I64, _I64, _I64, _I64, _I64, _I64, _I64]),
     "m4ri_amd_copy_block_batch_dev": (_I, [_P, _I64, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _P]),
@@ -664,6 +667,31 @@ def row_sums_collide_batch_dev(G: int, g_stride: int, g_bs: int, k: int, n: int,
     half with fewer sums belongs first.  Asynchronous, lock-free and capturable on both paths of plan_row_sums_collide_batch."""
     _check(lib().m4ri_amd_row_sums_collide_batch_dev(G or None, g_stride, g_bs, k, n, V or None, v_bs, batch, k1, t1, t2, cols or None, c_bs, ell,
                                                      w_min, hist or None, lightest or None, stream), "m4ri_amd_row_sums_collide_batch_dev")
+
+
+def row_sums_collide_list_batch_dev(G: int, g_stride: int, g_bs: int, k: int, n: int, V: int, v_bs: int, batch: int, k1: int, t1: int, t2: int,
+                                    cols: int = 0, c_bs: int = 0, ell: int = 0, w_min: int = 0, w_max: int = 1024, hist: int = 0, lightest: int = 0,
+                                    list: int = 0, l_bs: int = 0, cap: int = 0, count: int = 0, stream: int = 0) -> None:
+    """row_sums_collide_batch_dev with a list: the colliding pairs with w_min <= wt <= w_max (w_max above n is n; lightest ignores it).
+    DEVICE int64 outputs: count (batch entries: the true number of qualifying pairs per member, -1 for a refused member) and list (member
+    b's at list + b * l_bs entries: the first min(count[b], cap) are distinct keys (wt << 40) | (r1 * N2 + r2) of qualifying pairs in no
+    order, all of them if count[b] <= cap; the entries behind are not written).  They come together; list = 0 only with cap = 0 (a
+    filtered count).  hist and lightest as in row_sums_collide_batch_dev, each 0 = not wanted; one of hist, lightest, count is required.
+    row_sums_words_batch_dev turns the keys into words.  Asynchronous, lock-free and capturable on both paths."""
+    _check(lib().m4ri_amd_row_sums_collide_list_batch_dev(G or None, g_stride, g_bs, k, n, V or None, v_bs, batch, k1, t1, t2, cols or None, c_bs, ell,
+                                                          w_min, w_max, hist or None, lightest or None, list or None, l_bs, cap, count or None,
+                                                          stream), "m4ri_amd_row_sums_collide_list_batch_dev")
+
+
+def row_sums_words_batch_dev(G: int, g_stride: int, g_bs: int, k: int, n: int, V: int, v_bs: int, batch: int, k1: int, t1: int, t2: int, keys: int,
+                             l_bs: int, cap: int, count: int, W: int, w_stride: int, w_bs: int, skipped: int = 0, stream: int = 0) -> None:
+    """The words of listed keys on the device: for i < m_b = min(max(count[b], 0), cap) (count = 0: cap keys per member) row i of W_b
+    (rows w_stride words apart, members w_bs) becomes V_b ^ rows S1 ^ rows S2 of the pair of rank keys[b * l_bs + i] & (2^40 - 1); only the
+    n valid bits are written.  t2 = 0, k1 = k: the keys of row_sums_weights_batch_dev.  A key < 0 or with a rank >= N1 * N2 is skipped
+    on the device (its row is not written) and counted in skipped (DEVICE int32, batch entries, 0 = not wanted).  k, n <= 1024,
+    t1, t2 <= 8, N1 * N2 <= 2^40.  Asynchronous, lock-free and capturable."""
+    _check(lib().m4ri_amd_row_sums_words_batch_dev(G or None, g_stride, g_bs, k, n, V or None, v_bs, batch, k1, t1, t2, keys or None, l_bs, cap,
+                                                   count or None, W or None, w_stride, w_bs, skipped or None, stream), "m4ri_amd_row_sums_words_batch_dev")
 
 
 def plan_row_sums_collide_batch(k: int, n: int, k1: int, t1: int, t2: int, ell: int) -> int:

@@ -28,6 +28,14 @@
 //      initialisation kernel on the same stream (which also answers the refused members: their workgroups return without writing) and
 //      combined with global 64-bit integer atomics, one minimum and one add per non-zero bin per workgroup: the order changes nothing.
 // Members without pairs (t1 > k1, t2 > k2) or without columns are answered by the initialisation kernel alone.
+//
+// The list (m4ri_amd_row_sums_collide_list_batch_dev; LIST instantiations only, the others are compiled as before): where a match is
+// weighed, a pair with w_min <= wt <= w_max takes a slot and, if the slot is below cap, stores its key (wt << 40) | pair rank at
+// list[b * l_bs + slot]; count[b] ends as the number of slots taken, whatever cap is.
+//   0  the slot comes from a 32-bit counter in the workgroup's LDS (N1 * N2 < 2^32), count[b] is one plain store at the end: no global
+//      atomic.
+//   1  the initialisation kernel writes count 0 (-1 for a refused member), every match takes its slot with one returning 64-bit global
+//      atomic add on count[b]: the plain form, no aggregation per wave or workgroup (DESIGN.md 3.12 says why).
 // Plain launches on the caller's stream: no allocation, no copy to the host, no synchronisation, no engine workspace or lock.
 #include <hip/hip_runtime.h>
 #include <limits.h>
@@ -58,8 +66,8 @@ constexpr int RC_WT             = 16;  // register words of a weighed word: n <=
 
 // where the pieces of a workgroup's LDS are, in bytes; the same arithmetic on both sides of the launch
 struct RcCarve {
-  size_t skey, wmin, off, part, bins, cols, sr1, total;
-  __host__ __device__ RcCarve(int k, int n, int n1, int q) {
+  size_t skey, wmin, off, part, bins, cols, sr1, slots, total;
+  __host__ __device__ RcCarve(int k, int n, int n1, int q, bool list = false) {
     skey  = (size_t)(k + 1) * 8;                  // the row keys first: k + 1 words, V's last
     wmin  = skey + (size_t)n1 * 8;                // the sorted keys
     off   = wmin + (size_t)(RC_THREADS_MAX / 64) * 8;  // a minimum per wave
@@ -67,12 +75,13 @@ struct RcCarve {
     bins  = part + (size_t)RC_THREADS_MAX * 4;    // the scan's partial sums
     cols  = bins + (size_t)(n + 1) * 4;
     sr1   = cols + (size_t)RC_ELL_MAX * 4;
-    total = pad16(sr1 + (size_t)n1 * 2);          // r1 < 8192 in 16 bits
+    slots = pad16(sr1 + (size_t)n1 * 2);          // r1 < 8192 in 16 bits
+    total = slots + (list ? 16 : 0);              // the list's slot counter of path 0, only where a list is asked for
   }
 };
 
 // the most a workgroup asks for: 128 KiB and a little, which leaves room for the kernel's own static LDS (the votes of a barrier)
-const size_t RC_LDS_MAX = RcCarve((int)RS_K_MAX, (int)RS_N_MAX, (int)RC_N1_MAX, 13).total;
+const size_t RC_LDS_MAX = RcCarve((int)RS_K_MAX, (int)RS_N_MAX, (int)RC_N1_MAX, 13, true).total;
 
 struct RcArgs {
   const word *G, *V;    // V may be NULL; G too where no row is read (t1 = t2 = 0)
@@ -88,6 +97,9 @@ struct RcArgs {
   int64_t slices, slice_len;        // path 1: workgroups per member and right sums per workgroup
   int64_t *hist, *lightest;
   int64_t u0;                       // this launch: workgroups from u0 on
+  int w_max;                        // the list: at most n
+  int64_t *list, *count;            // list may be NULL at cap = 0
+  int64_t l_bs, cap;
 };
 
 // the key of the set of rank `rest` among the sets of t of the rows base .. base + kk - 1
@@ -114,14 +126,14 @@ __device__ __forceinline__ void add_set_rows(word (&c)[RC_WT], const word *g, in
   }
 }
 
-template <bool HIST, bool LIGHT>
+template <bool HIST, bool LIGHT, bool LIST>
 __global__ __launch_bounds__(RC_THREADS_MAX) void rc_kernel(RcArgs p) {
   extern __shared__ __align__(16) word rc_lds[];
   const int tid = threadIdx.x, T = blockDim.x, lane = tid & 63, wave = tid >> 6;
   const int64_t u  = p.u0 + blockIdx.x;
   const int64_t b  = p.atomic ? u / p.slices : u;
   const int64_t sl = p.atomic ? u - b * p.slices : 0;
-  const RcCarve at(p.k, p.n, p.n1, p.q);
+  const RcCarve at(p.k, p.n, p.n1, p.q, LIST);
   unsigned char *lds = reinterpret_cast<unsigned char *>(rc_lds);
   word *rowkey       = rc_lds;
   word *skey         = reinterpret_cast<word *>(lds + at.skey);
@@ -131,6 +143,7 @@ __global__ __launch_bounds__(RC_THREADS_MAX) void rc_kernel(RcArgs p) {
   uint32_t *bins     = reinterpret_cast<uint32_t *>(lds + at.bins);
   int32_t *wcols     = reinterpret_cast<int32_t *>(lds + at.cols);
   uint16_t *sr1      = reinterpret_cast<uint16_t *>(lds + at.sr1);
+  uint32_t *slots    = reinterpret_cast<uint32_t *>(lds + at.slots);  // LIST, path 0
   const int k = p.k, n = p.n, n1 = p.n1, nb = 1 << p.q;
   const word *g = p.G && p.t1 + p.t2 > 0 ? p.G + b * p.g_bs : nullptr;  // without rows in the sums G is not read at all
   const word *v = p.V ? p.V + b * p.v_bs : nullptr;
@@ -147,6 +160,7 @@ __global__ __launch_bounds__(RC_THREADS_MAX) void rc_kernel(RcArgs p) {
       if (HIST)
         for (int w = tid; w <= n; w += T) p.hist[b * ((int64_t)n + 1) + w] = -1;
       if (LIGHT && tid == 0) p.lightest[b] = -2;
+      if (LIST && tid == 0) p.count[b] = -1;
     }
     return;
   }
@@ -164,6 +178,7 @@ __global__ __launch_bounds__(RC_THREADS_MAX) void rc_kernel(RcArgs p) {
   for (int i = tid; i < nb; i += T) off[i] = 0;
   if (HIST)
     for (int i = tid; i <= n; i += T) bins[i] = 0;
+  if (LIST && tid == 0) slots[0] = 0;
   __syncthreads();
 
   // 2. the left table: count, scan, scatter
@@ -239,6 +254,11 @@ __global__ __launch_bounds__(RC_THREADS_MAX) void rc_kernel(RcArgs p) {
         const unsigned long long cand = ((unsigned long long)(uint32_t)wt << 40) | ((unsigned long long)r1 * (unsigned long long)p.n2 + (unsigned long long)r2);
         best                          = cand < best ? cand : best;
       }
+      if (LIST && wt >= p.w_min && wt <= p.w_max) {  // a slot each, taken whether or not it is below cap: the count is the true total
+        const unsigned long long slot = p.atomic ? atomicAdd(reinterpret_cast<unsigned long long *>(p.count + b), 1ull) : (unsigned long long)atomicAdd(slots, 1u);
+        if (slot < (unsigned long long)p.cap)
+          p.list[b * p.l_bs + (int64_t)slot] = (int64_t)(((unsigned long long)(uint32_t)wt << 40) | ((unsigned long long)r1 * (unsigned long long)p.n2 + (unsigned long long)r2));
+      }
     }
   }
 
@@ -256,6 +276,7 @@ __global__ __launch_bounds__(RC_THREADS_MAX) void rc_kernel(RcArgs p) {
     if (!p.atomic) p.lightest[b] = (int64_t)best;
     else if (best != ~0ull) atomicMin(reinterpret_cast<unsigned long long *>(p.lightest + b), best);
   }
+  if (LIST && !p.atomic && tid == 0) p.count[b] = (int64_t)slots[0];  // after the barrier above: every slot is taken
   if (HIST) {
     int64_t *h = p.hist + b * ((int64_t)n + 1);
     for (int w = tid; w <= n; w += T) {
@@ -273,6 +294,8 @@ struct RcInit {
   const int32_t *cols;
   int64_t c_bs;
   int64_t hist0, light_v;  // hist[b][0] = hist0, the other entries 0; lightest[b] = light_v
+  int64_t *list, *count;   // the list's part: count[b] = count_v, and list[b * l_bs + i] = i (weight 0, rank i) for i < min(count_v, cap):
+  int64_t l_bs, cap, count_v;  // count_v > 0 only for members without columns, whose pairs all weigh 0
 };
 
 // What path 1's atomics start from, the whole result of members without pairs or columns, and the refused form wherever it runs.
@@ -288,6 +311,11 @@ __global__ __launch_bounds__(BATCH_WAVE_THREADS) void rc_init_kernel(RcInit p) {
   if (p.hist)
     for (int w = tid; w <= p.n; w += BATCH_WAVE_THREADS) p.hist[b * ((int64_t)p.n + 1) + w] = bad ? -1 : w == 0 ? p.hist0 : 0;
   if (p.lightest && tid == 0) p.lightest[b] = bad ? -2 : p.light_v;
+  if (p.count) {
+    if (tid == 0) p.count[b] = bad ? -1 : p.count_v;
+    const int64_t m = bad ? 0 : p.count_v < p.cap ? p.count_v : p.cap;
+    for (int64_t i = tid; i < m; i += BATCH_WAVE_THREADS) p.list[b * p.l_bs + i] = i;
+  }
 }
 
 int launch_init(hipStream_t st, RcInit p, int64_t batch) {
@@ -326,6 +354,92 @@ int64_t slice_len(int64_t n1, int64_t n2, int64_t batch) {
   return len;
 }
 
+template <bool LIST>
+void launch_walk(bool hist, bool light, dim3 grid, dim3 block, size_t lds, hipStream_t st, const RcArgs &p) {
+  if (hist && light) hipLaunchKernelGGL((rc_kernel<true, true, LIST>), grid, block, lds, st, p);
+  else if (hist) hipLaunchKernelGGL((rc_kernel<true, false, LIST>), grid, block, lds, st, p);
+  else if (light) hipLaunchKernelGGL((rc_kernel<false, true, LIST>), grid, block, lds, st, p);
+  else if constexpr (LIST) hipLaunchKernelGGL((rc_kernel<false, false, true>), grid, block, lds, st, p);  // the list alone
+}
+
+// Both entry points.  Without count (and then without list) this is m4ri_amd_row_sums_collide_batch_dev as it always was: the same
+// checks in the same order, the same kernels.
+int collide(const word *G, int64_t g_stride, int64_t g_bs, int64_t k, int64_t n, const word *V, int64_t v_bs, int64_t batch, int64_t k1, int64_t t1,
+            int64_t t2, const int32_t *cols, int64_t c_bs, int64_t ell, int64_t w_min, int64_t w_max, int64_t *hist, int64_t *lightest, int64_t *list,
+            int64_t l_bs, int64_t cap, int64_t *count, void *stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (sizes_negative(k, n, k1, t1, t2, ell) || batch < 0 || g_stride < 0 || g_bs < 0 || v_bs < 0 || c_bs < 0 || w_min < 0 || w_max < 0 || cap < 0 ||
+      l_bs < 0)
+    return (int)hipErrorInvalidValue;
+  if (k > RS_K_MAX || n > RS_N_MAX || t1 > RS_T_MAX || t2 > RS_T_MAX || ell > RC_ELL_MAX) return (int)hipErrorNotSupported;
+  const int64_t n1 = binom_capped(k1, t1), n2 = binom_capped(k - k1, t2);
+  if (n1 > RC_N1_MAX) return (int)hipErrorNotSupported;
+  const int64_t pairs = n1 * n2;  // at most 2^13 * 2^41
+  if (pairs > RS_SUMS_MAX) return (int)hipErrorNotSupported;
+  if (!cols && ell > n) return (int)hipErrorInvalidValue;
+  if (!hist && !lightest && !count) return (int)hipErrorInvalidValue;
+  if ((list && !count) || (count && !list && cap > 0)) return (int)hipErrorInvalidValue;  // they come together; a count alone at cap = 0
+  if (count && batch > 1 && l_bs < cap) return (int)hipErrorInvalidValue;
+  const int64_t width = words_of(n);
+  const bool words    = k > 0 && n > 0;                      // G has words
+  const bool walked   = pairs > 0 && n > 0 && t1 + t2 >= 1;  // and they are read
+  if (n > 0 && k > 1 && g_stride < width) return (int)hipErrorInvalidValue;
+  if (batch > 0) {
+    if (walked && !G) return (int)hipErrorInvalidValue;
+    const bool listed = count && list && cap > 0;
+    const void *outs[4]      = {hist, lightest, count, listed ? list : nullptr};
+    const uintptr_t bytes[4] = {(uintptr_t)(batch * (n + 1)) * 8, (uintptr_t)batch * 8, (uintptr_t)batch * 8,
+                                ((uintptr_t)(batch - 1) * (uintptr_t)l_bs + (uintptr_t)cap) * 8};
+    for (int o = 0; o < 4; ++o) {
+      if (!outs[o]) continue;
+      for (int o2 = o + 1; o2 < 4; ++o2)
+        if (outs[o2] && spans_meet(outs[o], bytes[o], outs[o2], bytes[o2])) return (int)hipErrorInvalidValue;
+      if (words && G && spans_meet(outs[o], bytes[o], G, member_span_bytes(batch, g_bs, k, g_stride, width))) return (int)hipErrorInvalidValue;
+      if (V && n > 0 && spans_meet(outs[o], bytes[o], V, member_span_bytes(batch, v_bs, 1, 0, width))) return (int)hipErrorInvalidValue;
+      if (cols && ell > 0 && spans_meet(outs[o], bytes[o], cols, (uintptr_t)((batch - 1) * c_bs + ell) * 4)) return (int)hipErrorInvalidValue;
+    }
+  }
+  if (batch == 0) return 0;
+  RcInit in{};
+  in.hist = hist, in.lightest = lightest, in.n = (int)n, in.ell = (int)ell, in.cols = cols, in.c_bs = c_bs, in.light_v = -1;
+  in.list = list, in.count = count, in.l_bs = l_bs, in.cap = cap;
+  if (n == 0 || pairs == 0) {  // every word weighs 0: all pairs in the one bin, the lightest is rank 0 if weight 0 qualifies; or no pairs
+    in.hist0 = pairs, in.light_v = pairs > 0 && w_min == 0 ? 0 : -1;  // n = 0 with a window given: every entry is outside, all refused
+    in.count_v = w_min == 0 ? pairs : 0;                              // weight 0 is in the band iff w_min = 0: w_max >= 0
+    return launch_init(st, in, batch);
+  }
+  RcArgs p{};
+  p.G = G, p.V = V, p.cols = cols, p.g_stride = g_stride, p.g_bs = g_bs, p.v_bs = v_bs, p.c_bs = c_bs;
+  p.k = (int)k, p.k1 = (int)k1, p.k2 = (int)(k - k1), p.t1 = (int)t1, p.t2 = (int)t2, p.n = (int)n, p.width = (int)width, p.ell = (int)ell;
+  p.mask = tail_mask((int)(n & 63)), p.w_min = (int)(w_min > n + 1 ? n + 1 : w_min), p.n1 = (int)n1, p.n2 = n2;
+  p.hist = hist, p.lightest = lightest;
+  p.w_max = (int)(w_max > n ? n : w_max), p.list = list, p.count = count, p.l_bs = l_bs, p.cap = cap;
+  while (p.q < ell && ((int64_t)1 << p.q) < n1) ++p.q;
+  p.atomic    = plan(k, n, k1, t1, t2, ell, env_p0());
+  p.slice_len = p.atomic ? slice_len(n1, n2, batch) : n2;
+  p.slices    = (n2 + p.slice_len - 1) / p.slice_len;
+  static std::once_flag once;
+  static hipError_t attr = hipSuccess;
+  std::call_once(once, [] {
+    const void *kernels[] = {reinterpret_cast<const void *>(rc_kernel<true, true, false>), reinterpret_cast<const void *>(rc_kernel<true, false, false>),
+                             reinterpret_cast<const void *>(rc_kernel<false, true, false>), reinterpret_cast<const void *>(rc_kernel<true, true, true>),
+                             reinterpret_cast<const void *>(rc_kernel<true, false, true>), reinterpret_cast<const void *>(rc_kernel<false, true, true>),
+                             reinterpret_cast<const void *>(rc_kernel<false, false, true>)};
+    for (const void *f : kernels)
+      if (attr == hipSuccess) attr = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)RC_LDS_MAX);
+  });
+  HIPTRY(attr);
+  const size_t lds  = RcCarve((int)k, (int)n, (int)n1, p.q, count != nullptr).total;
+  const int threads = n1 <= 1024 && p.slice_len <= 4096 ? BATCH_WAVE_THREADS : RC_THREADS_MAX;
+  if (p.atomic) HIPTRY(launch_init(st, in, batch));
+  return launch_chunked(batch * p.slices, BATCH_CHUNK, [&](int64_t u0, int64_t nu) {
+    p.u0 = u0;
+    const dim3 grid((unsigned)nu), block((unsigned)threads);
+    if (count) launch_walk<true>(hist != nullptr, lightest != nullptr, grid, block, lds, st, p);
+    else launch_walk<false>(hist != nullptr, lightest != nullptr, grid, block, lds, st, p);
+  });
+}
+
 }  // namespace
 
 extern "C" {
@@ -345,68 +459,14 @@ int64_t m4ri_amd_row_sums_collide_slices(int64_t k, int64_t n, int64_t k1, int64
 int m4ri_amd_row_sums_collide_batch_dev(const word *G, int64_t g_stride, int64_t g_bs, int64_t k, int64_t n, const word *V, int64_t v_bs, int64_t batch,
                                         int64_t k1, int64_t t1, int64_t t2, const int32_t *cols, int64_t c_bs, int64_t ell, int64_t w_min,
                                         int64_t *hist, int64_t *lightest, void *stream) {
-  hipStream_t st = (hipStream_t)stream;
-  if (sizes_negative(k, n, k1, t1, t2, ell) || batch < 0 || g_stride < 0 || g_bs < 0 || v_bs < 0 || c_bs < 0 || w_min < 0)
-    return (int)hipErrorInvalidValue;
-  if (k > RS_K_MAX || n > RS_N_MAX || t1 > RS_T_MAX || t2 > RS_T_MAX || ell > RC_ELL_MAX) return (int)hipErrorNotSupported;
-  const int64_t n1 = binom_capped(k1, t1), n2 = binom_capped(k - k1, t2);
-  if (n1 > RC_N1_MAX) return (int)hipErrorNotSupported;
-  const int64_t pairs = n1 * n2;  // at most 2^13 * 2^41
-  if (pairs > RS_SUMS_MAX) return (int)hipErrorNotSupported;
-  if (!cols && ell > n) return (int)hipErrorInvalidValue;
-  if (!hist && !lightest) return (int)hipErrorInvalidValue;
-  const int64_t width = words_of(n);
-  const bool words    = k > 0 && n > 0;                      // G has words
-  const bool walked   = pairs > 0 && n > 0 && t1 + t2 >= 1;  // and they are read
-  if (n > 0 && k > 1 && g_stride < width) return (int)hipErrorInvalidValue;
-  if (batch > 0) {
-    if (walked && !G) return (int)hipErrorInvalidValue;
-    const uintptr_t hist_bytes = (uintptr_t)(batch * (n + 1)) * 8, light_bytes = (uintptr_t)batch * 8;
-    if (hist && lightest && spans_meet(hist, hist_bytes, lightest, light_bytes)) return (int)hipErrorInvalidValue;
-    for (int o = 0; o < 2; ++o) {
-      const void *out       = o ? (const void *)lightest : (const void *)hist;
-      const uintptr_t bytes = o ? light_bytes : hist_bytes;
-      if (!out) continue;
-      if (words && G && spans_meet(out, bytes, G, member_span_bytes(batch, g_bs, k, g_stride, width))) return (int)hipErrorInvalidValue;
-      if (V && n > 0 && spans_meet(out, bytes, V, member_span_bytes(batch, v_bs, 1, 0, width))) return (int)hipErrorInvalidValue;
-      if (cols && ell > 0 && spans_meet(out, bytes, cols, (uintptr_t)((batch - 1) * c_bs + ell) * 4)) return (int)hipErrorInvalidValue;
-    }
-  }
-  if (batch == 0) return 0;
-  RcInit in{};
-  in.hist = hist, in.lightest = lightest, in.n = (int)n, in.ell = (int)ell, in.cols = cols, in.c_bs = c_bs, in.light_v = -1;
-  if (n == 0 || pairs == 0) {  // every word weighs 0: all pairs in the one bin, the lightest is rank 0 if weight 0 qualifies; or no pairs
-    in.hist0 = pairs, in.light_v = pairs > 0 && w_min == 0 ? 0 : -1;  // n = 0 with a window given: every entry is outside, all refused
-    return launch_init(st, in, batch);
-  }
-  RcArgs p{};
-  p.G = G, p.V = V, p.cols = cols, p.g_stride = g_stride, p.g_bs = g_bs, p.v_bs = v_bs, p.c_bs = c_bs;
-  p.k = (int)k, p.k1 = (int)k1, p.k2 = (int)(k - k1), p.t1 = (int)t1, p.t2 = (int)t2, p.n = (int)n, p.width = (int)width, p.ell = (int)ell;
-  p.mask = tail_mask((int)(n & 63)), p.w_min = (int)(w_min > n + 1 ? n + 1 : w_min), p.n1 = (int)n1, p.n2 = n2;
-  p.hist = hist, p.lightest = lightest;
-  while (p.q < ell && ((int64_t)1 << p.q) < n1) ++p.q;
-  p.atomic    = plan(k, n, k1, t1, t2, ell, env_p0());
-  p.slice_len = p.atomic ? slice_len(n1, n2, batch) : n2;
-  p.slices    = (n2 + p.slice_len - 1) / p.slice_len;
-  static std::once_flag once;
-  static hipError_t attr = hipSuccess;
-  std::call_once(once, [] {
-    const void *kernels[] = {reinterpret_cast<const void *>(rc_kernel<true, true>), reinterpret_cast<const void *>(rc_kernel<true, false>),
-                             reinterpret_cast<const void *>(rc_kernel<false, true>)};
-    for (const void *f : kernels)
-      if (attr == hipSuccess) attr = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)RC_LDS_MAX);
-  });
-  HIPTRY(attr);
-  const size_t lds  = RcCarve((int)k, (int)n, (int)n1, p.q).total;
-  const int threads = n1 <= 1024 && p.slice_len <= 4096 ? BATCH_WAVE_THREADS : RC_THREADS_MAX;
-  if (p.atomic) HIPTRY(launch_init(st, in, batch));
-  return launch_chunked(batch * p.slices, BATCH_CHUNK, [&](int64_t u0, int64_t nu) {
-    p.u0 = u0;
-    const dim3 grid((unsigned)nu), block((unsigned)threads);
-    if (hist && lightest) hipLaunchKernelGGL((rc_kernel<true, true>), grid, block, lds, st, p);
-    else if (hist) hipLaunchKernelGGL((rc_kernel<true, false>), grid, block, lds, st, p);
-    else hipLaunchKernelGGL((rc_kernel<false, true>), grid, block, lds, st, p);
-  });
+  return collide(G, g_stride, g_bs, k, n, V, v_bs, batch, k1, t1, t2, cols, c_bs, ell, w_min, 0, hist, lightest, nullptr, 0, 0, nullptr, stream);
+}
+
+int m4ri_amd_row_sums_collide_list_batch_dev(const word *G, int64_t g_stride, int64_t g_bs, int64_t k, int64_t n, const word *V, int64_t v_bs,
+                                             int64_t batch, int64_t k1, int64_t t1, int64_t t2, const int32_t *cols, int64_t c_bs, int64_t ell,
+                                             int64_t w_min, int64_t w_max, int64_t *hist, int64_t *lightest, int64_t *list, int64_t l_bs, int64_t cap,
+                                             int64_t *count, void *stream) {
+  return collide(G, g_stride, g_bs, k, n, V, v_bs, batch, k1, t1, t2, cols, c_bs, ell, w_min, w_max, hist, lightest, list, l_bs, cap, count, stream);
 }
 
 }  // extern "C"
