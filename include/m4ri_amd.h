@@ -610,6 +610,82 @@ int m4ri_amd_row_sums_collide_list_batch_dev(const word *G, int64_t g_stride, in
 int m4ri_amd_row_sums_words_batch_dev(const word *G, int64_t g_stride, int64_t g_bs, int64_t k, int64_t n, const word *V, int64_t v_bs,
                                       int64_t batch, int64_t k1, int64_t t1, int64_t t2, const int64_t *keys, int64_t l_bs, int64_t cap,
                                       const int64_t *count, word *W, int64_t w_stride, int64_t w_bs, int32_t *skipped, void *stream);
+/* The join of two EXPLICIT lists of words on a window of bits (lists_collide_batch.hip): the merge step that Stern's collision search,
+ * Wagner's generalized birthday and the level-1 lists of MMT / BJMM share, for lists that are rows in memory and of any length -- the
+ * output of an earlier join among them.  Member b has a LEFT list X_b, nx rows of n bits at X + b * x_bs words, the rows x_stride
+ * words apart; a RIGHT list Y_b, ny rows, y_stride, y_bs; an optional word V_b at V + b * v_bs (V = NULL: none).  A batch stride of 0 is
+ * one operand shared by all members.  X, Y and V are READ ONLY and only their n valid bits count; X and Y may be the same memory or
+ * overlap (a self-join, the pairs i = j included).  The word of pair (i, j) is c_b(i, j) = V_b ^ X_b[i] ^ Y_b[j], its rank i * ny + j.
+ * cols (DEVICE int32, or NULL): member b's window, ell column indices at cols + b * c_bs entries (c_bs = 0: one window for all
+ * members; NULL: the columns 0 .. ell-1, one masked word per row); the entries need not be sorted, distinct or in one word.  The pair
+ * COLLIDES iff c is 0 at every window column; with ell = 0 every pair collides.
+ * The outputs are those of m4ri_amd_row_sums_collide_list_batch_dev with this pair rank in the key's low 40 bits:
+ * hist (DEVICE int64, batch * (n + 1) entries, or NULL): hist[b * (n + 1) + w] = the number of colliding pairs with wt(c) = w.
+ * lightest (DEVICE int64, batch entries, or NULL): the minimum over the colliding pairs with wt(c) >= w_min of (wt << 40) | rank, -1 if
+ * there is none; it ignores w_max.
+ * count (DEVICE int64, batch entries, or NULL): the number of colliding pairs with w_min <= wt(c) <= w_max (a w_max above n is n), the
+ * TRUE total however small cap is.  list (DEVICE int64, member b's entries at list + b * l_bs, cap of them): the entries
+ * i < min(count[b], cap) are DISTINCT keys (wt << 40) | rank of such pairs, in no particular order; count[b] > cap: some cap of them,
+ * which ones is not specified.  The entries from min(count[b], cap) on are NOT written.  list and count come together; list may be NULL
+ * only with cap = 0.  At least one of hist, lightest and count is required.  m4ri_amd_lists_words_batch_dev below turns the keys into
+ * words, which can be a list of the next join.
+ * A window entry outside 0 .. n-1 cannot be seen by the host, so the device decides: that member is REFUSED, every one of its hist
+ * entries is -1, its lightest -2, its count -1 and no list entry is written; nothing outside the member is read, the other members
+ * are unaffected.  A member with nx = 0 or ny = 0 has every bin 0, lightest -1 and count 0; n = 0 with ell = 0 puts all nx * ny pairs
+ * into bin 0 (lightest 0 if w_min = 0 and there is a pair; count = nx * ny if w_min = 0, else 0, the first min(count, cap) list entries
+ * the keys 0, 1, ...); batch = 0 succeeds without touching anything.
+ * Limits: n <= 1024, ell <= 64, nx, ny < 2^31 and nx * ny <= 2^40 (the pair rank fits the key); beyond any of them the call returns
+ * hipErrorNotSupported (801) before any HIP call.  There is NO bound on nx by LDS: a workgroup owns a member, a chunk of the left
+ * list (as many rows as its LDS table holds) and a slice of the right list, see m4ri_amd_lists_collide_units.  Every workgroup
+ * re-reads its slice once per left chunk.  Stern beyond the 8192 left sums of m4ri_amd_row_sums_collide_batch_dev: materialise each half
+ * with m4ri_amd_row_sums_words_batch_dev (t2 = 0, k1 = k, an iota of keys) and join those; the list index is then the colexicographic
+ * rank, so the pair ranks are the same.
+ * Asynchronous on `stream` on both paths of m4ri_amd_plan_lists_collide_batch: plain launches (on path 1 an initialisation of the
+ * outputs goes first, on the same stream), no allocation, no copy to the host, no synchronisation, no engine workspace, no engine
+ * lock; capturable.  All results are integer counts and minima: they do not depend on the order the hardware takes the pairs in.
+ * hipErrorInvalidValue, before any HIP call, for negative sizes, strides or batch strides, w_min, w_max, cap or l_bs < 0, a NULL cols
+ * with ell > n, x_stride < words(n) with nx > 1 or y_stride < words(n) with ny > 1, a NULL X or Y where rows are read (batch > 0,
+ * n > 0, nx > 0, ny > 0), none of the three outputs, a list without a count, a count without a list at cap > 0, l_bs < cap with
+ * batch > 1 (count given), or an output (hist, lightest, count, the list's span from its first member's start to the last member's
+ * cap-th entry) whose bytes meet another output or the span (first member's start to last member's end) of X, Y, V or cols. */
+int m4ri_amd_lists_collide_batch_dev(const word *X, int64_t x_stride, int64_t x_bs, int64_t nx, const word *Y, int64_t y_stride, int64_t y_bs,
+                                     int64_t ny, int64_t n, const word *V, int64_t v_bs, int64_t batch, const int32_t *cols, int64_t c_bs,
+                                     int64_t ell, int64_t w_min, int64_t w_max, int64_t *hist, int64_t *lightest, int64_t *list, int64_t l_bs,
+                                     int64_t cap, int64_t *count, void *stream);
+/* which path the call above takes for members of this shape in a batch of this size (pure host arithmetic; -1 for negative sizes; sizes
+ * beyond the call's limits are answered by the same rule): 0 a member is one chunk and one slice, one workgroup writes its outputs with
+ * plain stores, the count from a counter in LDS, no global atomics (members without pairs or columns count here: an initialisation
+ * kernel answers them); 1 a member has several chunks or slices, a workgroup each, their results combined with global 64-bit integer
+ * atomics after an initialisation kernel. */
+int m4ri_amd_plan_lists_collide_batch(int64_t nx, int64_t ny, int64_t n, int64_t ell, int64_t batch);
+/* the units of the call above, whichever path the shape takes: *chunk_rows = the left rows of a chunk (what one workgroup's LDS table
+ * holds; the last chunk of a list is shorter), *chunks = ceil(nx / chunk_rows) and *slices = the slices of the right list per member:
+ * slices of ceil(ny / slices) rows, no shorter than min(nx, chunk_rows) or than 256 rows unless the list is, as many as bring the call
+ * to 1024 workgroups, a slice times a chunk below 2^32.  chunks = slices = 0 for members without pairs or columns.  Each pointer may
+ * be NULL.  Returns 0, or -1 for negative sizes (nothing is stored then). */
+int m4ri_amd_lists_collide_units(int64_t nx, int64_t ny, int64_t n, int64_t ell, int64_t batch, int64_t *chunk_rows, int64_t *chunks,
+                                 int64_t *slices);
+/* The words behind listed keys of two explicit lists, on the device (lists_collide_batch.hip): what m4ri_amd_row_sums_words_batch_dev
+ * is to the row-sum calls.  X, Y, V, nx, ny, n, the strides and the sharing rule are those of m4ri_amd_lists_collide_batch_dev.
+ * keys (DEVICE int64): member b's at keys + b * l_bs entries.  count (DEVICE int64, batch entries, or NULL): member b has
+ * m_b = min(max(count[b], 0), cap) keys, so a refused member's -1 reads as 0 and a count beyond cap as cap; NULL: cap keys per member.
+ * W: member b's rows at W + b * w_bs words, w_stride words apart.  For i < m_b let r = keys[b * l_bs + i] & (2^40 - 1): the weight
+ * bits above are ignored.  Row i of W_b becomes V_b ^ X_b[r / ny] ^ Y_b[r % ny].  Only the n valid bits are written: bits at
+ * columns >= n, padding words, the rows from m_b on and the gaps keep what they held.
+ * A key cannot be seen by the host, so the device decides: if keys[...] < 0 or r >= nx * ny the row is SKIPPED, it is not written and
+ * no row index is formed from the key.  skipped (DEVICE int32, batch entries, or NULL): skipped[b] = the number of such rows, written
+ * whole, 0 for a clean member.
+ * Limits: those of the join (n <= 1024, nx, ny < 2^31, nx * ny <= 2^40), beyond them hipErrorNotSupported (801) before any HIP call.
+ * Asynchronous on `stream`: a memset of skipped and plain launches, no allocation, no copy to the host, no synchronisation, no engine
+ * lock; capturable.  count and keys are read on the device, so they may come from a call still in flight on the same stream.
+ * hipErrorInvalidValue, before any HIP call, for negative sizes, strides or batch strides, x_stride < words(n) with nx > 1,
+ * y_stride < words(n) with ny > 1, w_stride < words(n) with cap > 1, with batch > 1 and cap > 0 an l_bs < cap or a w_bs below
+ * (cap - 1) * w_stride + words(n), a NULL keys, W (n > 0), X or Y (where rows are read) with batch > 0 and cap > 0, or a W or skipped
+ * whose bytes meet the span of X, Y, V, keys, count or each other.  batch = 0 succeeds without touching anything; cap = 0 writes skipped
+ * only. */
+int m4ri_amd_lists_words_batch_dev(const word *X, int64_t x_stride, int64_t x_bs, int64_t nx, const word *Y, int64_t y_stride, int64_t y_bs,
+                                   int64_t ny, int64_t n, const word *V, int64_t v_bs, int64_t batch, const int64_t *keys, int64_t l_bs, int64_t cap,
+                                   const int64_t *count, word *W, int64_t w_stride, int64_t w_bs, int32_t *skipped, void *stream);
 /* Assembling, cutting and permuting the members of a batch where they are (assemble_batch.hip).  Conventions of the calls below, as
  * of the other batched calls: member b of X is at X + b * x_bs words, its rows x_stride words apart; a batch stride of 0 on a
  * READ-ONLY operand is one operand shared by all members.  Every call is asynchronous on `stream`: plain launches (several for a

@@ -200,6 +200,11 @@ SYMBOLS = {
     "m4ri_amd_row_sums_words_batch_dev": (_I, [_P, _I64, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I64, _I64, _P, _I64, _I64, _P, _P, _I64, _I64, _P, _P]),
     "m4ri_amd_plan_row_sums_collide_batch": (_I, [_I64, _I64, _I64, _I64, _I64, _I64]),
     "m4ri_amd_row_sums_collide_slices": (_I64, [_I64, _I64, _I64, _I64, _I64, _I64, _I64]),
+    "m4ri_amd_lists_collide_batch_dev": (_I, [_P, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I64, _P, _I64, _I64, _P, _I64, _I64, _I64, _I64, _P, _P, _P, _I64,
+                                              _I64, _P, _P]),
+    "m4ri_amd_plan_lists_collide_batch": (_I, [_I64, _I64, _I64, _I64, _I64]),
+    "m4ri_amd_lists_collide_units": (_I, [_I64, _I64, _I64, _I64, _I64, ctypes.POINTER(_I64), ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
+    "m4ri_amd_lists_words_batch_dev": (_I, [_P, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I64, _P, _I64, _I64, _P, _I64, _I64, _P, _P, _I64, _I64, _P, _P]),
     "m4ri_amd_copy_block_batch_dev": (_I, [_P, _I64, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _P]),
     "m4ri_amd_extract_tri_batch_dev": (_I, [_P, _I64, _I64, _P, _I64, _I64, _I64, _I64, _I64, _I, _I, _P, _P]),
     "m4ri_amd_apply_p_left_batch_dev": (_I, [_P, _I64, _I64, _I64, _I64, _I64, _P, _I64, _I64, _I, _P, _P]),
@@ -703,6 +708,49 @@ def plan_row_sums_collide_batch(k: int, n: int, k1: int, t1: int, t2: int, ell: 
 def row_sums_collide_slices(k: int, n: int, k1: int, t1: int, t2: int, ell: int, batch: int) -> int:
     """The workgroups per member of row_sums_collide_batch_dev on path 1: the slices of the right list. Host arithmetic."""
     return int(lib().m4ri_amd_row_sums_collide_slices(k, n, k1, t1, t2, ell, batch))
+
+
+def lists_collide_batch_dev(X: int, x_stride: int, x_bs: int, nx: int, Y: int, y_stride: int, y_bs: int, ny: int, n: int, V: int = 0, v_bs: int = 0,
+                            batch: int = 1, cols: int = 0, c_bs: int = 0, ell: int = 0, w_min: int = 0, w_max: int = 1024, hist: int = 0, lightest: int = 0,
+                            list: int = 0, l_bs: int = 0, cap: int = 0, count: int = 0, stream: int = 0) -> None:
+    """The join of two explicit lists on a window, for `batch` members: X_b (nx rows of n bits, rows x_stride words apart, members x_bs),
+    Y_b (ny rows), an optional word V_b; a batch stride of 0 shares an operand, X and Y may be the same memory.  The pair (i, j), rank
+    i * ny + j (divmod(rank, ny) gives it back), collides iff V_b ^ X_b[i] ^ Y_b[j] is 0 at the ell window columns (cols: DEVICE int32,
+    member b's at cols + b * c_bs entries, cols = 0: columns 0 .. ell-1).  DEVICE int64 outputs as in row_sums_collide_list_batch_dev, each
+    0 = not wanted, one required: hist (batch * (n + 1)), lightest (the minimum of (wt << 40) | rank over wt >= w_min, -1 if none), count
+    and list (the keys of the pairs with w_min <= wt <= w_max; count the true total, the first min(count, cap) entries distinct, the
+    entries behind not written; list = 0 only with cap = 0).  A member with a window entry outside 0 .. n-1 is refused on the device:
+    hist all -1, lightest -2, count -1.  n <= 1024, ell <= 64, nx, ny < 2^31, nx * ny <= 2^40; no bound on nx by LDS.  Asynchronous,
+    lock-free and capturable on both paths of plan_lists_collide_batch."""
+    _check(lib().m4ri_amd_lists_collide_batch_dev(X or None, x_stride, x_bs, nx, Y or None, y_stride, y_bs, ny, n, V or None, v_bs, batch, cols or None,
+                                                  c_bs, ell, w_min, w_max, hist or None, lightest or None, list or None, l_bs, cap, count or None, stream),
+           "m4ri_amd_lists_collide_batch_dev")
+
+
+def lists_words_batch_dev(X: int, x_stride: int, x_bs: int, nx: int, Y: int, y_stride: int, y_bs: int, ny: int, n: int, V: int, v_bs: int, batch: int,
+                          keys: int, l_bs: int, cap: int, count: int, W: int, w_stride: int, w_bs: int, skipped: int = 0, stream: int = 0) -> None:
+    """The words of listed keys of two explicit lists on the device: for i < m_b = min(max(count[b], 0), cap) (count = 0: cap keys per
+    member) and r = keys[b * l_bs + i] & (2^40 - 1), row i of W_b (rows w_stride words apart, members w_bs) becomes
+    V_b ^ X_b[r // ny] ^ Y_b[r % ny]; only the n valid bits are written.  A key < 0 or with r >= nx * ny is skipped on the device (its row
+    is not written) and counted in skipped (DEVICE int32, batch entries, 0 = not wanted).  The limits of lists_collide_batch_dev.
+    Asynchronous, lock-free and capturable."""
+    _check(lib().m4ri_amd_lists_words_batch_dev(X or None, x_stride, x_bs, nx, Y or None, y_stride, y_bs, ny, n, V or None, v_bs, batch, keys or None, l_bs,
+                                                cap, count or None, W or None, w_stride, w_bs, skipped or None, stream), "m4ri_amd_lists_words_batch_dev")
+
+
+def plan_lists_collide_batch(nx: int, ny: int, n: int, ell: int, batch: int) -> int:
+    """The path lists_collide_batch_dev takes (0 one chunk and one slice per member: one workgroup, plain stores; 1 several workgroups per
+    member and global atomics; -1 negative sizes). Host arithmetic."""
+    return int(lib().m4ri_amd_plan_lists_collide_batch(nx, ny, n, ell, batch))
+
+
+def lists_collide_units(nx: int, ny: int, n: int, ell: int, batch: int) -> tuple:
+    """(chunk_rows, chunks, slices) of lists_collide_batch_dev: the left rows of one workgroup's table, the chunks of the left list and the
+    slices of the right list per member. Host arithmetic; ValueError for negative sizes."""
+    c, ch, sl = _I64(0), _I64(0), _I64(0)
+    if lib().m4ri_amd_lists_collide_units(nx, ny, n, ell, batch, ctypes.byref(c), ctypes.byref(ch), ctypes.byref(sl)) != 0:
+        raise ValueError("lists_collide_units: negative sizes")
+    return int(c.value), int(ch.value), int(sl.value)
 
 
 def row_pair_rank(S1, S2, k1: int, k: int, t2: int) -> int:
