@@ -210,3 +210,36 @@ def test_two_streams(oracle):
     for (m, n, full, s, tA, tr, tp, exp, want_rank, want_piv) in jobs:
         assert np.array_equal(tA.cpu().numpy().view(np.uint64), exp), (m, n)
         assert np.array_equal(tr.cpu().numpy(), want_rank) and np.array_equal(tp.cpu().numpy(), want_piv), (m, n)
+
+
+def test_captured_into_a_graph(oracle):
+    """Paths 0, 1 and 2 are one launch each and capturable (path 3 blocks and is never captured): a shape of each captured on one
+    stream, one chain -- nothing runs, the buffers keep their dirt -- then replayed once.  An ordinary call of each kernel comes
+    first: a process's first call sets function attributes, which is not what this test is about."""
+    jobs = []
+    for path, (m, n, full, batch) in enumerate([(33, 50, 1, 5), (130, 70, 0, 3), (1100, 1100, 1, 2)]):
+        assert m4ri_amd.plan_echelonize_batch(m, n) == path
+        _run(oracle, m, n, batch, full, seed=900 + m)
+        stride, a_bs = (n + 63) // 64 + 1, m * ((n + 63) // 64 + 1) + 3
+        members = [_member(KINDS[b % len(KINDS)], m, n, 910 + m + 7 * b) for b in range(batch)]
+        h, idx, valid = _pack(members, m, n, stride, a_bs, 920 + m)
+        exp, want_rank, want_piv = _expected(oracle, members, h, idx, valid, full)
+        tA = torch.from_numpy(h.view(np.int64).copy()).cuda()
+        tr = torch.full((batch,), -7, dtype=torch.int32, device="cuda")
+        tp = torch.full((batch * min(m, n),), -7, dtype=torch.int32, device="cuda")
+        jobs.append((m, n, full, batch, stride, a_bs, h, exp, want_rank, want_piv, tA, tr, tp))
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        st = torch.cuda.current_stream().cuda_stream
+        for (m, n, full, batch, stride, a_bs, h, exp, want_rank, want_piv, tA, tr, tp) in jobs:
+            m4ri_amd.echelonize_batch_dev(tA.data_ptr(), stride, a_bs, m, n, batch, full, tr.data_ptr(), tp.data_ptr(), st)
+    torch.cuda.synchronize()
+    for (m, n, full, batch, stride, a_bs, h, exp, want_rank, want_piv, tA, tr, tp) in jobs:
+        assert np.array_equal(tA.cpu().numpy().view(np.uint64), h) and (tr == -7).all() and (tp == -7).all(), (m, n)
+    g.replay()
+    torch.cuda.synchronize()
+    for (m, n, full, batch, stride, a_bs, h, exp, want_rank, want_piv, tA, tr, tp) in jobs:
+        assert not np.array_equal(exp, h)
+        assert np.array_equal(tA.cpu().numpy().view(np.uint64), exp), (m, n)
+        assert np.array_equal(tr.cpu().numpy(), want_rank) and np.array_equal(tp.cpu().numpy(), want_piv), (m, n)

@@ -247,3 +247,28 @@ def test_two_streams(oracle):
     s2.synchronize()
     _verify(c1)
     _verify(c2)
+
+
+def test_captured_into_a_graph(oracle):
+    """Paths 0 and 1 are one launch each and capturable (path 2 blocks and is never captured): a shape of each captured on one stream,
+    one chain -- nothing runs, R and rank keep their dirt -- then replayed once.  An ordinary call of each kernel comes first: a
+    process's first call sets function attributes, which is not what this test is about."""
+    cases = []
+    for path, (m, n, kc, batch) in enumerate([(40, 50, 50, 7), (70, 200, 100, 7)]):
+        _run(oracle, m, n, kc, batch, 1100 + m, path=path)
+        c = _case(oracle, m, n, kc, batch, 1110 + m)
+        assert not np.array_equal(c["exp"], c["hR"])
+        _upload(c)
+        cases.append(c)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        for c in cases:
+            _launch(c, torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    for c in cases:
+        assert np.array_equal(c["tR"].cpu().numpy().view(np.uint64), c["hR"]) and (c["tr"] == -7).all(), (c["m"], c["n"])
+    g.replay()
+    torch.cuda.synchronize()
+    for c in cases:
+        _verify(c)

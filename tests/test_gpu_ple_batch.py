@@ -214,3 +214,28 @@ def test_non_default_stream(oracle):
     s.synchronize()
     _verify(c1)
     _verify(c2)
+
+
+def test_captured_into_a_graph(oracle):
+    """Paths 0, 1 and 2 are one launch each and capturable (path 3 blocks and is never captured): a shape of each captured on one
+    stream, one chain -- nothing runs, the matrices, P, Q and rank keep their dirt -- then replayed once.  An ordinary call of each
+    kernel comes first: a process's first call sets function attributes, which is not what this test is about."""
+    cases = []
+    for path, (m, n, batch, pluq) in enumerate([(33, 50, 5, 1), (100, 200, 3, 0), (1500, 1500, 2, 1)]):
+        _run(oracle, m, n, batch, pluq, 1100 + m, path=path)
+        c = _case(oracle, m, n, batch, pluq, 1110 + m)
+        _upload(c)
+        cases.append(c)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        for c in cases:
+            _launch(c, torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    for c in cases:
+        assert np.array_equal(c["tA"].cpu().numpy().view(np.uint64), c["h"]) and not np.array_equal(c["exp"], c["h"]), (c["m"], c["n"])
+        assert (c["tP"] == -7).all() and (c["tQ"] == -7).all() and (c["tr"] == -7).all(), (c["m"], c["n"])
+    g.replay()
+    torch.cuda.synchronize()
+    for c in cases:
+        _verify(c)

@@ -179,3 +179,37 @@ def test_non_default_stream(oracle):
     s = torch.cuda.Stream()
     _run(oracle, 64, 64, 64, 300, 600, stream=s)
     _run(oracle, 256, 256, 100, 40, 700, stream=s)
+
+
+def test_captured_into_a_graph(oracle):
+    """Paths 0 and 1 are one launch each and capturable (path 2 blocks and is never captured): a shape of each captured on one stream,
+    one chain, on decompositions made before the capture -- nothing runs, B and status keep their dirt -- then replayed once and
+    compared with the oracle's gf2o_solve_left.  _run's ordinary call of each kernel comes first: a process's first call sets function
+    attributes, which is not what this test is about."""
+    cases = []
+    for path, (m, n, k, batch) in enumerate([(40, 50, 17, 6), (100, 70, 130, 6)]):
+        _run(oracle, m, n, k, batch, 800 + m, path=path)
+        c = _solve_case(oracle, m, n, k, batch, 810 + m, systems=_systems(oracle, m, n, k, batch, 810 + m, False, False))
+        assert (c["status"] == 0).any() and (c["status"] == -1).any() and not np.array_equal(c["exp"], c["hB"])
+        c["tF"] = torch.from_numpy(c["hA"].view(np.int64).copy()).cuda()
+        c["tB"] = torch.from_numpy(c["hB"].view(np.int64).copy()).cuda()
+        c["tP"], c["tQ"], c["tr"], c["ts"] = (torch.full((x,), -7, dtype=torch.int32, device="cuda") for x in (batch * m, batch * n, batch, batch))
+        m4ri_amd.ple_batch_dev(c["tF"].data_ptr(), c["a_stride"], c["a_bs"], m, n, batch, True, c["tP"].data_ptr(), c["tQ"].data_ptr(), c["tr"].data_ptr())
+        cases.append(c)
+    torch.cuda.synchronize()
+    before = [[c[x].clone() for x in ("tF", "tP", "tQ", "tr")] for c in cases]
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        for c in cases:
+            m4ri_amd.pluq_solve_left_batch_dev(c["tF"].data_ptr(), c["a_stride"], c["a_bs"], c["m"], c["n"], c["tr"].data_ptr(), c["tP"].data_ptr(),
+                                               c["tQ"].data_ptr(), c["tB"].data_ptr(), c["b_stride"], c["b_bs"], c["k"], c["batch"], c["ts"].data_ptr(),
+                                               torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    for c in cases:
+        assert np.array_equal(c["tB"].cpu().numpy().view(np.uint64), c["hB"]) and (c["ts"] == -7).all(), (c["m"], c["n"])
+    g.replay()
+    torch.cuda.synchronize()
+    for c, kept in zip(cases, before):
+        assert np.array_equal(c["ts"].cpu().numpy(), c["status"]), (c["m"], c["n"])
+        assert np.array_equal(c["tB"].cpu().numpy().view(np.uint64), c["exp"]), (c["m"], c["n"])
+        assert all(torch.equal(c[x], y) for x, y in zip(("tF", "tP", "tQ", "tr"), kept)), "the solve wrote into the decomposition"

@@ -388,3 +388,43 @@ def test_two_streams(oracle):
     _verify(c1)
     _verify(c2)
     assert np.array_equal(iB.cpu().numpy().view(np.uint64), ci["exp"])
+
+
+def test_captured_into_a_graph(oracle):
+    """Paths 0 and 1 of the solve and of the inverse are one launch each and capturable (path 2 blocks and is never captured): a
+    shape of each, solves and inverses in ONE graph on one stream, one chain -- nothing runs, B, Binv, status and rank keep their
+    dirt -- then replayed once.  An ordinary call of each kernel comes first: a process's first call sets function attributes, which
+    is not what this test is about."""
+    solves, invs = [], []
+    for path, (m, n, k, batch) in enumerate([(40, 50, 17, 6), (100, 70, 130, 6)]):
+        _run_solve(oracle, m, n, k, batch, 1500 + m, path=path)
+        c = _solve_case(oracle, m, n, k, batch, 1510 + m)
+        assert (c["status"] == 0).any() and (c["status"] == -1).any() and not np.array_equal(c["exp"], c["hB"])
+        _upload(c)
+        solves.append(c)
+    for path, n in enumerate([37, 100]):
+        _run_inv(oracle, n, 4, 1520 + n, path=path)
+        c = _inv_case(oracle, n, 4, 1530 + n)
+        c["tA"], c["tB"] = (torch.from_numpy(c[x].view(np.int64).copy()).cuda() for x in ("hA", "hB"))
+        c["tr"] = torch.full((4,), -7, dtype=torch.int32, device="cuda")
+        invs.append(c)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        st = torch.cuda.current_stream().cuda_stream
+        for c in solves:
+            _launch(c, st)
+        for c in invs:
+            m4ri_amd.inv_batch_dev(c["tB"].data_ptr(), c["b_stride"], c["b_bs"], c["tA"].data_ptr(), c["a_stride"], c["a_bs"], c["n"], 4,
+                                   c["tr"].data_ptr(), st)
+    torch.cuda.synchronize()
+    for c in solves + invs:
+        assert np.array_equal(c["tB"].cpu().numpy().view(np.uint64), c["hB"]) and (c["tr"] == -7).all()
+    assert all((c["ts"] == -7).all() for c in solves)
+    g.replay()
+    torch.cuda.synchronize()
+    for c in solves:
+        _verify(c)
+    for c in invs:
+        assert np.array_equal(c["tB"].cpu().numpy().view(np.uint64), c["exp"]) and not np.array_equal(c["exp"], c["hB"])
+        assert np.array_equal(c["tA"].cpu().numpy().view(np.uint64), c["hA"]) and np.array_equal(c["tr"].cpu().numpy(), c["rank"])
