@@ -91,7 +91,7 @@ def _stale(target: str, deps: list[str]) -> bool:
 def build(force: bool = False, verbose: bool = True) -> str:
     hipcc = _hipcc()
     os.makedirs(OBJ, exist_ok=True)
-    headers = [os.path.join(CSRC, "gf2_common.h"), os.path.join(CSRC, "gf2_internal.h"), os.path.join(CSRC, "batch_common.h"), os.path.join(CSRC, "dev_scratch.h"), os.path.join(CSRC, "row_gather.h"), os.path.join(CSRC, "subset_rank.h"), os.path.join(CSRC, "transpose_block.h"), os.path.join(CSRC, "scheme444.h"), os.path.join(HERE, "..", "include", "m4ri_amd.h")]
+    headers = [os.path.join(CSRC, "gf2_common.h"), os.path.join(CSRC, "gf2_internal.h"), os.path.join(CSRC, "batch_common.h"), os.path.join(CSRC, "dev_scratch.h"), os.path.join(CSRC, "row_gather.h"), os.path.join(CSRC, "subset_rank.h"), os.path.join(CSRC, "join_common.h"), os.path.join(CSRC, "transpose_block.h"), os.path.join(CSRC, "scheme444.h"), os.path.join(HERE, "..", "include", "m4ri_amd.h")]
     jobs = []
     for src in SOURCES:
         s = os.path.join(CSRC, src)

@@ -3,6 +3,8 @@ the unpacked bits (tests/lists_collide_cases.py: brute force where the lists are
 paths, at the edges of a chunk of the left list and with the right list in slices.  C is the chunk m4ri_amd.lists_collide_units reports.
 Every operand is dirty behind column n and in its padding; every output lies in a frame of sentinels that must come back unchanged, and
 so must every operand.  Every comparison is exact."""
+from math import comb
+
 import numpy as np
 import pytest
 import torch
@@ -425,6 +427,64 @@ def test_materialised_row_sums():
     torch.cuda.synchronize()
     _same(old, new)
     assert 50 <= int(new[3].body()[0]) <= cap
+
+
+def _pair_sums(A):
+    """The sums of two rows of A in colexicographic order of {i < j}: rank C(j, 2) + i."""
+    return np.array([A[i] ^ A[j] for j in range(A.shape[0]) for i in range(j)], dtype=np.uint8).reshape(-1, A.shape[1])
+
+
+def _join_threads(left, left_256, slice_len):
+    """join_threads of join_common.h: 256 threads where they hold the left table and the slice is short."""
+    return 256 if left <= left_256 and slice_len <= 4096 else 1024
+
+
+SCAN_EDGES = [  # k1 = k2, N per side, ell, threads of both kernels, buckets
+    (2, 1, 0, 256, 1),           # one entry, one bucket: every thread but one idle in the scan
+    (20, 190, 0, 256, 1),        # one bucket, every pair a match: all 32-bit bins and the LDS slot counter in use
+    (20, 190, 5, 256, 32),       # fewer buckets than threads
+    (65, 2080, 5, 1024, 32),     # 1024 threads in both kernels, fewer buckets than threads
+    (65, 2080, 13, 1024, 4096),  # q held at ceil(log2 2080) = 12 below ell: four buckets per thread
+]
+
+
+@pytest.mark.parametrize("k1,N,ell,threads,nb", SCAN_EDGES, ids=[f"k{a}-N{b}-ell{c}" for a, b, c, _, _ in SCAN_EDGES])
+def test_both_joins_on_the_scan_edges(k1, N, ell, threads, nb):
+    """The join of the row sums (t1 = t2 = 2) and the join of the two materialised lists share the table's scan, the match report and
+    the output step (join_common.h), so agreeing with each other proves little: each is judged against the NumPy rule on the materialised
+    lists, at the shapes on the edges of the scan.  Both halves are written out by row_sums_words_batch_dev from an iota of keys."""
+    n, stride, seed = 100, 3, 7 * k1 + ell
+    assert N == comb(k1, 2) and m4ri_amd.plan_row_sums_collide_batch(2 * k1, n, k1, 2, 2, ell) == 0
+    assert m4ri_amd.lists_collide_units(N, N, n, ell, 1) == (C, 1, 1) and N <= C         # path 0 in both: the slice is the whole right list
+    assert _join_threads(N, 1024, N) == threads and _join_threads(N, 8 * 256, N) == threads   # rc_kernel: N1 <= 1024; lc_kernel: 8 keys per thread
+    assert 1 << min(ell, (N - 1).bit_length()) == nb
+    rng = np.random.default_rng(seed)
+    Gb = _bits(2 * k1, n, 300 + seed)
+    G = Arr(lc.pack(Gb, stride, rng).ravel())
+    window = _window(n, ell, 400 + seed)
+    cols = Arr(np.array(window + [12345], dtype=np.int32))
+    X, Y = _pair_sums(Gb[:k1]), _pair_sums(Gb[k1:])
+    hist, lightest, keys, count = lc.expect(X, Y, None, window, 0, n, lc.join)
+    assert count >= 1 and (ell > 0 or count == N * N)
+    cap = count + 7
+    iota = Arr(np.arange(N, dtype=np.int64))
+    halves = [Arr(rng.integers(-(1 << 62), 1 << 62, size=N * stride, dtype=np.int64)) for _ in range(2)]
+    for h, off, want in zip(halves, (0, stride * k1), (X, Y)):
+        m4ri_amd.row_sums_words_batch_dev(G.ptr(off), stride, 0, k1, n, 0, 0, 1, k1, 2, 0, iota.ptr(), N, N, 0, h.ptr(), stride, 0)
+        torch.cuda.synchronize()
+        assert np.array_equal(lc.unpack(h.get().reshape(N, stride), n), want), "the materialised list"
+    sums, lists = (Out(n + 1), Out(1), Out(cap), Out(1)), (Out(n + 1), Out(1), Out(cap), Out(1))
+    m4ri_amd.row_sums_collide_list_batch_dev(G.ptr(), stride, 0, 2 * k1, n, 0, 0, 1, k1, 2, 2, cols.ptr(), 0, ell, 0, n, sums[0].p, sums[1].p, sums[2].p, cap, cap,
+                                             sums[3].p)
+    m4ri_amd.lists_collide_batch_dev(halves[0].ptr(), stride, 0, N, halves[1].ptr(), stride, 0, N, n, 0, 0, 1, cols.ptr(), 0, ell, 0, n, lists[0].p, lists[1].p,
+                                     lists[2].p, cap, cap, lists[3].p)
+    torch.cuda.synchronize()
+    for name, o in (("row sums", sums), ("lists", lists)):
+        h, l, lst, cnt = (x.body() for x in o)
+        assert np.array_equal(h, hist), name
+        assert l.tolist() == [lightest] and cnt.tolist() == [count], name
+        assert np.array_equal(np.sort(lst[:count]), keys) and (lst[count:] == SENT).all(), name
+    assert G.unchanged() and cols.unchanged()
 
 
 # ---- the words --------------------------------------------------------------------------------------------------------------------------
