@@ -686,6 +686,61 @@ int m4ri_amd_lists_collide_units(int64_t nx, int64_t ny, int64_t n, int64_t ell,
 int m4ri_amd_lists_words_batch_dev(const word *X, int64_t x_stride, int64_t x_bs, int64_t nx, const word *Y, int64_t y_stride, int64_t y_bs,
                                    int64_t ny, int64_t n, const word *V, int64_t v_bs, int64_t batch, const int64_t *keys, int64_t l_bs, int64_t cap,
                                    const int64_t *count, word *W, int64_t w_stride, int64_t w_bs, int32_t *skipped, void *stream);
+/* The rows of a list of words SORTED and DEDUPLICATED, on the device (sort_rows_batch.hip): what a level list of Wagner's k-tree or of
+ * MMT / BJMM needs between two joins -- after a join on a window equal words are the rule, and the keys of a join come in no
+ * particular order.  Member b has a list X_b, nx rows of n bits at X + b * x_bs words, the rows x_stride words apart (x_bs = 0: one
+ * list shared by all members); X is READ ONLY and only the n valid bits count.  xcount (DEVICE int64, batch entries, or NULL): member
+ * b has m_b = min(max(xcount[b], 0), nx) rows, the clamp of the words calls, so the count of a join still in flight on the same stream
+ * plugs in and a refused member's -1 reads as 0; NULL: nx rows.  The rows from m_b on are NOT read.
+ * cols (DEVICE int32, or NULL): member b's window, ell column indices at cols + b * c_bs entries (c_bs = 0: one window for all
+ * members; NULL: the columns 0 .. ell-1), exactly as in the joins: unsorted, repeated, in any word.
+ * THE ORDER.  Row i goes before row j iff (key_i, w_i[0], ..., w_i[words(n)-1], i) is lexicographically smaller than the same tuple of
+ * j: key is the window bits as an unsigned 64-bit number (bit t = column cols[t]), w[.] are the row's 64-bit words compared as
+ * unsigned numbers, the last one masked to the valid bits, and the index makes the order total.  The result is therefore ONE fixed
+ * permutation, the same on every run and on both paths.  ell = 0 sorts by the words alone.  The window is the caller's discriminator:
+ * after a join on the columns 0 .. l-1 every word is 0 there and word 0 says little, so the natural choice is the NEXT join's window.
+ * Equal keys are settled by reading the rows from memory; a window that separates nothing (ell = 0 on rows whose low words agree, or a
+ * list of few distinct rows) is correct but slow: every comparison then reads both rows.
+ * Outputs, all DEVICE int64, member b's entries at + b * l_bs (ucount: batch entries); at least one of order and ucount is required:
+ * order (or NULL): the entries p < m_b hold the index of the p-th row in that order.
+ * ucount and uniq: ucount[b] = the number of classes of equal rows (equal on the n valid bits); the entries q < ucount[b] of uniq hold
+ * the SMALLEST index of the q-th class, the classes ascending in the order above: the entries of order at the class heads.  The high
+ * 24 bits of an entry are 0, so it is a valid key of m4ri_amd_lists_words_batch_dev with ny = 1 (rank = row index): with Y one zero row,
+ * keys = uniq and count = ucount that call writes the deduplicated sorted list.  uniq may be NULL: ucount alone counts the distinct
+ * rows.  mult (or NULL; needs uniq): mult[q] = the size of class q; a member's entries sum to m_b.
+ * The entries from m_b on (order) or from ucount[b] on (uniq, mult) are NOT written.
+ * A window entry outside 0 .. n-1 cannot be seen by the host, so the device decides: that member is REFUSED, its ucount is -1 and
+ * nothing else of it is written; the other members are unaffected.  nx = 0 or m_b = 0: ucount 0 and no entry.  n = 0 (ell = 0) makes
+ * all rows equal: order 0 .. m_b-1, ucount min(m_b, 1), uniq 0, mult m_b.  batch = 0 succeeds without touching anything.
+ * scratch, scratch_bytes: DEVICE memory of the caller's, 8-byte aligned, at least m4ri_amd_sort_rows_scratch_bytes(nx, n, ell, batch)
+ * bytes, which is 0 (scratch is then ignored) on path 0 of m4ri_amd_plan_sort_rows_batch.  Its content before and after is meaningless.
+ * Limits: n <= 1024, ell <= 64, nx <= 2^24 (an index fits the low 24 bits of a key); beyond them hipErrorNotSupported (801) before any
+ * HIP call.
+ * Asynchronous on `stream` on both paths: plain launches (m4ri_amd_sort_rows_units gives their number), no allocation, no copy to the
+ * host, no synchronisation, no engine workspace, no engine lock, no atomics; capturable.  xcount is read on the device.
+ * hipErrorInvalidValue, before any HIP call, for negative sizes, strides or batch strides, a NULL cols with ell > n, x_stride <
+ * words(n) with nx > 1, l_bs < nx with batch > 1, neither order nor ucount, uniq without ucount, mult without uniq, and with batch > 0
+ * a NULL X where rows are read (n > 0, nx > 0), a scratch that is NULL, misaligned or too small where one is needed, or an output or
+ * the scratch whose bytes (first member's start to last member's nx-th entry) meet another output or the span of X, xcount or cols. */
+int m4ri_amd_sort_rows_batch_dev(const word *X, int64_t x_stride, int64_t x_bs, int64_t nx, int64_t n, const int64_t *xcount, int64_t batch,
+                                 const int32_t *cols, int64_t c_bs, int64_t ell, int64_t *order, int64_t *ucount, int64_t *uniq, int64_t *mult,
+                                 int64_t l_bs, void *scratch, int64_t scratch_bytes, void *stream);
+/* which path the call above takes (pure host arithmetic; -1 for negative sizes; sizes beyond the call's limits are answered by the same
+ * rule): 0 nx is at most the chunk of m4ri_amd_sort_rows_units, one workgroup per member sorts its entries in LDS and writes every
+ * output with plain stores, one launch, no scratch; 1 longer lists, the entries in the caller's scratch: chunks sorted in LDS, merge
+ * levels with their long strides in global memory and their short ones in LDS, then the class heads, a scan and a scatter. */
+int m4ri_amd_plan_sort_rows_batch(int64_t nx, int64_t n, int64_t ell, int64_t batch);
+/* the units of the call above: *chunk_rows = C, the entries one workgroup sorts in LDS (the longest list of path 0); *padded = the
+ * entries the host sizes a member's network by, the smallest power of two >= max(nx, 2) (the device sorts the next power of two of
+ * m_b, which is no larger); *launches = the kernel launches of one call that asks for every output, for a batch within one grid: 1 on
+ * path 0, and with L = log2(padded / C) on path 1 the chunk sort, per level l = 1 .. L its l global strides and one LDS launch, and
+ * four launches for heads, scan, scatter and mult.  Each pointer may be NULL.  Returns 0, or -1 for negative sizes (nothing is stored
+ * then). */
+int m4ri_amd_sort_rows_units(int64_t nx, int64_t n, int64_t ell, int64_t batch, int64_t *chunk_rows, int64_t *padded, int64_t *launches);
+/* the bytes of scratch the sort needs for members of this shape in a batch of this size (pure host arithmetic): 0 on path 0 and for
+ * batch = 0, on path 1 a multiple of 16 that holds per member `padded` entries of 8 + 4 + 1 bytes, a count per 1024 entries and one
+ * word; -1 for negative sizes or a size beyond int64. */
+int64_t m4ri_amd_sort_rows_scratch_bytes(int64_t nx, int64_t n, int64_t ell, int64_t batch);
 /* Assembling, cutting and permuting the members of a batch where they are (assemble_batch.hip).  Conventions of the calls below, as
  * of the other batched calls: member b of X is at X + b * x_bs words, its rows x_stride words apart; a batch stride of 0 on a
  * READ-ONLY operand is one operand shared by all members.  Every call is asynchronous on `stream`: plain launches (several for a

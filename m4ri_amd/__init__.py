@@ -205,6 +205,10 @@ SYMBOLS = {
     "m4ri_amd_plan_lists_collide_batch": (_I, [_I64, _I64, _I64, _I64, _I64]),
     "m4ri_amd_lists_collide_units": (_I, [_I64, _I64, _I64, _I64, _I64, ctypes.POINTER(_I64), ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
     "m4ri_amd_lists_words_batch_dev": (_I, [_P, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I64, _P, _I64, _I64, _P, _I64, _I64, _P, _P, _I64, _I64, _P, _P]),
+    "m4ri_amd_sort_rows_batch_dev": (_I, [_P, _I64, _I64, _I64, _I64, _P, _I64, _P, _I64, _I64, _P, _P, _P, _P, _I64, _P, _I64, _P]),
+    "m4ri_amd_plan_sort_rows_batch": (_I, [_I64, _I64, _I64, _I64]),
+    "m4ri_amd_sort_rows_units": (_I, [_I64, _I64, _I64, _I64, ctypes.POINTER(_I64), ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
+    "m4ri_amd_sort_rows_scratch_bytes": (_I64, [_I64, _I64, _I64, _I64]),
     "m4ri_amd_copy_block_batch_dev": (_I, [_P, _I64, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _P]),
     "m4ri_amd_extract_tri_batch_dev": (_I, [_P, _I64, _I64, _P, _I64, _I64, _I64, _I64, _I64, _I, _I, _P, _P]),
     "m4ri_amd_apply_p_left_batch_dev": (_I, [_P, _I64, _I64, _I64, _I64, _I64, _P, _I64, _I64, _I, _P, _P]),
@@ -751,6 +755,47 @@ def lists_collide_units(nx: int, ny: int, n: int, ell: int, batch: int) -> tuple
     if lib().m4ri_amd_lists_collide_units(nx, ny, n, ell, batch, ctypes.byref(c), ctypes.byref(ch), ctypes.byref(sl)) != 0:
         raise ValueError("lists_collide_units: negative sizes")
     return int(c.value), int(ch.value), int(sl.value)
+
+
+def sort_rows_batch_dev(X: int, x_stride: int, x_bs: int, nx: int, n: int, xcount: int = 0, batch: int = 1, cols: int = 0, c_bs: int = 0, ell: int = 0,
+                        order: int = 0, ucount: int = 0, uniq: int = 0, mult: int = 0, l_bs: int = 0, scratch: int = 0, scratch_bytes: int = 0,
+                        stream: int = 0) -> None:
+    """The rows of the lists X_b (nx rows of n bits, rows x_stride words apart, members x_bs, x_bs = 0 one shared list; the first
+    m_b = min(max(xcount[b], 0), nx) rows count, xcount = 0: nx) sorted and deduplicated on the device.  Row i goes before row j iff
+    (key_i, words of row i as unsigned numbers, i) is lexicographically smaller; key = the bits at the ell window columns (cols: DEVICE
+    int32, member b's at cols + b * c_bs, cols = 0: columns 0 .. ell-1), bit t = column cols[t].  DEVICE int64 outputs, member b's at
+    + b * l_bs, each 0 = not wanted, order or ucount required: order (the row indices in that order), ucount (batch entries: the number
+    of distinct rows), uniq (needs ucount: the smallest index of each class, a valid key of lists_words_batch_dev with ny = 1), mult
+    (needs uniq: the class sizes).  Entries behind m_b / ucount[b] are not written.  A member with a window entry outside 0 .. n-1 is
+    refused on the device: ucount -1, nothing else written.  scratch: DEVICE memory of sort_rows_scratch_bytes(nx, n, ell, batch) bytes
+    (0 on path 0).  n <= 1024, ell <= 64, nx <= 2^24.  Asynchronous, lock-free, no atomics, capturable."""
+    _check(lib().m4ri_amd_sort_rows_batch_dev(X or None, x_stride, x_bs, nx, n, xcount or None, batch, cols or None, c_bs, ell, order or None, ucount or None,
+                                              uniq or None, mult or None, l_bs, scratch or None, scratch_bytes, stream), "m4ri_amd_sort_rows_batch_dev")
+
+
+def plan_sort_rows_batch(nx: int, n: int, ell: int, batch: int) -> int:
+    """The path sort_rows_batch_dev takes (0 one workgroup per member sorts in LDS, one launch, no scratch; 1 the entries in the caller's
+    scratch, chunk sorts and merge levels; -1 negative sizes). Host arithmetic."""
+    return int(lib().m4ri_amd_plan_sort_rows_batch(nx, n, ell, batch))
+
+
+def sort_rows_units(nx: int, n: int, ell: int, batch: int) -> tuple:
+    """(chunk_rows, padded, launches) of sort_rows_batch_dev: the entries one workgroup sorts in LDS (the longest list of path 0), the
+    power of two the host sizes a member's network by, and the kernel launches of a call that asks for every output. Host arithmetic;
+    ValueError for negative sizes."""
+    c, pd, ln = _I64(0), _I64(0), _I64(0)
+    if lib().m4ri_amd_sort_rows_units(nx, n, ell, batch, ctypes.byref(c), ctypes.byref(pd), ctypes.byref(ln)) != 0:
+        raise ValueError("sort_rows_units: negative sizes")
+    return int(c.value), int(pd.value), int(ln.value)
+
+
+def sort_rows_scratch_bytes(nx: int, n: int, ell: int, batch: int) -> int:
+    """The bytes of device scratch sort_rows_batch_dev needs (0 on path 0). Host arithmetic; ValueError for negative sizes or a size
+    beyond int64."""
+    r = int(lib().m4ri_amd_sort_rows_scratch_bytes(nx, n, ell, batch))
+    if r < 0:
+        raise ValueError("sort_rows_scratch_bytes: negative sizes, or beyond int64")
+    return r
 
 
 def row_pair_rank(S1, S2, k1: int, k: int, t2: int) -> int:

@@ -1,11 +1,11 @@
-// The argument checks of the five entry points of the join family (m4ri_amd_row_sums_collide_batch_dev, m4ri_amd_row_sums_collide_list_batch_dev,
-// m4ri_amd_row_sums_words_batch_dev, m4ri_amd_lists_collide_batch_dev, m4ri_amd_lists_words_batch_dev) and their host helpers (plan,
-// slices, units) as a stand-alone program for the host sanitizers: every call returns before any HIP call, so no GPU is needed and no
+// The argument checks of the six entry points of the join family (m4ri_amd_row_sums_collide_batch_dev, m4ri_amd_row_sums_collide_list_batch_dev,
+// m4ri_amd_row_sums_words_batch_dev, m4ri_amd_lists_collide_batch_dev, m4ri_amd_lists_words_batch_dev, m4ri_amd_sort_rows_batch_dev) and their
+// host helpers (plan, slices, units, scratch size) as a stand-alone program for the host sanitizers: every call returns before any HIP call, so no GPU is needed and no
 // pointer is dereferenced.  The expected codes are those of tests/test_row_sums_collide_plan.py, test_row_sums_collide_list_plan.py and
-// test_lists_collide_plan.py.  From the repository root:
+// test_lists_collide_plan.py and test_sort_rows_plan.py.  From the repository root:
 //   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined \
 //         -o join_hostcheck m4ri_amd/csrc/rowsums_collide_batch.hip m4ri_amd/csrc/rowsums_words_batch.hip m4ri_amd/csrc/lists_collide_batch.hip \
-//         tools/join_hostcheck.cpp && ./join_hostcheck
+//         m4ri_amd/csrc/sort_rows_batch.hip tools/join_hostcheck.cpp && ./join_hostcheck
 #include <cstdint>
 #include <cstdio>
 #include "../include/m4ri_amd.h"
@@ -107,6 +107,51 @@ int main() {
   EXPECT(m4ri_amd_row_sums_collide_slices(400, 64, 129, 2, 2, 4, 1), 0);
   EXPECT(m4ri_amd_row_sums_collide_slices(1024, 64, 1, 1, 4, 8, INT64_MAX), (45367119105ll + (1ll << 32) - 2) / ((1ll << 32) - 1));  // C(1023, 4) in slices below 2^32
   EXPECT(m4ri_amd_row_sums_collide_slices(8, 64, 4, 2, 2, 4, -1), -1);
+  // the sort of the rows of a list: two members of 6 rows of 64 bits at X, counts at N, windows at C, order / uniq / mult at K, H, L (l_bs 7), ucount at N + 8
+  int64_t *U = N + 8;
+  void *T = (void *)(1ull << 34);
+  EXPECT(m4ri_amd_sort_rows_batch_dev(X, 1, 6, 6, 64, N, 0, C, 3, 3, K, U, H, L, 7, nullptr, 0, nullptr), 0);
+  EXPECT(m4ri_amd_sort_rows_batch_dev(X, 1, 6, -1, 64, N, 2, C, 3, 3, K, U, H, L, 7, nullptr, 0, nullptr), 1);
+  EXPECT(m4ri_amd_sort_rows_batch_dev(X, 1, 6, 6, 64, N, 2, C, 3, 3, K, U, H, L, 7, nullptr, -1, nullptr), 1);
+  EXPECT(m4ri_amd_sort_rows_batch_dev(X, 0, 6, 6, 64, N, 2, C, 3, 3, K, U, H, L, 7, nullptr, 0, nullptr), 1);                 // x_stride < words(n)
+  EXPECT(m4ri_amd_sort_rows_batch_dev(X, 1, 6, 6, 64, N, 2, C, 3, 3, K, U, H, L, 5, nullptr, 0, nullptr), 1);                 // l_bs < nx
+  EXPECT(m4ri_amd_sort_rows_batch_dev(nullptr, 1, 6, 6, 64, N, 2, C, 3, 3, K, U, H, L, 7, nullptr, 0, nullptr), 1);
+  EXPECT(m4ri_amd_sort_rows_batch_dev(X, 1, 6, 6, 64, N, 2, C, 3, 3, nullptr, nullptr, nullptr, nullptr, 7, nullptr, 0, nullptr), 1);   // no output
+  EXPECT(m4ri_amd_sort_rows_batch_dev(X, 1, 6, 6, 64, N, 2, C, 3, 3, K, nullptr, H, nullptr, 7, nullptr, 0, nullptr), 1);      // uniq without ucount
+  EXPECT(m4ri_amd_sort_rows_batch_dev(X, 1, 6, 6, 64, N, 2, C, 3, 3, K, U, nullptr, L, 7, nullptr, 0, nullptr), 1);            // mult without uniq
+  EXPECT(m4ri_amd_sort_rows_batch_dev(X, 1, 6, 6, 2, N, 2, nullptr, 3, 3, K, U, H, L, 7, nullptr, 0, nullptr), 1);             // ell > n, no window
+  EXPECT(m4ri_amd_sort_rows_batch_dev(X, 1, 6, 6, 64, N, 2, C, 3, 3, (int64_t *)X + 11, U, H, L, 7, nullptr, 0, nullptr), 1);  // order on X's last word
+  EXPECT(m4ri_amd_sort_rows_batch_dev(X, 1, 6, 6, 64, N, 2, C, 3, 3, K, N + 1, H, L, 7, nullptr, 0, nullptr), 1);              // ucount on xcount
+  EXPECT(m4ri_amd_sort_rows_batch_dev(X, 1, 6, 6, 64, N, 2, C, 3, 3, K, U, K + 12, L, 7, nullptr, 0, nullptr), 1);             // uniq on order's last entry
+  EXPECT(m4ri_amd_sort_rows_batch_dev(X, 1, 6, 6, 64, N, 2, C, 3, 3, K, U, (int64_t *)(C + 4), L, 7, nullptr, 0, nullptr), 1); // uniq on the windows
+  EXPECT(m4ri_amd_sort_rows_batch_dev(X, 17, 6, 6, 1025, N, 2, C, 3, 3, K, U, H, L, 7, nullptr, 0, nullptr), 801);
+  EXPECT(m4ri_amd_sort_rows_batch_dev(X, 1, 6, 6, 64, N, 2, C, 65, 65, K, U, H, L, 7, nullptr, 0, nullptr), 801);
+  EXPECT(m4ri_amd_sort_rows_batch_dev(X, 1, 6, (1ll << 24) + 1, 64, N, 0, C, 3, 3, K, U, H, L, 1ll << 25, nullptr, 0, nullptr), 801);
+  EXPECT(m4ri_amd_sort_rows_batch_dev(X, 1, 6, INT64_MAX, 64, N, 2, C, 3, 3, K, U, H, L, INT64_MAX, nullptr, 0, nullptr), 801);
+  EXPECT(m4ri_amd_sort_rows_batch_dev(X, 1, 1 << 24, 1 << 24, 64, N, 0, C, 3, 3, K, U, H, L, 1 << 24, nullptr, 0, nullptr), 0);
+  const int64_t need = m4ri_amd_sort_rows_scratch_bytes(10000, 64, 3, 2);
+  EXPECT(need, (2 * (16384 * 13 + 16 * 4 + 4) + 15) / 16 * 16);
+  EXPECT(m4ri_amd_sort_rows_batch_dev(X, 1, 10000, 10000, 64, N, 2, C, 3, 3, K, U, H, L, 10000, nullptr, need, nullptr), 1);   // no scratch
+  EXPECT(m4ri_amd_sort_rows_batch_dev(X, 1, 10000, 10000, 64, N, 2, C, 3, 3, K, U, H, L, 10000, T, need - 1, nullptr), 1);     // too small
+  EXPECT(m4ri_amd_sort_rows_batch_dev(X, 1, 10000, 10000, 64, N, 2, C, 3, 3, K, U, H, L, 10000, (char *)T + 4, need, nullptr), 1);   // misaligned
+  EXPECT(m4ri_amd_sort_rows_batch_dev(X, 1, 10000, 10000, 64, N, 2, C, 3, 3, K, U, H, L, 10000, (char *)U - need + 8, need, nullptr), 1);   // its end on ucount
+  EXPECT(m4ri_amd_sort_rows_batch_dev(X, 1, 10000, 10000, 64, N, 0, C, 3, 3, K, U, H, L, 10000, nullptr, 0, nullptr), 0);
+  EXPECT(m4ri_amd_sort_rows_scratch_bytes(8192, 1024, 64, 1000), 0);
+  EXPECT(m4ri_amd_sort_rows_scratch_bytes(1 << 24, 1024, 64, INT64_MAX), -1);
+  EXPECT(m4ri_amd_sort_rows_scratch_bytes(INT64_MAX, 1024, 64, INT64_MAX), -1);
+  EXPECT(m4ri_amd_sort_rows_scratch_bytes(-1, 64, 3, 2), -1);
+  EXPECT(m4ri_amd_plan_sort_rows_batch(8192, 64, 3, 2), 0);
+  EXPECT(m4ri_amd_plan_sort_rows_batch(8193, 64, 3, 2), 1);
+  EXPECT(m4ri_amd_plan_sort_rows_batch(INT64_MAX, 64, 3, INT64_MAX), 1);
+  EXPECT(m4ri_amd_plan_sort_rows_batch(5, 64, -3, 2), -1);
+  int64_t sc = 0, sp = 0, sl2 = 0;
+  EXPECT(m4ri_amd_sort_rows_units(4 * 8192 + 3, 64, 3, 1, &sc, &sp, &sl2), 0);
+  EXPECT(sc, 8192);
+  EXPECT(sp, 65536);
+  EXPECT(sl2, 1 + (1 + 2 + 3) + 3 + 4);
+  EXPECT(m4ri_amd_sort_rows_units(INT64_MAX, 64, 3, INT64_MAX, &sc, &sp, &sl2), 0);
+  EXPECT(m4ri_amd_sort_rows_units(0, 0, 0, 0, nullptr, nullptr, nullptr), 0);
+  EXPECT(m4ri_amd_sort_rows_units(5, 64, 3, -1, &sc, &sp, &sl2), -1);
   printf("%d checks, %d failed\n", n, fails);
   return fails != 0;
 }
