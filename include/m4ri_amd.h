@@ -874,6 +874,54 @@ int m4ri_amd_plan_echelonize_order_batch(int64_t nrows, int64_t ncols);
  * hipErrorNotSupported (801).  hipErrorInvalidValue for negative n, batch or o_bs, o_bs < n with batch > 1, or a NULL order with
  * batch > 0 and n > 0. */
 int m4ri_amd_random_orders_batch_dev(int32_t *order, int64_t o_bs, int64_t n, int64_t batch, uint64_t seed, void *stream);
+/* `steps` PIVOT EXCHANGES on the stored reduced echelon forms of `batch` members, one launch (pivot_exchange_batch.hip): the move from
+ * one information set to the next in information-set decoding, one pivot step on a form that is already reduced instead of an
+ * elimination from scratch.  The state is what m4ri_amd_echelonize_order_batch_dev(full = 1) left: D_b, nrows x ncols at D + b * d_bs
+ * words, rows d_stride apart, in place; pivots (DEVICE int32, in/out), member b's pm = min(pivot_rows, ncols) entries at b * pm, entry
+ * i the pivot column of row i; rank (DEVICE int32, batch entries, READ ONLY).  R_b = min(max(rank[b], 0), pm): a refused member's -1
+ * reads as 0.  The rows from pivot_rows on only follow.
+ * The rule.  For s = 0 .. steps-1, in this order, member b:
+ * 1. The request (r, c).  With req (DEVICE int32): r = req[b * r_bs + 2 s], c = req[b * r_bs + 2 s + 1] (r_bs = 0: one list for all
+ *    members).  With req == NULL it is drawn on the device so that any host reproduces it (m4ri_amd.exchange_draw in the Python layer):
+ *    h = output number b * steps + s of the counter-form splitmix64 stream seeded `seed` (the stream of m4ri_amd_fill_dev and
+ *    m4ri_amd_random_orders_batch_dev); if R_b = 0 the step is skipped; else r = (h >> 32) mod R_b, start = (h & 0xffffffff) mod ncols,
+ *    and c = the first column in the cyclic order start, start + 1, ..., ncols - 1, 0, ..., start - 1 with bit (r, c) of the current D_b
+ *    set and c != pivots[r]; if there is none the step is skipped.
+ * 2. Validity, decided on the device.  The step is performed iff 0 <= r < R_b, 0 <= c < ncols, bit (r, c) is set and c != pivots[r];
+ *    otherwise it is skipped: nothing is written, and no index is formed from the request.  On a reduced form a column that is another
+ *    row's pivot has bit (r, c) clear, so such a request falls out here.
+ * 3. The exchange.  Every row i != r of all nrows rows, followers included, with bit c set becomes row i ^ row r.  old = pivots[r],
+ *    then pivots[r] = c.  With order (DEVICE int32, in/out, member b's olen entries at order + b * o_bs; NULL or olen = 0: none kept):
+ *    p = the first position with order[p] == old, q = the first with order[q] == c; if both exist the two entries are swapped,
+ *    otherwise order is unchanged.  Entries of order are only compared, never used as indices: they need no range check.
+ * done[b] (DEVICE int32, batch entries, or NULL) = the number of steps performed, written whole.  Only the valid bits of D_b are
+ * written: never the bits at columns >= ncols, the words from the width to the stride or the words between members; a member with
+ * no performed step is not written at all.  After the call D_b is again the reduced form for the new pivots, so calls chain.  For
+ * full-rank members the result equals m4ri_amd_echelonize_order_batch_dev(A, order = the new pivots, full = 1) bit for bit, followers
+ * included: the reduced form on an information set is unique.  With an order kept (the order the form was made on), cols = order + k
+ * stays a window of non-information columns for m4ri_amd_row_sums_collide_batch_dev.
+ * hipErrorInvalidValue, before any HIP call, for negative sizes, strides, batch strides or steps, pivot_rows > nrows, olen > ncols,
+ * d_stride < words(ncols), overlapping D members (batch > 1 and d_bs < (nrows - 1) * d_stride + width), r_bs < 2 * steps with
+ * r_bs != 0 and batch > 1, o_bs < olen with an order and batch > 1 (order is written: it cannot be shared), a NULL D, pivots or rank
+ * with non-empty members and steps > 0, or any two of D's span, pivots, rank, req, order and done whose bytes meet.  batch = 0
+ * succeeds without touching anything; steps = 0 writes done (zeros) only.  Members beyond path 2 of
+ * m4ri_amd_plan_pivot_exchange_batch return hipErrorNotSupported (801), nothing touched.  Asynchronous on `stream`: plain launches
+ * (one, several for a batch beyond one grid), no allocation, no copy to the host, no synchronisation, no engine lock, no atomics;
+ * capturable. */
+int m4ri_amd_pivot_exchange_batch_dev(word *D, int64_t d_stride, int64_t d_bs, int64_t nrows, int64_t ncols, int64_t pivot_rows, int32_t *pivots,
+                                      const int32_t *rank, int64_t batch, const int32_t *req, int64_t r_bs, int64_t steps, uint64_t seed,
+                                      int32_t *order, int64_t o_bs, int64_t olen, int32_t *done, void *stream);
+/* which path the call above takes for members of this shape and this many steps (pure host arithmetic; -1 for negative sizes or
+ * steps): 0 one wave per member, lane i holds row i and pivots[i], lane j order[j] (nrows, ncols <= 64); 1 one workgroup per member,
+ * the member staged in LDS for all steps (rows padded to an odd number of words, a row index, one flag buffer, 128 bytes of slots and
+ * an order of ncols entries, within 160 KiB) and steps != 1; 2 one workgroup per member in place in D_b (valid words up to 512 KiB),
+ * which a call of ONE step takes for members that would fit in LDS too: a step in place touches only the rows with the bit while
+ * staging moves the whole member, and as measured (steps = 1, 4 and 16) in place wins at one step and loses at four;
+ * 3 above the cap: the call returns 801.  The environment variables M4RI_AMD_PIVOT_EXCHANGE_PATH0_MAX (the largest side of path 0,
+ * clamped to [0, 64]) and M4RI_AMD_PIVOT_EXCHANGE_PATH1_MAX (the LDS bytes of path 1, clamped to [0, 163840]; when it is set, it
+ * alone decides between paths 1 and 2, at any step count) replace the bounds in the routing of a call, read per call; this function
+ * does not read them. */
+int m4ri_amd_plan_pivot_exchange_batch(int64_t nrows, int64_t ncols, int64_t steps);
 /* `batch` independent systems A_b X_b = B_b (mzd_solve_left, m4ri/solve.c:30-152; solve_batch.hip).  A_b: the m x n matrix at
  * A + b * a_bs, READ ONLY (a_bs = 0: one A shared by all members).  B_b: the max(m, n) x k matrix at B + b * b_bs.  status[b]
  * (DEVICE int32, required): 0, or -1 when A_b X = B_b has no solution, A_b padded with zero rows to max(m, n).  On status 0, B_b is

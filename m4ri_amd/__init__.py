@@ -228,6 +228,8 @@ SYMBOLS = {
     "m4ri_amd_echelonize_order_batch_dev": (_I, [_P, _I64, _I64, _P, _I64, _I64, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I, _P, _P, _P]),
     "m4ri_amd_plan_echelonize_order_batch": (_I, [_I64, _I64]),
     "m4ri_amd_random_orders_batch_dev": (_I, [_P, _I64, _I64, _I64, ctypes.c_uint64, _P]),
+    "m4ri_amd_pivot_exchange_batch_dev": (_I, [_P, _I64, _I64, _I64, _I64, _I64, _P, _P, _I64, _P, _I64, _I64, ctypes.c_uint64, _P, _I64, _I64, _P, _P]),
+    "m4ri_amd_plan_pivot_exchange_batch": (_I, [_I64, _I64, _I64]),
     "m4ri_amd_solve_left_batch_dev": (_I, [_P, _I64, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I64, _P, _P, _P]),
     "m4ri_amd_inv_batch_dev": (_I, [_P, _I64, _I64, _P, _I64, _I64, _I64, _I64, _P, _P]),
     "m4ri_amd_plan_solve_batch": (_I, [_I64, _I64, _I64]),
@@ -927,6 +929,37 @@ def random_order(seed: int, b: int, n: int):
         raise ValueError("random_order: 0 <= n <= 4096")
     keys = (splitmix_words(seed, b * n, n) & ~np.uint64(4095)) | np.arange(n, dtype=np.uint64)
     return (np.sort(keys) & np.uint64(4095)).astype(np.int32)
+
+
+def pivot_exchange_batch_dev(D: int, d_stride: int, d_bs: int, nrows: int, ncols: int, pivot_rows: int, pivots: int, rank: int, batch: int,
+                             req: int = 0, r_bs: int = 0, steps: int = 0, seed: int = 0, order: int = 0, o_bs: int = 0, olen: int = 0, done: int = 0,
+                             stream: int = 0) -> None:
+    """`steps` pivot exchanges in place on the reduced forms echelonize_order_batch_dev(full=1) left in D_b, with its pivots (DEVICE
+    int32, in/out) and rank (DEVICE int32, read only).  Step s of member b takes the request (r, c) = the DEVICE int32 entries 2 s and
+    2 s + 1 at req + b * r_bs (r_bs = 0: one list for all), or with req 0 draws it from the stream seeded `seed` (exchange_draw); a
+    request that is not valid -- r not a pivot row, c not a column, bit (r, c) clear, c the row's own pivot -- is skipped.  A performed
+    step adds row r into every other row with bit c, sets pivots[r] = c and swaps the old and the new pivot column in member b's olen
+    DEVICE int32 entries at order + b * o_bs (order 0: none kept).  done (DEVICE int32, 0 = not wanted): the steps performed per
+    member.  Asynchronous, lock-free and capturable on paths 0-2 of plan_pivot_exchange_batch; path 3: 801."""
+    _check(lib().m4ri_amd_pivot_exchange_batch_dev(D or None, d_stride, d_bs, nrows, ncols, pivot_rows, pivots or None, rank or None, batch, req or None,
+                                                   r_bs, steps, seed & 0xFFFFFFFFFFFFFFFF, order or None, o_bs, olen, done or None, stream),
+           "m4ri_amd_pivot_exchange_batch_dev")
+
+
+def plan_pivot_exchange_batch(nrows: int, ncols: int, steps: int) -> int:
+    """The path pivot_exchange_batch_dev takes for members of this shape and this many steps (0 wave, 1 LDS, 2 global, 3 not supported).
+    Host arithmetic."""
+    return int(lib().m4ri_amd_plan_pivot_exchange_batch(nrows, ncols, steps))
+
+
+def exchange_draw(seed: int, b: int, steps: int, s: int, rank: int, ncols: int):
+    """(r, start) of step s of member b in a call of pivot_exchange_batch_dev without requests: output number b * steps + s of the
+    splitmix64 stream seeded `seed`, its high half mod the member's rank and its low half mod ncols.  The column exchanged is the first
+    one from start on, cyclically, at which row r has a bit and which is not its own pivot."""
+    if rank < 1 or ncols < 1 or not 0 <= s < steps or b < 0:
+        raise ValueError("exchange_draw: rank >= 1, ncols >= 1, 0 <= s < steps, b >= 0")
+    h = int(splitmix_words(seed, b * steps + s, 1)[0])
+    return (h >> 32) % rank, (h & 0xFFFFFFFF) % ncols
 
 
 def solve_left_batch_dev(A: int, a_stride: int, a_bs: int, m: int, n: int, B: int, b_stride: int, b_bs: int, k: int, batch: int, status: int,
