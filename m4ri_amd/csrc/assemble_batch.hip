@@ -19,8 +19,6 @@
 //      m4ri_amd_apply_p_right_dev on a clean scratch copy.  Allocates and BLOCKS.
 // Paths 0 and 1 and the copy kernel are plain launches on the caller's stream: no allocation, no copy, no engine workspace.
 #include <hip/hip_runtime.h>
-#include <stdlib.h>
-#include <mutex>
 #include <vector>
 #include "batch_common.h"
 #include "transpose_block.h"
@@ -138,13 +136,6 @@ int launch_copy(CopyArgs p, int64_t rows, int64_t batch, hipStream_t st) {
   return 0;
 }
 
-// the span in bytes of `batch` blocks of `rows` rows, words [w0, w1) of each row, from the first one's first word to the last one's
-// last; *first = its start
-uintptr_t block_span(const word *X, int64_t stride, int64_t bs, int64_t row, int64_t w0, int64_t w1, int64_t rows, int64_t batch, const void **first) {
-  *first = X + row * stride + w0;
-  return member_span_bytes(batch, bs, rows, stride, w1 - w0);
-}
-
 // ---- the permutations -------------------------------------------------------------------------------------------------------------
 
 __device__ __forceinline__ word transposed(word x, int lane) {
@@ -251,15 +242,7 @@ __global__ void perm_status_kernel(int32_t *status, int64_t batch) {
   for (int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; b < batch; b += (int64_t)gridDim.x * blockDim.x) status[b] = 0;
 }
 
-int64_t perm_lds_bytes(int64_t nrows, int64_t ncols, int right) { return nrows * words_of(ncols) * 8 + 8 * (right ? ncols : nrows) + 8; }
-
-// an environment bound of this call: `dflt` unless the variable is set; clamped to [0, hi]
-int64_t env_bound(const char *name, int64_t dflt, int64_t hi) {
-  const char *s = getenv(name);
-  if (!s || !*s) return dflt;
-  const int64_t v = atoll(s);
-  return v < 0 ? 0 : v > hi ? hi : v;
-}
+int64_t perm_lds_bytes(int64_t nrows, int64_t ncols, int right) { return nrows * width_of(ncols) * 8 + 8 * (right ? ncols : nrows) + 8; }
 
 // p0: the largest side of path 0; p1: the LDS bytes path 1 may use.  Measured (tools/bench_assemble_batch.py,
 // profiles/assemble_batch_bench.txt) on 256 MiB of members, every spread under 1 %: at 64 x 64 path 0 beats path 1 3.2x on
@@ -268,7 +251,7 @@ int64_t env_bound(const char *name, int64_t dflt, int64_t hi) {
 int plan_perm(int64_t nrows, int64_t ncols, int right, int64_t p0, int64_t p1) {
   if (nrows < 0 || ncols < 0) return -1;
   if (nrows <= p0 && ncols <= p0) return 0;
-  const int64_t width = words_of(ncols);
+  const int64_t width = width_of(ncols);
   if (nrows > p1 / 8 || width > p1 / 8 || ncols > p1 / 8 || nrows * width > p1 / 8) return 2;
   return perm_lds_bytes(nrows, ncols, right) <= p1 ? 1 : 2;
 }
@@ -276,7 +259,7 @@ int plan_perm(int64_t nrows, int64_t ncols, int right, int64_t p0, int64_t p1) {
 // path 2.  A validated call with non-empty members and L > 0.
 int run_perm_path2(word *A, int64_t stride, int64_t a_bs, int64_t nrows, int64_t ncols, int64_t batch, const int32_t *P, int64_t p_bs, int64_t L, int right,
                    int trans, int32_t *status, hipStream_t st) {
-  const int64_t width = words_of(ncols), n = right ? ncols : nrows;
+  const int64_t width = width_of(ncols), n = right ? ncols : nrows;
   std::vector<int32_t> hp((size_t)((batch - 1) * p_bs + L)), hs((size_t)batch, 0);
   HIPTRY(hipMemcpyAsync(hp.data(), P, hp.size() * 4, hipMemcpyDeviceToHost, st));
   HIPTRY(hipStreamSynchronize(st));
@@ -301,16 +284,14 @@ int run_perm_path2(word *A, int64_t stride, int64_t a_bs, int64_t nrows, int64_t
 int apply_p_batch(word *A, int64_t stride, int64_t a_bs, int64_t nrows, int64_t ncols, int64_t batch, const int32_t *P, int64_t p_bs, int64_t length,
                   int trans, int32_t *status, int right, hipStream_t st) {
   if (nrows < 0 || ncols < 0 || batch < 0 || stride < 0 || a_bs < 0 || p_bs < 0 || length < 0) return (int)hipErrorInvalidValue;
-  const int64_t width = words_of(ncols), n = right ? ncols : nrows;
+  const int64_t width = width_of(ncols), n = right ? ncols : nrows;
   const bool data = nrows > 0 && ncols > 0;
   if (data && stride < width) return (int)hipErrorInvalidValue;
-  if (batch > 1 && data && a_bs < (nrows - 1) * stride + width) return (int)hipErrorInvalidValue;
+  if (data && !members_fit(batch, a_bs, nrows, stride, width)) return (int)hipErrorInvalidValue;
   const int64_t L = length < n ? length : n;
   if (batch > 0 && data && (!A || (L > 0 && !P))) return (int)hipErrorInvalidValue;
   if (batch == 0 || !data) return 0;
-  const uintptr_t a_span = member_span_bytes(batch, a_bs, nrows, stride, width), p_span = (uintptr_t)(((batch - 1) * p_bs + L) * 4);
-  if (L > 0 && spans_meet(A, a_span, P, p_span)) return (int)hipErrorInvalidValue;
-  if (status && (spans_meet(status, (uintptr_t)batch * 4, A, a_span) || (L > 0 && spans_meet(status, (uintptr_t)batch * 4, P, p_span))))
+  if (spans_meet_any({rows_span(A, batch, a_bs, nrows, stride, width), entries_span(status, batch, 1, 1, 4)}, {entries_span(P, batch, p_bs, L, 4)}))
     return (int)hipErrorInvalidValue;
   if (L == 0) {  // the identity
     if (!status) return 0;
@@ -319,26 +300,19 @@ int apply_p_batch(word *A, int64_t stride, int64_t a_bs, int64_t nrows, int64_t 
     return (int)hipGetLastError();
   }
   const int asc  = right ? trans != 0 : trans == 0;
-  const int path = plan_perm(nrows, ncols, right, env_bound("M4RI_AMD_PERM_BATCH_PATH0_MAX", 64, 64),
-                             env_bound("M4RI_AMD_PERM_BATCH_PATH1_MAX", BATCH_LDS_BUDGET, BATCH_LDS_BUDGET));
-  if (path == 0) {
-    const int64_t per = BATCH_WAVE_THREADS / 64;
-    return launch_chunked(batch, BATCH_CHUNK * per, [&](int64_t b0, int64_t nb) {
-      hipLaunchKernelGGL(perm_wave_kernel, dim3((unsigned)((nb + per - 1) / per)), dim3(BATCH_WAVE_THREADS), 0, st, A, stride, a_bs, (int)nrows, (int)ncols, P,
-                         p_bs, (int)L, right, asc, status, b0, b0 + nb);
+  const int path = plan_perm(nrows, ncols, right, env_bound("M4RI_AMD_PERM_BATCH_PATH0_MAX", 64, 0, 64),
+                             env_bound("M4RI_AMD_PERM_BATCH_PATH1_MAX", BATCH_LDS_BUDGET, 0, BATCH_LDS_BUDGET));
+  if (path == 0)
+    return launch_waves(batch, [&](dim3 grid, int64_t b0, int64_t nb) {
+      hipLaunchKernelGGL(perm_wave_kernel, grid, dim3(BATCH_WAVE_THREADS), 0, st, A, stride, a_bs, (int)nrows, (int)ncols, P, p_bs, (int)L, right, asc, status,
+                         b0, b0 + nb);
     });
-  }
   if (path == 2) return run_perm_path2(A, stride, a_bs, nrows, ncols, batch, P, p_bs, L, right, trans, status, st);
-  static std::once_flag once;
-  static hipError_t attr = hipSuccess;
-  std::call_once(once, [] {
-    attr = hipFuncSetAttribute(reinterpret_cast<const void *>(perm_block_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)BATCH_LDS_BUDGET);
-  });
-  HIPTRY(attr);
+  HIPTRY(set_max_dynamic_lds(BATCH_LDS_BUDGET, perm_block_kernel));
   const size_t lds  = (size_t)(nrows * width * 8 + 4 * (L + n) + 8);
   const int threads = block_threads(nrows, width);
-  return launch_chunked(batch, BATCH_CHUNK, [&](int64_t b0, int64_t nb) {
-    hipLaunchKernelGGL(perm_block_kernel, dim3((unsigned)nb), dim3(threads), lds, st, A, stride, a_bs, (int)nrows, (int)ncols, P, p_bs, (int)L, right, asc,
+  return launch_members(batch, [&](dim3 grid, int64_t b0) {
+    hipLaunchKernelGGL(perm_block_kernel, grid, dim3(threads), lds, st, A, stride, a_bs, (int)nrows, (int)ncols, P, p_bs, (int)L, right, asc,
                        status, b0);
   });
 }
@@ -353,15 +327,16 @@ int m4ri_amd_copy_block_batch_dev(word *D, int64_t d_stride, int64_t d_bs, int64
     return (int)hipErrorInvalidValue;
   if (cols > 64 * ASM_MAX_UNITS - 64 || d_col > INT64_MAX - cols - 64 || a_col > INT64_MAX - cols - 64) return (int)hipErrorInvalidValue;
   const bool data  = rows > 0 && cols > 0;
-  const int64_t d0 = d_col >> 6, d1 = words_of(d_col + cols), a0 = a_col >> 6, a1 = words_of(a_col + cols);
+  const int64_t d0 = d_col >> 6, d1 = width_of(d_col + cols), a0 = a_col >> 6, a1 = width_of(a_col + cols);
   if (data && (d_stride < d1 || a_stride < a1)) return (int)hipErrorInvalidValue;
-  if (batch > 1 && data && d_bs < (rows - 1) * d_stride + (d1 - d0)) return (int)hipErrorInvalidValue;
+  if (data && !members_fit(batch, d_bs, rows, d_stride, d1 - d0)) return (int)hipErrorInvalidValue;
   if (batch > 0 && data && (!D || !A)) return (int)hipErrorInvalidValue;
   if (batch == 0 || !data) return 0;
-  const void *df, *af;
-  const uintptr_t dn = block_span(D, d_stride, d_bs, d_row, d0, d1, rows, batch, &df);
-  const uintptr_t an = block_span(A, a_stride, a_bs, a_row, a0, a1, rows, batch, &af);
-  if (spans_meet(df, dn, af, an)) return (int)hipErrorInvalidValue;
+  // the blocks: words [d0, d1) and [a0, a1) of `rows` rows from d_row and a_row on.  One that starts beyond the address space is refused.
+  const wide d_first = (wide)d_row * (wide)d_stride + (wide)d0, a_first = (wide)a_row * (wide)a_stride + (wide)a0, space = (wide)1 << 61;
+  if (d_first >= space || a_first >= space) return (int)hipErrorInvalidValue;
+  if (spans_meet(rows_span(D, batch, d_bs, rows, d_stride, d1 - d0, (int64_t)d_first), rows_span(A, batch, a_bs, rows, a_stride, a1 - a0, (int64_t)a_first)))
+    return (int)hipErrorInvalidValue;
   CopyArgs p{};
   p.D = D + d_row * d_stride, p.A = A + a_row * a_stride;
   p.d_stride = d_stride, p.d_bs = d_bs, p.a_stride = a_stride, p.a_bs = a_bs;
@@ -377,15 +352,14 @@ int m4ri_amd_extract_tri_batch_dev(word *D, int64_t d_stride, int64_t d_bs, cons
   if (diag < 0 || diag > 2) return (int)hipErrorInvalidValue;
   if (nrows > INT32_MAX || ncols > INT32_MAX) return (int)hipErrorInvalidValue;  // a rank: 32 bits
   const int64_t k = nrows < ncols ? nrows : ncols, rows = upper ? k : nrows, cols = upper ? ncols : k;
-  const int64_t wd = words_of(cols), wa = words_of(ncols);
+  const int64_t wd = width_of(cols), wa = width_of(ncols);
   const bool data  = k > 0;
   if (data && (d_stride < wd || a_stride < wa)) return (int)hipErrorInvalidValue;
-  if (batch > 1 && data && d_bs < (rows - 1) * d_stride + wd) return (int)hipErrorInvalidValue;
+  if (data && !members_fit(batch, d_bs, rows, d_stride, wd)) return (int)hipErrorInvalidValue;
   if (batch > 0 && data && (!D || !A)) return (int)hipErrorInvalidValue;
   if (batch == 0 || !data) return 0;
-  const uintptr_t dn = member_span_bytes(batch, d_bs, rows, d_stride, wd);
-  if (spans_meet(D, dn, A, member_span_bytes(batch, a_bs, nrows, a_stride, wa))) return (int)hipErrorInvalidValue;
-  if (rank && spans_meet(D, dn, rank, (uintptr_t)batch * 4)) return (int)hipErrorInvalidValue;
+  if (spans_meet_any({rows_span(D, batch, d_bs, rows, d_stride, wd)}, {rows_span(A, batch, a_bs, nrows, a_stride, wa), entries_span(rank, batch, 1, 1, 4)}))
+    return (int)hipErrorInvalidValue;
   CopyArgs p{};
   p.D = D, p.A = A, p.d_stride = d_stride, p.d_bs = d_bs, p.a_stride = a_stride, p.a_bs = a_bs;
   p.cols = cols, p.nw = (uint32_t)wd, p.tri = upper ? 1 : 2, p.diag = diag, p.rank = rank, p.k = k;

@@ -283,10 +283,7 @@ __global__ __launch_bounds__(AUX_THREADS) void fill_splitmix_kernel(word *__rest
   const int64_t gstr   = (int64_t)gridDim.x * AUX_THREADS;
   for (int64_t i = (int64_t)blockIdx.x * AUX_THREADS + threadIdx.x; i < total; i += gstr) {
     const int64_t r = i / w, j = i - r * w;
-    uint64_t z = seed + (uint64_t)(first + i + 1) * 0x9E3779B97F4A7C15ull;  // first = row0 * w: rows of a larger matrix
-    z          = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z          = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    z ^= z >> 31;
+    uint64_t z = splitmix64(seed, (uint64_t)(first + i));  // first = row0 * w: rows of a larger matrix
     if (j == w - 1) z &= mask;
     M[r * stride + j] = z;
   }

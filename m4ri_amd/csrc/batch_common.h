@@ -1,6 +1,6 @@
-// batch_common.h -- what the batched small-matrix calls share (echelon_batch.hip, solve_batch.hip, ple_batch.hip and the launch side
-// of mul_small_batch.hip): the launch constants, the device pieces of the workgroup-per-member elimination (one column at a time:
-// flag pass, pivot search, row swap, update) and the host scaffolding around the launches.  Everything here is internal to the file
+// batch_common.h -- what the batched calls (the *_batch.hip files, join_common.h) share: the launch constants, the device pieces of the
+// workgroup-per-member elimination (one column at a time: flag pass, pivot search, row swap, update) and the host side of a call: its
+// argument checks (widths, environment bounds, member fit, spans) and its launches.  Everything here is internal to the file
 // that includes it (an unnamed namespace, as in those files); the kernels stay in their files, and so do the bodies of the wave
 // kernels, which carry a different payload per lane.
 //
@@ -12,6 +12,9 @@
 // global memory; a column without a pivot writes nothing, and the next flag pass uses the other flag buffer.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <cstdlib>
+#include <initializer_list>
+#include <mutex>
 #include <vector>
 #include "dev_scratch.h"  // Scratch: the device temporaries of a one-by-one path
 #include "gf2_internal.h"
@@ -175,6 +178,26 @@ inline int64_t lds_row_words(int64_t width) { return width + ((width & 1) ^ 1); 
 
 inline int block_threads(int64_t rows, int64_t width) { return rows * width >= 8192 ? BATCH_MAX_THREADS : 256; }
 
+// words(ncols) for any ncols >= 0, INT64_MAX included (words_of adds 63 first)
+inline int64_t width_of(int64_t ncols) { return ncols / 64 + (ncols % 64 != 0); }
+
+// LDS bytes of a member staged with its row index and `flag_bufs` flag buffers, `extra` bytes behind them
+inline int64_t lds_bytes_staged(int64_t nrows, int64_t width, int flag_bufs, int64_t extra) {
+  return nrows * lds_row_words(width) * 8 + (int64_t)pad16((size_t)nrows * 4) + flag_bufs * ((nrows + 63) / 64) * 8 + extra;
+}
+
+// The paths of the calls that walk a member's columns on an order given per member (echelon_order_batch.hip, pivot_exchange_batch.hip).
+// p0: the largest side of path 0; p1: the LDS bytes path 1 may use for lds_bytes_staged and the order, counted at its longest, ncols
+// entries; in_place: path 2 although the member fits.
+inline int plan_on_order(int64_t nrows, int64_t ncols, int64_t p0, int64_t p1, int flag_bufs, int64_t extra, bool in_place = false) {
+  if (nrows < 0 || ncols < 0) return -1;
+  if (nrows <= p0 && ncols <= p0) return 0;
+  const int64_t width = width_of(ncols), cap = BATCH_CAP_BYTES / 8;
+  if (nrows > cap || width > cap || nrows * width > cap) return 3;
+  if (in_place) return 2;
+  return lds_bytes_staged(nrows, width, flag_bufs, extra) + 4 * ncols <= p1 ? 1 : 2;
+}
+
 // fn(b0, cnt) launches members b0 .. b0 + cnt - 1, at most members_per_launch of them (what BATCH_CHUNK workgroups hold); the
 // launch error is checked after each
 template <typename Fn>
@@ -186,14 +209,86 @@ int launch_chunked(int64_t batch, int64_t members_per_launch, Fn fn) {
   return 0;
 }
 
-// bytes from the first member's start to the last member's end (batch, rows > 0)
-inline uintptr_t member_span_bytes(int64_t batch, int64_t bs, int64_t rows, int64_t stride, int64_t width) {
-  return (uintptr_t)(((batch - 1) * bs + (rows - 1) * stride + width) * 8);
+// ---- the host side of a batched call -----------------------------------------------------------------------------------
+// Every size, stride and pointer below comes from a caller: nothing here overflows on the way to its answer, which is the one the
+// comparison has over the integers.
+
+using wide = unsigned __int128;
+
+// An environment bound of a call, read per call: `dflt` unless the variable is set; rounded down to a multiple, then clamped to [lo, hi].
+inline int64_t env_bound(const char *name, int64_t dflt, int64_t lo, int64_t hi, int64_t multiple_of = 1) {
+  const char *s = getenv(name);
+  if (!s || !*s) return dflt;
+  const int64_t v = strtoll(s, nullptr, 10) / multiple_of * multiple_of;
+  return v < lo ? lo : v > hi ? hi : v;
 }
 
-// do [p, p + pn) and [q, q + qn) (bytes) meet?
-inline bool spans_meet(const void *p, uintptr_t pn, const void *q, uintptr_t qn) {
-  return (uintptr_t)p < (uintptr_t)q + qn && (uintptr_t)q < (uintptr_t)p + pn;
+// May `batch` members of `rows` rows, `stride` words apart and `width` words wide, lie bs words apart?  (No sign is negative.)
+inline bool members_fit(int64_t batch, int64_t bs, int64_t rows, int64_t stride, int64_t width) {
+  return !(batch > 1 && rows > 0 && (wide)bs < (wide)(rows - 1) * (wide)stride + (wide)width);
+}
+
+// The bytes [lo, hi) of an operand, from its first member's start to its last member's end; lo == hi: absent, empty or not read.
+// A count beyond the address space is held at 2^64 entries: such a span ends behind every pointer either way.
+struct Span {
+  wide lo, hi;
+};
+
+inline Span span_of(const void *p, wide first, wide count, int size) {
+  const wide all = (wide)1 << 64, lo = (wide)(uintptr_t)p + first * (wide)size;
+  return Span{lo, lo + (count < all ? count : all) * (wide)size};
+}
+
+// rows of `width` words (nothing where there are none), from word `first_word` of M on
+inline Span rows_span(const word *M, int64_t batch, int64_t bs, int64_t rows, int64_t stride, int64_t width, int64_t first_word = 0) {
+  if (!M || batch <= 0 || rows <= 0 || width <= 0) return Span{0, 0};
+  return span_of(M, (wide)first_word, (wide)(batch - 1) * (wide)bs + (wide)(rows - 1) * (wide)stride + (wide)width, 8);
+}
+
+// `count` entries of `size` bytes per member, bs entries apart
+inline Span entries_span(const void *p, int64_t batch, int64_t bs, wide count, int size) {
+  if (!p || batch <= 0 || count == 0) return Span{0, 0};
+  return span_of(p, 0, (wide)(batch - 1) * (wide)bs + count, size);
+}
+
+inline bool spans_meet(Span a, Span b) { return a.lo < a.hi && b.lo < b.hi && a.lo < b.hi && b.lo < a.hi; }
+
+// does one of the outputs meet another, or an operand?
+inline bool spans_meet_any(std::initializer_list<Span> outs, std::initializer_list<Span> operands = {}) {
+  for (const Span *o = outs.begin(); o != outs.end(); ++o) {
+    for (const Span *o2 = o + 1; o2 != outs.end(); ++o2)
+      if (spans_meet(*o, *o2)) return true;
+    for (const Span &in : operands)
+      if (spans_meet(*o, in)) return true;
+  }
+  return false;
+}
+
+// The most dynamic LDS a kernel may be launched with is an attribute of the kernel.  It is set on the given kernels (a NULL among them
+// is passed over) by the first call through each instantiation and the result kept: once per process for a call site, as long as no
+// other site of the file passes kernels of the same types -- Site tells such sites apart.
+template <int Site = 0, typename... Kernels>
+hipError_t set_max_dynamic_lds(size_t bytes, Kernels... kernels) {
+  static std::once_flag once;
+  static hipError_t attr = hipSuccess;
+  std::call_once(once, [&] {
+    for (const void *k : {reinterpret_cast<const void *>(kernels)...})
+      if (k && attr == hipSuccess) attr = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  });
+  return attr;
+}
+
+// the workgroup-per-member kernels: fn(grid, b0) launches members b0 .. b0 + grid.x - 1
+template <typename Fn>
+int launch_members(int64_t batch, Fn fn) {
+  return launch_chunked(batch, BATCH_CHUNK, [&](int64_t b0, int64_t nb) { fn(dim3((unsigned)nb), b0); });
+}
+
+// the wave kernels, four members per workgroup: fn(grid, b0, nb) launches members b0 .. b0 + nb - 1
+template <typename Fn>
+int launch_waves(int64_t batch, Fn fn) {
+  const int64_t per = BATCH_WAVE_THREADS / 64;
+  return launch_chunked(batch, BATCH_CHUNK * per, [&](int64_t b0, int64_t nb) { fn(dim3((unsigned)((nb + per - 1) / per)), b0, nb); });
 }
 
 // a clean copy (tail bits zero) of the rows x ncols matrix at src into scratch
@@ -206,7 +301,7 @@ inline int clean_copy(word *dst, int64_t dst_stride, const word *src, int64_t sr
 // are rows r0 .. r1-1 of the k-column matrix at M (stride words) all zero?  Copies them to the host.  Blocking.
 inline int rows_zero(const word *M, int64_t stride, int64_t r0, int64_t r1, int64_t k, hipStream_t st, bool *zero) {
   *zero = true;
-  const int64_t w = words_of(k);
+  const int64_t w = width_of(k);
   if (r1 <= r0 || w == 0) return 0;
   std::vector<word> h((size_t)((r1 - r0) * w));
   HIPTRY(hipMemcpy2DAsync(h.data(), (size_t)w * 8, M + r0 * stride, (size_t)stride * 8, (size_t)w * 8, (size_t)(r1 - r0), hipMemcpyDeviceToHost, st));

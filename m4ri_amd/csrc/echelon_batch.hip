@@ -14,7 +14,6 @@
 // Memory rules: bits at columns >= ncols of a row's last word are never changed, nor the words from `width` to `stride` of a row,
 // nor anything between members.
 #include <hip/hip_runtime.h>
-#include <mutex>
 #include <vector>
 #include "batch_common.h"
 #include "../../include/m4ri_amd.h"
@@ -181,7 +180,7 @@ int64_t lds_bytes_path1(int64_t nrows, int64_t width) {
 
 int run_path3(word *A, int64_t stride, int64_t a_bs, int64_t nrows, int64_t ncols, int64_t batch, int full, int32_t *rank, int32_t *pivots,
               hipStream_t st) {
-  const int64_t width = words_of(ncols), mn = nrows < ncols ? nrows : ncols;
+  const int64_t width = width_of(ncols), mn = nrows < ncols ? nrows : ncols;
   const word mask     = tail_mask((int)(ncols & 63));
   const int64_t total = batch * nrows;
   word *save          = nullptr;
@@ -215,7 +214,7 @@ extern "C" {
 int m4ri_amd_plan_echelonize_batch(int64_t nrows, int64_t ncols) {
   if (nrows < 0 || ncols < 0) return -1;
   if (nrows <= 64 && ncols <= 64) return 0;
-  const int64_t width = words_of(ncols);
+  const int64_t width = width_of(ncols);
   if (nrows > BATCH_CAP_BYTES / 8 || width > BATCH_CAP_BYTES / 8 || nrows * width > BATCH_CAP_BYTES / 8) return 3;
   return lds_bytes_path1(nrows, width) <= BATCH_LDS_BUDGET ? 1 : 2;
 }
@@ -223,9 +222,9 @@ int m4ri_amd_plan_echelonize_batch(int64_t nrows, int64_t ncols) {
 int m4ri_amd_echelonize_batch_dev(word *A, int64_t stride, int64_t a_bs, int64_t nrows, int64_t ncols, int64_t batch, int full, int32_t *rank,
                                   int32_t *pivots, void *stream) {
   if (nrows < 0 || ncols < 0 || batch < 0 || stride < 0 || a_bs < 0) return (int)hipErrorInvalidValue;
-  const int64_t width = words_of(ncols);
+  const int64_t width = width_of(ncols);
   if (stride < width) return (int)hipErrorInvalidValue;
-  if (batch > 1 && nrows > 0 && a_bs < (nrows - 1) * stride + width) return (int)hipErrorInvalidValue;
+  if (!members_fit(batch, a_bs, nrows, stride, width)) return (int)hipErrorInvalidValue;
   if (batch > 0 && !rank) return (int)hipErrorInvalidValue;
   if (batch > 0 && nrows > 0 && ncols > 0 && !A) return (int)hipErrorInvalidValue;
   if (batch == 0) return 0;
@@ -233,30 +232,19 @@ int m4ri_amd_echelonize_batch_dev(word *A, int64_t stride, int64_t a_bs, int64_t
   if (nrows == 0 || ncols == 0) return (int)hipMemsetAsync(rank, 0, (size_t)batch * 4, st);  // min(nrows, ncols) = 0: no pivots
   const int mn   = (int)(nrows < ncols ? nrows : ncols);
   const int path = m4ri_amd_plan_echelonize_batch(nrows, ncols);
-  if (path == 0) {
-    const int64_t per = BATCH_WAVE_THREADS / 64;
-    return launch_chunked(batch, BATCH_CHUNK * per, [&](int64_t b0, int64_t n) {
-      hipLaunchKernelGGL(eb_wave_kernel, dim3((unsigned)((n + per - 1) / per)), dim3(BATCH_WAVE_THREADS), 0, st, A, stride, a_bs, (int)nrows, (int)ncols,
-                         b0, batch, full, rank, pivots, mn);
+  if (path == 0)
+    return launch_waves(batch, [&](dim3 grid, int64_t b0, int64_t) {
+      hipLaunchKernelGGL(eb_wave_kernel, grid, dim3(BATCH_WAVE_THREADS), 0, st, A, stride, a_bs, (int)nrows, (int)ncols, b0, batch, full, rank, pivots, mn);
     });
-  }
   if (path == 3) return run_path3(A, stride, a_bs, nrows, ncols, batch, full, rank, pivots, st);
   const bool inlds   = path == 1;
   const int threads  = block_threads(nrows, width);
   const int ldw      = inlds ? (int)lds_row_words(width) : 0;
   const size_t lds   = inlds ? (size_t)lds_bytes_path1(nrows, width) : (size_t)(2 * ((nrows + 63) / 64) * 8);
-  static std::once_flag once;
-  std::call_once(once, [] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(eb_block_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)BATCH_LDS_BUDGET);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(eb_block_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)BATCH_LDS_BUDGET);
-  });
-  return launch_chunked(batch, BATCH_CHUNK, [&](int64_t b0, int64_t n) {
-    if (inlds)
-      hipLaunchKernelGGL(eb_block_kernel<true>, dim3((unsigned)n), dim3(threads), lds, st, A, stride, a_bs, (int)nrows, (int)ncols, ldw, b0, full, rank,
-                         pivots, mn);
-    else
-      hipLaunchKernelGGL(eb_block_kernel<false>, dim3((unsigned)n), dim3(threads), lds, st, A, stride, a_bs, (int)nrows, (int)ncols, ldw, b0, full, rank,
-                         pivots, mn);
+  HIPTRY(set_max_dynamic_lds(BATCH_LDS_BUDGET, eb_block_kernel<true>, eb_block_kernel<false>));
+  return launch_members(batch, [&](dim3 grid, int64_t b0) {
+    if (inlds) hipLaunchKernelGGL(eb_block_kernel<true>, grid, dim3(threads), lds, st, A, stride, a_bs, (int)nrows, (int)ncols, ldw, b0, full, rank, pivots, mn);
+    else hipLaunchKernelGGL(eb_block_kernel<false>, grid, dim3(threads), lds, st, A, stride, a_bs, (int)nrows, (int)ncols, ldw, b0, full, rank, pivots, mn);
   });
 }
 

@@ -17,8 +17,6 @@
 // The order is range-checked by the whole wave or workgroup before the first write to global memory; a member with a bad entry gets
 // rank -1, pivots -1, and its D_b is not written.
 #include <hip/hip_runtime.h>
-#include <cstdlib>
-#include <mutex>
 #include "batch_common.h"
 #include "../../include/m4ri_amd.h"
 
@@ -210,30 +208,8 @@ __global__ __launch_bounds__(BATCH_MAX_THREADS) void eo_block_kernel(EoArgs p, i
   if (t == 0) p.rank[b] = rank;
 }
 
-// LDS bytes of path 1 without the order
-int64_t lds_bytes_rows(int64_t nrows, int64_t width) {
-  return nrows * lds_row_words(width) * 8 + (int64_t)pad16((size_t)nrows * 4) + 2 * ((nrows + 63) / 64) * 8 + 4 * EO_VOTES;
-}
-
-// an environment bound of this call: `dflt` unless the variable is set; clamped to [0, hi]
-int64_t env_bound(const char *name, int64_t dflt, int64_t hi) {
-  const char *s = getenv(name);
-  if (!s || !*s) return dflt;
-  const int64_t v = atoll(s);
-  return v < 0 ? 0 : v > hi ? hi : v;
-}
-
-// words(ncols) for any ncols >= 0, INT64_MAX included (words_of adds 63 first)
-int64_t width_of(int64_t ncols) { return ncols / 64 + (ncols % 64 != 0); }
-
-// p0: the largest side of path 0; p1: the LDS bytes path 1 may use (the order counted at its longest, ncols entries)
-int plan(int64_t nrows, int64_t ncols, int64_t p0, int64_t p1) {
-  if (nrows < 0 || ncols < 0) return -1;
-  if (nrows <= p0 && ncols <= p0) return 0;
-  const int64_t width = width_of(ncols), cap = BATCH_CAP_BYTES / 8;
-  if (nrows > cap || width > cap || nrows * width > cap) return 3;
-  return lds_bytes_rows(nrows, width) + 4 * ncols <= p1 ? 1 : 2;
-}
+// path 1 stages two flag buffers and the votes; p0, p1: plan_on_order's
+int plan(int64_t nrows, int64_t ncols, int64_t p0, int64_t p1) { return plan_on_order(nrows, ncols, p0, p1, 2, 4 * EO_VOTES); }
 
 // ---- random orders ------------------------------------------------------------------------------------------------------------------
 
@@ -249,10 +225,7 @@ __global__ __launch_bounds__(BATCH_MAX_THREADS) void eo_random_orders_kernel(int
   for (int j = t; j < N; j += T) {
     uint64_t z = ~(uint64_t)0;
     if (j < n) {
-      z = seed + ((uint64_t)b * (uint64_t)n + (uint64_t)j + 1) * 0x9E3779B97F4A7C15ull;
-      z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-      z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-      z ^= z >> 31;
+      z = splitmix64(seed, (uint64_t)b * (uint64_t)n + (uint64_t)j);
       z = (z & ~(uint64_t)4095) | (uint64_t)j;
     }
     keys[j] = z;
@@ -288,26 +261,22 @@ int m4ri_amd_echelonize_order_batch_dev(word *D, int64_t d_stride, int64_t d_bs,
   const int64_t width = width_of(ncols);
   if (d_stride < width || a_stride < width) return (int)hipErrorInvalidValue;
   // the cap next: below it a member's word counts are small
-  const int path = plan(nrows, ncols, env_bound("M4RI_AMD_ECH_ORDER_PATH0_MAX", 64, 64),
-                        env_bound("M4RI_AMD_ECH_ORDER_PATH1_MAX", BATCH_LDS_BUDGET, BATCH_LDS_BUDGET));
+  const int path = plan(nrows, ncols, env_bound("M4RI_AMD_ECH_ORDER_PATH0_MAX", 64, 0, 64),
+                        env_bound("M4RI_AMD_ECH_ORDER_PATH1_MAX", BATCH_LDS_BUDGET, 0, BATCH_LDS_BUDGET));
   if (path == 3) return (int)hipErrorNotSupported;
   const bool data = nrows > 0 && ncols > 0;
-  if (batch > 1 && data && d_bs < (nrows - 1) * d_stride + width) return (int)hipErrorInvalidValue;
+  if (data && !members_fit(batch, d_bs, nrows, d_stride, width)) return (int)hipErrorInvalidValue;
   const bool in_place = (const word *)D == A && d_stride == a_stride && d_bs == a_bs;
   if (in_place && a_bs == 0 && batch > 1) return (int)hipErrorInvalidValue;
   const int64_t pm = pivot_rows < ncols ? pivot_rows : ncols;
   if (batch > 0) {
     if (!rank) return (int)hipErrorInvalidValue;
     if (data && (!A || !D)) return (int)hipErrorInvalidValue;
-    // the spans, bytes; an absent or empty operand meets nothing
-    const void *ptr[5]  = {D, A, order, rank, pivots};
-    const uintptr_t n[5] = {data ? member_span_bytes(batch, d_bs, nrows, d_stride, width) : 0,
-                            data ? member_span_bytes(batch, a_bs, nrows, a_stride, width) : 0,
-                            order && olen > 0 ? (uintptr_t)(((batch - 1) * o_bs + olen) * 4) : 0, (uintptr_t)batch * 4,
-                            pivots ? (uintptr_t)(batch * pm) * 4 : 0};
-    auto meet = [&](int x, int y) { return ptr[x] && ptr[y] && n[x] && n[y] && spans_meet(ptr[x], n[x], ptr[y], n[y]); };
-    if (!in_place && meet(0, 1)) return (int)hipErrorInvalidValue;
-    if (meet(0, 2) || meet(0, 3) || meet(0, 4) || meet(3, 4) || meet(3, 2) || meet(4, 2)) return (int)hipErrorInvalidValue;
+    // D against A unless in place; D, rank and pivots against each other and the order.  rank and pivots are not held against A.
+    const Span d = rows_span(D, batch, d_bs, nrows, d_stride, width);
+    if (!in_place && spans_meet(d, rows_span(A, batch, a_bs, nrows, a_stride, width))) return (int)hipErrorInvalidValue;
+    if (spans_meet_any({d, entries_span(rank, batch, 1, 1, 4), entries_span(pivots, batch, pm, pm, 4)}, {entries_span(order, batch, o_bs, olen, 4)}))
+      return (int)hipErrorInvalidValue;
   }
   if (batch == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
@@ -317,27 +286,18 @@ int m4ri_amd_echelonize_order_batch_dev(word *D, int64_t d_stride, int64_t d_bs,
   p.order = olen > 0 ? order : nullptr, p.o_bs = o_bs, p.olen = (int)olen;
   p.nrows = (int)nrows, p.ncols = (int)ncols, p.pivot_rows = (int)pivot_rows, p.pm = (int)pm, p.full = full;
   p.rank = rank, p.pivots = pivots;
-  if (path == 0) {
-    const int64_t per = BATCH_WAVE_THREADS / 64;
-    return launch_chunked(batch, BATCH_CHUNK * per, [&](int64_t b0, int64_t nb) {
-      hipLaunchKernelGGL(eo_wave_kernel, dim3((unsigned)((nb + per - 1) / per)), dim3(BATCH_WAVE_THREADS), 0, st, p, b0, b0 + nb);
+  if (path == 0)
+    return launch_waves(batch, [&](dim3 grid, int64_t b0, int64_t nb) {
+      hipLaunchKernelGGL(eo_wave_kernel, grid, dim3(BATCH_WAVE_THREADS), 0, st, p, b0, b0 + nb);
     });
-  }
-  static std::once_flag once;
-  static hipError_t attr = hipSuccess;
-  std::call_once(once, [] {
-    attr = hipFuncSetAttribute(reinterpret_cast<const void *>(eo_block_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)BATCH_LDS_BUDGET);
-    if (attr == hipSuccess)
-      attr = hipFuncSetAttribute(reinterpret_cast<const void *>(eo_block_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)BATCH_LDS_BUDGET);
-  });
-  HIPTRY(attr);
+  HIPTRY(set_max_dynamic_lds(BATCH_LDS_BUDGET, eo_block_kernel<true>, eo_block_kernel<false>));
   const bool inlds  = path == 1;
   const int threads = block_threads(nrows, width);
   const int ldw     = inlds ? (int)lds_row_words(width) : 0;
-  const size_t lds  = inlds ? (size_t)(lds_bytes_rows(nrows, width) + (p.order ? 4 * olen : 0)) : (size_t)(2 * ((nrows + 63) / 64) * 8 + 4 * EO_VOTES);
-  return launch_chunked(batch, BATCH_CHUNK, [&](int64_t b0, int64_t nb) {
-    if (inlds) hipLaunchKernelGGL(eo_block_kernel<true>, dim3((unsigned)nb), dim3(threads), lds, st, p, ldw, b0);
-    else hipLaunchKernelGGL(eo_block_kernel<false>, dim3((unsigned)nb), dim3(threads), lds, st, p, ldw, b0);
+  const size_t lds  = inlds ? (size_t)(lds_bytes_staged(nrows, width, 2, 4 * EO_VOTES) + (p.order ? 4 * olen : 0)) : (size_t)(2 * ((nrows + 63) / 64) * 8 + 4 * EO_VOTES);
+  return launch_members(batch, [&](dim3 grid, int64_t b0) {
+    if (inlds) hipLaunchKernelGGL(eo_block_kernel<true>, grid, dim3(threads), lds, st, p, ldw, b0);
+    else hipLaunchKernelGGL(eo_block_kernel<false>, grid, dim3(threads), lds, st, p, ldw, b0);
   });
 }
 
@@ -351,8 +311,8 @@ int m4ri_amd_random_orders_batch_dev(int32_t *order, int64_t o_bs, int64_t n, in
   while (N < n) N *= 2;
   const int threads = N / 2 < 64 ? 64 : N / 2 > BATCH_MAX_THREADS ? BATCH_MAX_THREADS : N / 2;
   hipStream_t st    = (hipStream_t)stream;
-  return launch_chunked(batch, BATCH_CHUNK, [&](int64_t b0, int64_t nb) {
-    hipLaunchKernelGGL(eo_random_orders_kernel, dim3((unsigned)nb), dim3(threads), 0, st, order, o_bs, (int)n, N, seed, b0);
+  return launch_members(batch, [&](dim3 grid, int64_t b0) {
+    hipLaunchKernelGGL(eo_random_orders_kernel, grid, dim3(threads), 0, st, order, o_bs, (int)n, N, seed, b0);
   });
 }
 

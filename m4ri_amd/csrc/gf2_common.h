@@ -21,6 +21,18 @@ struct DMat {
 
 static inline int64_t words_of(int64_t ncols) { return (ncols + 63) >> 6; }
 
+// Output number k of the counter-form splitmix64 stream seeded `seed`: what m4ri_amd_fill_dev, m4ri_amd_random_orders_batch_dev and
+// the drawn requests of m4ri_amd_pivot_exchange_batch_dev document as their random bits.
+#ifdef __HIP__
+__host__ __device__ __attribute__((always_inline))
+#endif
+static inline uint64_t splitmix64(uint64_t seed, uint64_t k) {
+  uint64_t z = seed + (k + 1) * 0x9E3779B97F4A7C15ull;
+  z          = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z          = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+
 // HIP device ids the per-device tables hold (engines, arenas, solver scratch): 0 .. GF2_MAX_DEVICES - 1
 constexpr int GF2_MAX_DEVICES = 16;
 

@@ -16,8 +16,6 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <limits.h>
-#include <initializer_list>
-#include <mutex>
 #include "batch_common.h"
 #include "subset_rank.h"  // RS_N_MAX, RS_SUMS_MAX: the limits of a word and of a rank, which every call of the family has
 
@@ -231,41 +229,13 @@ __global__ __launch_bounds__(THREADS) void join_init_kernel(JoinInit p) {
 
 template <int THREADS = BATCH_WAVE_THREADS>
 int join_launch_init(hipStream_t st, JoinInit p, int64_t batch) {
-  return launch_chunked(batch, BATCH_CHUNK, [&](int64_t b0, int64_t nb) {
+  return launch_members(batch, [&](dim3 grid, int64_t b0) {
     p.b0 = b0;
-    hipLaunchKernelGGL(join_init_kernel<THREADS>, dim3((unsigned)nb), dim3(THREADS), 0, st, p);
+    hipLaunchKernelGGL(join_init_kernel<THREADS>, grid, dim3(THREADS), 0, st, p);
   });
 }
 
 // ---- the host side of a join --------------------------------------------------------------------------------------------------------------
-
-// an operand's bytes from the first member's start to the last member's end; p = NULL: not there, or not read
-struct JoinSpan {
-  const void *p;
-  uintptr_t bytes;
-};
-
-// the n-bit rows of an operand, nothing where it has no words
-inline JoinSpan join_rows_span(const word *M, int64_t batch, int64_t bs, int64_t rows, int64_t stride, int64_t n) {
-  return M && batch > 0 && rows > 0 && n > 0 ? JoinSpan{M, member_span_bytes(batch, bs, rows, stride, words_of(n))} : JoinSpan{nullptr, 0};
-}
-
-// count entries of `size` bytes per member, bs entries apart
-inline JoinSpan join_entries_span(const void *p, int64_t batch, int64_t bs, int64_t count, int size) {
-  return p && batch > 0 && count > 0 ? JoinSpan{p, ((uintptr_t)(batch - 1) * (uintptr_t)bs + (uintptr_t)count) * (uintptr_t)size} : JoinSpan{nullptr, 0};
-}
-
-// does one of the outputs meet another, or an operand?
-inline bool join_spans_meet(std::initializer_list<JoinSpan> outs, std::initializer_list<JoinSpan> operands) {
-  for (const JoinSpan *o = outs.begin(); o != outs.end(); ++o) {
-    if (!o->p) continue;
-    for (const JoinSpan *o2 = o + 1; o2 != outs.end(); ++o2)
-      if (o2->p && spans_meet(o->p, o->bytes, o2->p, o2->bytes)) return true;
-    for (const JoinSpan &in : operands)
-      if (in.p && spans_meet(o->p, o->bytes, in.p, in.bytes)) return true;
-  }
-  return false;
-}
 
 // the rules of the window and of the outputs that come after the limits of a call
 inline int join_check_outputs(const int32_t *cols, int64_t ell, int64_t n, const int64_t *hist, const int64_t *lightest, const int64_t *list, int64_t l_bs,
@@ -279,10 +249,10 @@ inline int join_check_outputs(const int32_t *cols, int64_t ell, int64_t n, const
 
 // do the four outputs (batch > 0) meet each other or an operand?  The window is an operand of every join.
 inline bool join_outputs_meet(int64_t *hist, int64_t *lightest, int64_t *list, int64_t l_bs, int64_t cap, int64_t *count, int64_t batch, int64_t n,
-                              const int32_t *cols, int64_t c_bs, int64_t ell, JoinSpan a, JoinSpan b, JoinSpan c = {nullptr, 0}) {
-  return join_spans_meet({join_entries_span(hist, batch, n + 1, n + 1, 8), join_entries_span(lightest, batch, 1, 1, 8), join_entries_span(count, batch, 1, 1, 8),
-                          join_entries_span(count ? list : nullptr, batch, l_bs, cap, 8)},
-                         {a, b, c, join_entries_span(cols, batch, c_bs, ell, 4)});
+                              const int32_t *cols, int64_t c_bs, int64_t ell, Span a, Span b, Span c = {0, 0}) {
+  return spans_meet_any({entries_span(hist, batch, n + 1, n + 1, 8), entries_span(lightest, batch, 1, 1, 8), entries_span(count, batch, 1, 1, 8),
+                         entries_span(count ? list : nullptr, batch, l_bs, cap, 8)},
+                        {a, b, c, entries_span(cols, batch, c_bs, ell, 4)});
 }
 
 // the initialisation of a call; hist0, light_v and count_v as path 1's atomics need them
@@ -335,19 +305,13 @@ using JoinKernels = const JoinKernel<Args>[2][2][2];
 template <typename Args>
 int join_launch(JoinKernels<Args> &kernels, size_t lds_max, hipStream_t st, const JoinInit &in, int64_t batch, Args &p, int64_t units, int threads,
                 size_t lds) {
-  static std::once_flag once;  // per Args, not per table: a second table of kernels with the same argument struct would need its own
-  static hipError_t attr = hipSuccess;
-  std::call_once(once, [&] {
-    for (int i = 1; i < 8; ++i)
-      if (attr == hipSuccess)
-        attr = hipFuncSetAttribute(reinterpret_cast<const void *>(kernels[i >> 2][(i >> 1) & 1][i & 1]), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max);
-  });
-  HIPTRY(attr);
+  // once per Args, not per table: a second table of kernels with the same argument struct would need a Site of its own
+  HIPTRY(set_max_dynamic_lds(lds_max, kernels[0][0][1], kernels[0][1][0], kernels[0][1][1], kernels[1][0][0], kernels[1][0][1], kernels[1][1][0], kernels[1][1][1]));
   if (p.atomic) HIPTRY(join_launch_init(st, in, batch));
   const JoinKernel<Args> kernel = kernels[p.count != nullptr][p.hist != nullptr][p.lightest != nullptr];
-  return launch_chunked(units, BATCH_CHUNK, [&](int64_t u0, int64_t nu) {
+  return launch_members(units, [&](dim3 grid, int64_t u0) {
     p.u0 = u0;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)nu), dim3((unsigned)threads), lds, st, p);
+    hipLaunchKernelGGL(kernel, grid, dim3((unsigned)threads), lds, st, p);
   });
 }
 
@@ -416,14 +380,14 @@ __device__ __forceinline__ void join_words(const JoinWords &p, Index (&rows)[JOI
 
 // The checks of a words call that follow its limits and its operands' strides.  missing: a row operand that is read is NULL.
 inline int join_words_check(int64_t n, int64_t batch, const int64_t *keys, int64_t l_bs, int64_t cap, const int64_t *count, const word *W, int64_t w_stride,
-                            int64_t w_bs, const int32_t *skipped, bool missing, JoinSpan a, JoinSpan b, JoinSpan c = {nullptr, 0}) {
-  const int64_t width = words_of(n);
+                            int64_t w_bs, const int32_t *skipped, bool missing, Span a, Span b, Span c = {0, 0}) {
+  const int64_t width = width_of(n);
   if (cap > 1 && w_stride < width) return (int)hipErrorInvalidValue;
-  if (batch > 1 && cap > 0 && (l_bs < cap || (n > 0 && (__int128)w_bs < (__int128)(cap - 1) * w_stride + width))) return (int)hipErrorInvalidValue;
+  if (batch > 1 && cap > 0 && (l_bs < cap || (n > 0 && !members_fit(batch, w_bs, cap, w_stride, width)))) return (int)hipErrorInvalidValue;
   if (batch > 0 && cap > 0) {
     if (!keys || (n > 0 && !W) || missing) return (int)hipErrorInvalidValue;
-    if (join_spans_meet({join_rows_span(W, batch, w_bs, cap, w_stride, n), join_entries_span(skipped, batch, 1, 1, 4)},
-                        {a, b, c, join_entries_span(keys, batch, l_bs, cap, 8), join_entries_span(count, batch, 1, 1, 8)}))
+    if (spans_meet_any({rows_span(W, batch, w_bs, cap, w_stride, width), entries_span(skipped, batch, 1, 1, 4)},
+                       {a, b, c, entries_span(keys, batch, l_bs, cap, 8), entries_span(count, batch, 1, 1, 8)}))
       return (int)hipErrorInvalidValue;
   }
   return 0;
@@ -439,14 +403,14 @@ int join_words_launch(void (*kernel)(Args), Args &p, int64_t n, int64_t batch, c
   if (cap == 0) return 0;
   JoinWords &o = p.o;
   o.keys = keys, o.count = count, o.W = W, o.skipped = skipped, o.l_bs = l_bs, o.cap = cap, o.w_stride = w_stride, o.w_bs = w_bs;
-  o.width = (int)words_of(n), o.group = 1;
+  o.width = (int)width_of(n), o.group = 1;
   while (o.group < o.width) o.group <<= 1;
   o.mask = tail_mask((int)(n & 63)), o.pairs = pairs;
   o.chunks = (cap + JOIN_WORDS_ROWS - 1) / JOIN_WORDS_ROWS;
   if (batch > INT64_MAX / o.chunks) return (int)hipErrorInvalidValue;
-  return launch_chunked(batch * o.chunks, BATCH_CHUNK, [&](int64_t u0, int64_t nu) {
+  return launch_members(batch * o.chunks, [&](dim3 grid, int64_t u0) {
     o.u0 = u0;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)nu), dim3(JOIN_WORDS_ROWS), 0, st, p);
+    hipLaunchKernelGGL(kernel, grid, dim3(JOIN_WORDS_ROWS), 0, st, p);
   });
 }
 

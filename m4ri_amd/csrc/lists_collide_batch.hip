@@ -258,13 +258,13 @@ int m4ri_amd_lists_collide_batch_dev(const word *X, int64_t x_stride, int64_t x_
   if (unsupported(nx, ny, n) || ell > JOIN_ELL_MAX) return (int)hipErrorNotSupported;
   const int64_t pairs = nx * ny;  // at most 2^40
   if (const int e = join_check_outputs(cols, ell, n, hist, lightest, list, l_bs, cap, count, batch)) return e;
-  const int64_t width = words_of(n);
+  const int64_t width = width_of(n);
   if (n > 0 && ((nx > 1 && x_stride < width) || (ny > 1 && y_stride < width))) return (int)hipErrorInvalidValue;
   const bool walked = pairs > 0 && n > 0;  // rows are read
   if (batch > 0) {
     if (walked && (!X || !Y)) return (int)hipErrorInvalidValue;
-    if (join_outputs_meet(hist, lightest, list, l_bs, cap, count, batch, n, cols, c_bs, ell, join_rows_span(X, batch, x_bs, nx, x_stride, n),
-                          join_rows_span(Y, batch, y_bs, ny, y_stride, n), join_rows_span(V, batch, v_bs, 1, 0, n)))
+    if (join_outputs_meet(hist, lightest, list, l_bs, cap, count, batch, n, cols, c_bs, ell, rows_span(X, batch, x_bs, nx, x_stride, width),
+                          rows_span(Y, batch, y_bs, ny, y_stride, width), rows_span(V, batch, v_bs, 1, 0, width)))
       return (int)hipErrorInvalidValue;
   }
   if (batch == 0) return 0;
@@ -294,12 +294,12 @@ int m4ri_amd_lists_words_batch_dev(const word *X, int64_t x_stride, int64_t x_bs
     return (int)hipErrorInvalidValue;
   if (unsupported(nx, ny, n)) return (int)hipErrorNotSupported;
   const int64_t pairs = nx * ny;
-  const int64_t width = words_of(n);
+  const int64_t width = width_of(n);
   if (n > 0 && ((nx > 1 && x_stride < width) || (ny > 1 && y_stride < width))) return (int)hipErrorInvalidValue;
   const bool read = pairs > 0 && n > 0;  // rows of X and Y are read
   if (const int e = join_words_check(n, batch, keys, l_bs, cap, count, W, w_stride, w_bs, skipped, read && (!X || !Y),
-                                     join_rows_span(X, batch, x_bs, nx, x_stride, n), join_rows_span(Y, batch, y_bs, ny, y_stride, n),
-                                     join_rows_span(V, batch, v_bs, 1, 0, n)))
+                                     rows_span(X, batch, x_bs, nx, x_stride, width), rows_span(Y, batch, y_bs, ny, y_stride, width),
+                                     rows_span(V, batch, v_bs, 1, 0, width)))
     return e;
   LwArgs p{};
   p.X = X, p.Y = Y, p.V = n > 0 ? V : nullptr, p.x_stride = x_stride, p.x_bs = x_bs, p.y_stride = y_stride, p.y_bs = y_bs, p.v_bs = v_bs;

@@ -183,17 +183,6 @@ __global__ __launch_bounds__(BATCH_WAVE_THREADS) void msb_block_kernel(word *__r
   if (row < m) *c = (r & mask) | (prev & ~mask);
 }
 
-// the path-1 bound of this call: `bound` (MSB_D1, or MSB_D1OP with a transposed operand) unless the environment overrides it (read
-// per call; [64, 256] in multiples of 64)
-int64_t path1_max(int64_t bound) {
-  const char *s = getenv("M4RI_AMD_MUL_SMALL_BATCH_PATH1_MAX");
-  if (!s || !*s) return bound;
-  int64_t v = atoll(s) / 64 * 64;
-  if (v < 64) v = 64;
-  if (v > 256) v = 256;
-  return v;
-}
-
 int plan(int64_t m, int64_t l, int64_t n, int64_t d1) {
   if (m < 0 || l < 0 || n < 0) return -1;
   const int64_t mx = m > l ? (m > n ? m : n) : (l > n ? l : n);
@@ -214,19 +203,18 @@ int mul_small_batch(word *C, int64_t c_stride, int64_t c_bs, const word *A, int6
                     int64_t b_bs, int64_t m, int64_t l, int64_t n, int64_t batch, bool ta, bool tb, int add, void *stream) {
   if (m < 0 || l < 0 || n < 0 || batch < 0 || c_stride < 0 || c_bs < 0 || a_stride < 0 || a_bs < 0 || b_stride < 0 || b_bs < 0)
     return (int)hipErrorInvalidValue;
-  const int64_t wn = words_of(n);
-  const int64_t a_rows = ta ? l : m, wa = words_of(ta ? m : l), b_rows = tb ? n : l, wb = words_of(tb ? l : n);  // as stored
+  const int64_t wn = width_of(n);
+  const int64_t a_rows = ta ? l : m, wa = width_of(ta ? m : l), b_rows = tb ? n : l, wb = width_of(tb ? l : n);  // as stored
   if (a_stride < wa || b_stride < wb || c_stride < wn) return (int)hipErrorInvalidValue;
-  if (batch > 1 && m > 0 && c_bs < (m - 1) * c_stride + wn) return (int)hipErrorInvalidValue;
+  if (!members_fit(batch, c_bs, m, c_stride, wn)) return (int)hipErrorInvalidValue;
   const bool c_data = m > 0 && n > 0, a_data = m > 0 && l > 0, b_data = l > 0 && n > 0;
   if (batch > 0 && ((c_data && !C) || (a_data && !A) || (b_data && !B))) return (int)hipErrorInvalidValue;
-  if (batch > 0 && c_data) {  // C's span (first member's start to last member's end) must not meet A's or B's
-    const uintptr_t cn = member_span_bytes(batch, c_bs, m, c_stride, wn);
-    if (a_data && spans_meet(C, cn, A, member_span_bytes(batch, a_bs, a_rows, a_stride, wa))) return (int)hipErrorInvalidValue;
-    if (b_data && spans_meet(C, cn, B, member_span_bytes(batch, b_bs, b_rows, b_stride, wb))) return (int)hipErrorInvalidValue;
-  }
+  // C's span (first member's start to last member's end) must not meet A's or B's
+  if (spans_meet_any({rows_span(C, batch, c_bs, m, c_stride, wn)}, {rows_span(A, batch, a_bs, a_rows, a_stride, wa), rows_span(B, batch, b_bs, b_rows, b_stride, wb)}))
+    return (int)hipErrorInvalidValue;
   if (batch == 0 || m == 0 || n == 0) return 0;
-  const int path = plan(m, l, n, path1_max(ta || tb ? MSB_D1OP : MSB_D1));
+  // the path-1 bound: MSB_D1, or MSB_D1OP with a transposed operand, unless the environment overrides it
+  const int path = plan(m, l, n, env_bound("M4RI_AMD_MUL_SMALL_BATCH_PATH1_MAX", ta || tb ? MSB_D1OP : MSB_D1, 64, 256, 64));
   if (path == 2) {
     if (ta || tb) return (int)hipErrorNotSupported;
     return m4ri_amd_m4rm_batch_dev(C, c_stride, c_bs, A, a_stride, a_bs, B, b_stride, b_bs, m, l, n, batch, add, stream);
@@ -235,9 +223,9 @@ int mul_small_batch(word *C, int64_t c_stride, int64_t c_bs, const word *A, int6
   const int64_t per = BATCH_WAVE_THREADS / 64;
   if (path == 0) {
     const WaveKernel kernel = WAVE_KERNELS[n > 32][ta][tb];
-    return launch_chunked(batch, BATCH_CHUNK * per, [&](int64_t b0, int64_t nb) {
-      hipLaunchKernelGGL(kernel, dim3((unsigned)((nb + per - 1) / per)), dim3(BATCH_WAVE_THREADS), 0, st, C, c_stride, c_bs, A, a_stride, a_bs, B, b_stride,
-                         b_bs, (int)m, (int)l, (int)n, b0, batch, add != 0);
+    return launch_waves(batch, [&](dim3 grid, int64_t b0, int64_t) {
+      hipLaunchKernelGGL(kernel, grid, dim3(BATCH_WAVE_THREADS), 0, st, C, c_stride, c_bs, A, a_stride, a_bs, B, b_stride, b_bs, (int)m, (int)l, (int)n, b0,
+                         batch, add != 0);
     });
   }
   const int64_t mb = (m + 63) / 64, blocks = mb * wn;       // waves per member: at most 16

@@ -19,7 +19,6 @@
 // by a request before it has passed the checks; entries of the order are only compared.
 #include <hip/hip_runtime.h>
 #include <cstdlib>
-#include <mutex>
 #include "batch_common.h"
 #include "../../include/m4ri_amd.h"
 
@@ -45,14 +44,6 @@ struct PxArgs {
   int64_t o_bs;
   int32_t *done;  // or nullptr
 };
-
-// output number k of the counter-form splitmix64 stream (m4ri_amd_fill_dev's, m4ri_amd_random_orders_batch_dev's)
-__device__ __forceinline__ uint64_t px_splitmix(uint64_t seed, uint64_t k) {
-  uint64_t z = seed + (k + 1) * 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
 
 __device__ __forceinline__ int px_rank(const PxArgs &p, int64_t b) {
   const int R = p.rank[b];
@@ -80,7 +71,7 @@ __global__ __launch_bounds__(BATCH_WAVE_THREADS) void px_wave_kernel(PxArgs p, i
       if (rq) {
         r = rq[2 * s], c = rq[2 * s + 1];
       } else {
-        const uint64_t h = px_splitmix(p.seed, (uint64_t)b * (uint64_t)p.steps + (uint64_t)s);
+        const uint64_t h = splitmix64(p.seed, (uint64_t)b * (uint64_t)p.steps + (uint64_t)s);
         r                = (int)((uint32_t)(h >> 32) % (uint32_t)R);
         const int start  = (int)((uint32_t)h % (uint32_t)p.ncols);
         word cand        = readlane64(v, r);
@@ -194,7 +185,7 @@ __global__ __launch_bounds__(BATCH_MAX_THREADS) void px_block_kernel(PxArgs p, i
     if (rq) {
       r = rq[2 * s], c = rq[2 * s + 1];
     } else {
-      const uint64_t h = px_splitmix(p.seed, (uint64_t)b * (uint64_t)p.steps + (uint64_t)s);
+      const uint64_t h = splitmix64(p.seed, (uint64_t)b * (uint64_t)p.steps + (uint64_t)s);
       r                = (int)((uint32_t)(h >> 32) % (uint32_t)R);
       c                = px_cyclic_scan(row(r), width, mask, pv[r], (int)((uint32_t)h % (uint32_t)p.ncols), lane);
     }
@@ -256,31 +247,9 @@ __global__ __launch_bounds__(BATCH_MAX_THREADS) void px_block_kernel(PxArgs p, i
   if (t == 0 && p.done) p.done[b] = cnt;
 }
 
-// LDS bytes of path 1 without the order
-int64_t lds_bytes_rows(int64_t nrows, int64_t width) {
-  return nrows * lds_row_words(width) * 8 + (int64_t)pad16((size_t)nrows * 4) + ((nrows + 63) / 64) * 8 + 8 * PX_WAVES;
-}
-
-// an environment bound of this call: `dflt` unless the variable is set; clamped to [0, hi]
-int64_t env_bound(const char *name, int64_t dflt, int64_t hi) {
-  const char *s = getenv(name);
-  if (!s || !*s) return dflt;
-  const int64_t v = atoll(s);
-  return v < 0 ? 0 : v > hi ? hi : v;
-}
-
-// words(ncols) for any ncols >= 0, INT64_MAX included (words_of adds 63 first)
-int64_t width_of(int64_t ncols) { return ncols / 64 + (ncols % 64 != 0); }
-
-// p0: the largest side of path 0; p1: the LDS bytes path 1 may use (the order counted at its longest, ncols entries); few: the step
-// counts sent in place although the member fits
+// path 1 stages one flag buffer and the slots; p0, p1: plan_on_order's; few: the step counts sent in place although the member fits
 int plan(int64_t nrows, int64_t ncols, int64_t steps, int64_t p0, int64_t p1, int64_t few) {
-  if (nrows < 0 || ncols < 0 || steps < 0) return -1;
-  if (nrows <= p0 && ncols <= p0) return 0;
-  const int64_t width = width_of(ncols), cap = BATCH_CAP_BYTES / 8;
-  if (nrows > cap || width > cap || nrows * width > cap) return 3;
-  if (steps > 0 && steps <= few) return 2;
-  return lds_bytes_rows(nrows, width) + 4 * ncols <= p1 ? 1 : 2;
+  return steps < 0 ? -1 : plan_on_order(nrows, ncols, p0, p1, 1, 8 * PX_WAVES, steps > 0 && steps <= few);
 }
 
 }  // namespace
@@ -302,27 +271,20 @@ int m4ri_amd_pivot_exchange_batch_dev(word *D, int64_t d_stride, int64_t d_bs, i
   // the cap next: below it a member's word counts are small
   // a caller who sets the LDS bound has chosen between paths 1 and 2: the step count no longer does
   const char *p1_set = getenv("M4RI_AMD_PIVOT_EXCHANGE_PATH1_MAX");
-  const int path     = plan(nrows, ncols, steps, env_bound("M4RI_AMD_PIVOT_EXCHANGE_PATH0_MAX", 64, 64),
-                            env_bound("M4RI_AMD_PIVOT_EXCHANGE_PATH1_MAX", BATCH_LDS_BUDGET, BATCH_LDS_BUDGET), p1_set && *p1_set ? 0 : PX_INPLACE_MAX_STEPS);
+  const int path     = plan(nrows, ncols, steps, env_bound("M4RI_AMD_PIVOT_EXCHANGE_PATH0_MAX", 64, 0, 64),
+                            env_bound("M4RI_AMD_PIVOT_EXCHANGE_PATH1_MAX", BATCH_LDS_BUDGET, 0, BATCH_LDS_BUDGET), p1_set && *p1_set ? 0 : PX_INPLACE_MAX_STEPS);
   if (path == 3) return (int)hipErrorNotSupported;
   const bool data = nrows > 0 && ncols > 0;
-  if (batch > 1 && data && d_bs < (nrows - 1) * d_stride + width) return (int)hipErrorInvalidValue;
+  if (data && !members_fit(batch, d_bs, nrows, d_stride, width)) return (int)hipErrorInvalidValue;
   if (batch > 1 && req && r_bs != 0 && r_bs / 2 < steps) return (int)hipErrorInvalidValue;  // r_bs < 2 * steps, for any steps
   if (batch > 1 && order && o_bs < olen) return (int)hipErrorInvalidValue;
   const int64_t pm = pivot_rows < ncols ? pivot_rows : ncols;
   if (batch > 0) {
     if (data && steps > 0 && (!D || !pivots || !rank)) return (int)hipErrorInvalidValue;
-    // the spans, bytes; an absent or empty operand meets nothing
-    const void *ptr[6]   = {D, pivots, rank, req, order, done};
-    const uintptr_t n[6] = {data ? member_span_bytes(batch, d_bs, nrows, d_stride, width) : 0,
-                            (uintptr_t)(batch * pm) * 4,
-                            (uintptr_t)batch * 4,
-                            steps > 0 ? (uintptr_t)(((r_bs ? batch - 1 : 0) * r_bs + 2 * steps) * 4) : 0,
-                            olen > 0 ? (uintptr_t)(((batch - 1) * o_bs + olen) * 4) : 0,
-                            (uintptr_t)batch * 4};
-    for (int x = 0; x < 6; ++x)
-      for (int y = x + 1; y < 6; ++y)
-        if (ptr[x] && ptr[y] && n[x] && n[y] && spans_meet(ptr[x], n[x], ptr[y], n[y])) return (int)hipErrorInvalidValue;
+    // every operand against every other
+    if (spans_meet_any({rows_span(D, batch, d_bs, nrows, d_stride, width), entries_span(pivots, batch, pm, pm, 4), entries_span(rank, batch, 1, 1, 4),
+                        entries_span(req, batch, r_bs, (wide)2 * steps, 4), entries_span(order, batch, o_bs, olen, 4), entries_span(done, batch, 1, 1, 4)}))
+      return (int)hipErrorInvalidValue;
   }
   if (batch == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
@@ -333,25 +295,18 @@ int m4ri_amd_pivot_exchange_batch_dev(word *D, int64_t d_stride, int64_t d_bs, i
   p.nrows = (int)nrows, p.ncols = (int)ncols, p.pm = (int)pm, p.steps = steps;
   p.pivots = pivots, p.rank = rank, p.req = req, p.r_bs = r_bs, p.seed = seed;
   p.order = olen > 0 ? order : nullptr, p.o_bs = o_bs, p.olen = (int)olen, p.done = done;
-  if (path == 0) {
-    const int64_t per = BATCH_WAVE_THREADS / 64;
-    return launch_chunked(batch, BATCH_CHUNK * per, [&](int64_t b0, int64_t nb) {
-      hipLaunchKernelGGL(px_wave_kernel, dim3((unsigned)((nb + per - 1) / per)), dim3(BATCH_WAVE_THREADS), 0, st, p, b0, b0 + nb);
+  if (path == 0)
+    return launch_waves(batch, [&](dim3 grid, int64_t b0, int64_t nb) {
+      hipLaunchKernelGGL(px_wave_kernel, grid, dim3(BATCH_WAVE_THREADS), 0, st, p, b0, b0 + nb);
     });
-  }
-  static std::once_flag once;
-  static hipError_t attr = hipSuccess;
-  std::call_once(once, [] {
-    attr = hipFuncSetAttribute(reinterpret_cast<const void *>(px_block_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)BATCH_LDS_BUDGET);
-  });
-  HIPTRY(attr);
+  HIPTRY(set_max_dynamic_lds(BATCH_LDS_BUDGET, px_block_kernel<true>));
   const bool inlds  = path == 1;
   const int threads = block_threads(nrows, width);
   const int ldw     = inlds ? (int)lds_row_words(width) : 0;
-  const size_t lds  = inlds ? (size_t)(lds_bytes_rows(nrows, width) + (p.order ? 4 * olen : 0)) : (size_t)(((nrows + 63) / 64) * 8 + 8 * PX_WAVES);
-  return launch_chunked(batch, BATCH_CHUNK, [&](int64_t b0, int64_t nb) {
-    if (inlds) hipLaunchKernelGGL(px_block_kernel<true>, dim3((unsigned)nb), dim3(threads), lds, st, p, ldw, b0);
-    else hipLaunchKernelGGL(px_block_kernel<false>, dim3((unsigned)nb), dim3(threads), lds, st, p, ldw, b0);
+  const size_t lds  = inlds ? (size_t)(lds_bytes_staged(nrows, width, 1, 8 * PX_WAVES) + (p.order ? 4 * olen : 0)) : (size_t)(((nrows + 63) / 64) * 8 + 8 * PX_WAVES);
+  return launch_members(batch, [&](dim3 grid, int64_t b0) {
+    if (inlds) hipLaunchKernelGGL(px_block_kernel<true>, grid, dim3(threads), lds, st, p, ldw, b0);
+    else hipLaunchKernelGGL(px_block_kernel<false>, grid, dim3(threads), lds, st, p, ldw, b0);
   });
 }
 

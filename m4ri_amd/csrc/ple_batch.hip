@@ -29,7 +29,6 @@
 //      global memory, a word per row once per 64 columns; one barrier per column of L and of U.
 //   2  larger members one by one through m4ri_amd_pluq_solve_left_dev on scratch copies.  Blocking.
 #include <hip/hip_runtime.h>
-#include <mutex>
 #include <vector>
 #include "batch_common.h"
 #include "../../include/m4ri_amd.h"
@@ -210,13 +209,13 @@ __global__ void pb_identity_kernel(int32_t *__restrict__ P, int64_t nrows, int32
 }
 
 int64_t lds_bytes_ple(int64_t nrows, int64_t ncols) {
-  return nrows * lds_row_words(words_of(ncols)) * 8 + 2 * (int64_t)pad16((size_t)nrows * 4) + (int64_t)pad16((size_t)ncols * 4) +
+  return nrows * lds_row_words(width_of(ncols)) * 8 + 2 * (int64_t)pad16((size_t)nrows * 4) + (int64_t)pad16((size_t)ncols * 4) +
          2 * ((nrows + 63) / 64) * 8;
 }
 
 int run_ple_path3(word *A, int64_t stride, int64_t a_bs, int64_t nrows, int64_t ncols, int64_t batch, int pluq, int32_t *P, int32_t *Q,
                   int32_t *rank, hipStream_t st) {
-  const int64_t width = words_of(ncols);
+  const int64_t width = width_of(ncols);
   std::vector<int32_t> hp((size_t)(batch * nrows)), hq((size_t)(batch * ncols)), hr((size_t)batch);
   word *s = nullptr;
   Scratch scratch(st);
@@ -400,14 +399,14 @@ __global__ __launch_bounds__(BATCH_MAX_THREADS) void ps_block_kernel(const word 
 
 int64_t lds_bytes_solve(int64_t m, int64_t n, int64_t k) {
   const int64_t R = m > n ? m : n, mn = m < n ? m : n;
-  return R * lds_row_words(words_of(k)) * 8 + (int64_t)pad16((size_t)R * 4) + (int64_t)pad16((size_t)mn * 4) + 16 + m * 8;
+  return R * lds_row_words(width_of(k)) * 8 + (int64_t)pad16((size_t)R * 4) + (int64_t)pad16((size_t)mn * 4) + 16 + m * 8;
 }
 
 // path 2: rank, P and Q to the host once; per member B's padding rows m .. R-1 checked, then m4ri_amd_pluq_solve_left_dev with the
 // check on clean copies of A_b (once when shared) and B_b, and X copied back only when it exists.  (R > 64 or k > 64 here, so k > 0.)
 int run_solve_path2(const word *A, int64_t a_stride, int64_t a_bs, int64_t m, int64_t n, const int32_t *rank, const int32_t *P, const int32_t *Q,
                     word *B, int64_t b_stride, int64_t b_bs, int64_t k, int64_t batch, int32_t *status, hipStream_t st) {
-  const int64_t R = m > n ? m : n, mn = m < n ? m : n, wa = words_of(n), wb = words_of(k), nf = a_bs ? batch : 1;
+  const int64_t R = m > n ? m : n, mn = m < n ? m : n, wa = width_of(n), wb = width_of(k), nf = a_bs ? batch : 1;
   std::vector<int32_t> hs((size_t)batch), hr((size_t)nf), hp((size_t)(nf * m)), hq((size_t)(nf * n));
   word *sA = nullptr, *sB = nullptr;
   Scratch scratch(st);
@@ -445,7 +444,7 @@ extern "C" {
 int m4ri_amd_plan_ple_batch(int64_t nrows, int64_t ncols) {
   if (nrows < 0 || ncols < 0) return -1;
   if (nrows <= 64 && ncols <= 64) return 0;
-  const int64_t width = words_of(ncols);
+  const int64_t width = width_of(ncols);
   if (nrows > BATCH_CAP_BYTES / 8 || width > BATCH_CAP_BYTES / 8 || nrows * width > BATCH_CAP_BYTES / 8) return 3;
   return lds_bytes_ple(nrows, ncols) <= BATCH_LDS_BUDGET ? 1 : 2;
 }
@@ -453,9 +452,9 @@ int m4ri_amd_plan_ple_batch(int64_t nrows, int64_t ncols) {
 int m4ri_amd_ple_batch_dev(word *A, int64_t stride, int64_t a_bs, int64_t nrows, int64_t ncols, int64_t batch, int pluq, int32_t *P, int32_t *Q,
                            int32_t *rank, void *stream) {
   if (nrows < 0 || ncols < 0 || batch < 0 || stride < 0 || a_bs < 0) return (int)hipErrorInvalidValue;
-  const int64_t width = words_of(ncols);
+  const int64_t width = width_of(ncols);
   if (stride < width) return (int)hipErrorInvalidValue;
-  if (batch > 1 && nrows > 0 && a_bs < (nrows - 1) * stride + width) return (int)hipErrorInvalidValue;
+  if (!members_fit(batch, a_bs, nrows, stride, width)) return (int)hipErrorInvalidValue;
   if (batch > 0 && (!rank || (nrows > 0 && !P) || (ncols > 0 && !Q))) return (int)hipErrorInvalidValue;
   if (batch > 0 && nrows > 0 && ncols > 0 && !A) return (int)hipErrorInvalidValue;
   if (batch == 0) return 0;
@@ -466,30 +465,19 @@ int m4ri_amd_ple_batch_dev(word *A, int64_t stride, int64_t a_bs, int64_t nrows,
     return (int)hipGetLastError();
   }
   const int path = m4ri_amd_plan_ple_batch(nrows, ncols);
-  if (path == 0) {
-    const int64_t per = BATCH_WAVE_THREADS / 64;
-    return launch_chunked(batch, BATCH_CHUNK * per, [&](int64_t b0, int64_t n) {
-      hipLaunchKernelGGL(pb_wave_kernel, dim3((unsigned)((n + per - 1) / per)), dim3(BATCH_WAVE_THREADS), 0, st, A, stride, a_bs, (int)nrows, (int)ncols,
-                         b0, batch, pluq, P, Q, rank);
+  if (path == 0)
+    return launch_waves(batch, [&](dim3 grid, int64_t b0, int64_t) {
+      hipLaunchKernelGGL(pb_wave_kernel, grid, dim3(BATCH_WAVE_THREADS), 0, st, A, stride, a_bs, (int)nrows, (int)ncols, b0, batch, pluq, P, Q, rank);
     });
-  }
   if (path == 3) return run_ple_path3(A, stride, a_bs, nrows, ncols, batch, pluq, P, Q, rank, st);
   const bool inlds  = path == 1;
   const int threads = block_threads(nrows, width);
   const int ldw     = inlds ? (int)lds_row_words(width) : 0;
   const size_t lds  = inlds ? (size_t)lds_bytes_ple(nrows, ncols) : (size_t)(2 * ((nrows + 63) / 64) * 8);
-  static std::once_flag once;
-  std::call_once(once, [] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(pb_block_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)BATCH_LDS_BUDGET);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(pb_block_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)BATCH_LDS_BUDGET);
-  });
-  return launch_chunked(batch, BATCH_CHUNK, [&](int64_t b0, int64_t n) {
-    if (inlds)
-      hipLaunchKernelGGL(pb_block_kernel<true>, dim3((unsigned)n), dim3(threads), lds, st, A, stride, a_bs, (int)nrows, (int)ncols, ldw, b0, pluq, P, Q,
-                         rank);
-    else
-      hipLaunchKernelGGL(pb_block_kernel<false>, dim3((unsigned)n), dim3(threads), lds, st, A, stride, a_bs, (int)nrows, (int)ncols, ldw, b0, pluq, P, Q,
-                         rank);
+  HIPTRY(set_max_dynamic_lds(BATCH_LDS_BUDGET, pb_block_kernel<true>, pb_block_kernel<false>));
+  return launch_members(batch, [&](dim3 grid, int64_t b0) {
+    if (inlds) hipLaunchKernelGGL(pb_block_kernel<true>, grid, dim3(threads), lds, st, A, stride, a_bs, (int)nrows, (int)ncols, ldw, b0, pluq, P, Q, rank);
+    else hipLaunchKernelGGL(pb_block_kernel<false>, grid, dim3(threads), lds, st, A, stride, a_bs, (int)nrows, (int)ncols, ldw, b0, pluq, P, Q, rank);
   });
 }
 
@@ -497,7 +485,7 @@ int m4ri_amd_plan_pluq_solve_batch(int64_t m, int64_t n, int64_t k) {
   if (m < 0 || n < 0 || k < 0) return -1;
   const int64_t R = m > n ? m : n;
   if (R <= 64 && k <= 64) return 0;
-  if (R > BATCH_LDS_BUDGET / 8 || words_of(k) > BATCH_LDS_BUDGET / 8) return 2;
+  if (R > BATCH_LDS_BUDGET / 8 || width_of(k) > BATCH_LDS_BUDGET / 8) return 2;
   return lds_bytes_solve(m, n, k) <= BATCH_LDS_BUDGET ? 1 : 2;
 }
 
@@ -505,36 +493,29 @@ int m4ri_amd_pluq_solve_left_batch_dev(const word *A, int64_t a_stride, int64_t 
                                        const int32_t *Q, word *B, int64_t b_stride, int64_t b_bs, int64_t k, int64_t batch, int32_t *status,
                                        void *stream) {
   if (m < 0 || n < 0 || k < 0 || batch < 0 || a_stride < 0 || a_bs < 0 || b_stride < 0 || b_bs < 0) return (int)hipErrorInvalidValue;
-  const int64_t R = m > n ? m : n, wa = words_of(n), wb = words_of(k);
+  const int64_t R = m > n ? m : n, wa = width_of(n), wb = width_of(k);
   if (a_stride < wa || b_stride < wb) return (int)hipErrorInvalidValue;
-  if (batch > 1 && R > 0 && b_bs < (R - 1) * b_stride + wb) return (int)hipErrorInvalidValue;
+  if (!members_fit(batch, b_bs, R, b_stride, wb)) return (int)hipErrorInvalidValue;
   if (batch > 0 && (!status || !rank || (m > 0 && !P) || (n > 0 && !Q))) return (int)hipErrorInvalidValue;
   const bool a_data = m > 0 && n > 0, b_data = R > 0 && k > 0;
   if (batch > 0 && ((a_data && !A) || (b_data && !B))) return (int)hipErrorInvalidValue;
   // B's span and A's span (first member's start to last member's end) must not meet
-  if (batch > 0 && a_data && b_data &&
-      spans_meet(B, member_span_bytes(batch, b_bs, R, b_stride, wb), A, member_span_bytes(batch, a_bs, m, a_stride, wa)))
-    return (int)hipErrorInvalidValue;
+  if (spans_meet(rows_span(B, batch, b_bs, R, b_stride, wb), rows_span(A, batch, a_bs, m, a_stride, wa))) return (int)hipErrorInvalidValue;
   if (batch == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
   if (k == 0) return (int)hipMemsetAsync(status, 0, (size_t)batch * 4, st);  // no right-hand side: nothing to contradict
   const int path = m4ri_amd_plan_pluq_solve_batch(m, n, k);
   if (path == 2) return run_solve_path2(A, a_stride, a_bs, m, n, rank, P, Q, B, b_stride, b_bs, k, batch, status, st);
-  if (path == 0) {
-    const int64_t per = BATCH_WAVE_THREADS / 64;
-    return launch_chunked(batch, BATCH_CHUNK * per, [&](int64_t b0, int64_t cnt) {
-      hipLaunchKernelGGL(ps_wave_kernel, dim3((unsigned)((cnt + per - 1) / per)), dim3(BATCH_WAVE_THREADS), 0, st, A, a_stride, a_bs, (int)m, (int)n, rank,
-                         P, Q, B, b_stride, b_bs, (int)k, b0, batch, status);
+  if (path == 0)
+    return launch_waves(batch, [&](dim3 grid, int64_t b0, int64_t) {
+      hipLaunchKernelGGL(ps_wave_kernel, grid, dim3(BATCH_WAVE_THREADS), 0, st, A, a_stride, a_bs, (int)m, (int)n, rank, P, Q, B, b_stride, b_bs, (int)k, b0,
+                         batch, status);
     });
-  }
-  static std::once_flag once;
-  std::call_once(once, [] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(ps_block_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)BATCH_LDS_BUDGET);
-  });
+  HIPTRY(set_max_dynamic_lds(BATCH_LDS_BUDGET, ps_block_kernel));
   const int threads = block_threads(R, wb);
   const size_t lds  = (size_t)lds_bytes_solve(m, n, k);
-  return launch_chunked(batch, BATCH_CHUNK, [&](int64_t b0, int64_t cnt) {
-    hipLaunchKernelGGL(ps_block_kernel, dim3((unsigned)cnt), dim3(threads), lds, st, A, a_stride, a_bs, (int)m, (int)n, rank, P, Q, B, b_stride, b_bs,
+  return launch_members(batch, [&](dim3 grid, int64_t b0) {
+    hipLaunchKernelGGL(ps_block_kernel, grid, dim3(threads), lds, st, A, a_stride, a_bs, (int)m, (int)n, rank, P, Q, B, b_stride, b_bs,
                        (int)k, (int)lds_row_words(wb), b0, status);
   });
 }

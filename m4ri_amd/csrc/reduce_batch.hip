@@ -19,7 +19,6 @@
 // no allocation, no copy to the host, no synchronisation, no engine workspace or lock.
 #include <hip/hip_runtime.h>
 #include <limits.h>
-#include <stdlib.h>
 #include "batch_common.h"
 #include "../../include/m4ri_amd.h"
 
@@ -222,17 +221,9 @@ int launch_init(hipStream_t st, const RedArgs &p, int64_t lightest_v, int64_t ba
   return 0;
 }
 
-// an environment bound of this call: `dflt` unless the variable is set; clamped to [0, hi]
-int64_t env_bound(const char *name, int64_t dflt, int64_t hi) {
-  const char *s = getenv(name);
-  if (!s || !*s) return dflt;
-  const int64_t v = atoll(s);
-  return v < 0 ? 0 : v > hi ? hi : v;
-}
-
 int plan(int64_t nrows, int64_t ncols, int64_t w0, int64_t t1) {
   if (nrows < 0 || ncols < 0) return -1;
-  const int64_t width = words_of(ncols);
+  const int64_t width = width_of(ncols);
   if (nrows == 0 || width == 0) return 0;
   if (nrows <= 64 && width <= w0) return 0;
   return nrows <= t1 / width ? 1 : 2;  // nrows * width <= t1, without the product
@@ -240,42 +231,34 @@ int plan(int64_t nrows, int64_t ncols, int64_t w0, int64_t t1) {
 
 bool aligned16(const word *p, int64_t stride, int64_t bs) { return ((uintptr_t)p & 15) == 0 && !(stride & 1) && !(bs & 1); }
 
-// does the output of `bytes` bytes at `out` meet an operand of the call?
-bool meets(const void *out, uintptr_t bytes, const RedArgs &p, int64_t batch) {
-  if (!out || !bytes) return false;
-  if (p.A && spans_meet(out, bytes, p.A, member_span_bytes(batch, p.a_bs, p.nrows, p.a_stride, p.width))) return true;
-  return p.B && spans_meet(out, bytes, p.B, member_span_bytes(batch, p.b_bs, p.nrows, p.b_stride, p.width));
-}
-
 // The one call behind the three entry points.  need_b: B is an operand that must be there (the mismatch); the outputs not of the
 // entry point are NULL in p.
 int reduce_batch(RedArgs p, int64_t ncols, int64_t batch, bool need_b, hipStream_t st) {
   if (p.nrows < 0 || ncols < 0 || batch < 0 || p.a_stride < 0 || p.a_bs < 0 || p.b_stride < 0 || p.b_bs < 0) return (int)hipErrorInvalidValue;
   if (p.nrows > INT32_MAX || ncols > INT32_MAX) return (int)hipErrorInvalidValue;  // a row index, a row weight: 32 bits
   if (!p.total && !p.row_weight && !p.lightest && !p.first && !p.end) return (int)hipErrorInvalidValue;
-  p.width         = words_of(ncols);
+  p.width         = width_of(ncols);
   p.mask          = tail_mask((int)(ncols & 63));
   const bool data = p.nrows > 0 && ncols > 0;
   const bool hasb = need_b || p.B;
   if (data && (p.a_stride < p.width || (hasb && p.b_stride < p.width))) return (int)hipErrorInvalidValue;
   if (batch > 0 && data && (!p.A || (need_b && !p.B))) return (int)hipErrorInvalidValue;
-  if (batch > 0 && data &&
-      (meets(p.total, (uintptr_t)batch * 8, p, batch) || meets(p.row_weight, (uintptr_t)(batch * p.nrows) * 4, p, batch) ||
-       meets(p.lightest, (uintptr_t)batch * 8, p, batch) || meets(p.first, (uintptr_t)batch * 4, p, batch) || meets(p.end, (uintptr_t)batch * 4, p, batch)))
-    return (int)hipErrorInvalidValue;
+  const Span a = rows_span(p.A, batch, p.a_bs, p.nrows, p.a_stride, p.width), b = rows_span(p.B, batch, p.b_bs, p.nrows, p.b_stride, p.width);
+  for (const Span &out : {entries_span(p.total, batch, 1, 1, 8), entries_span(p.row_weight, batch, p.nrows, p.nrows, 4), entries_span(p.lightest, batch, 1, 1, 8),
+                          entries_span(p.first, batch, 1, 1, 4), entries_span(p.end, batch, 1, 1, 4)})  // each output against the operands, not each other
+    if (spans_meet_any({out}, {a, b})) return (int)hipErrorInvalidValue;
   if (batch == 0) return 0;
   if (!data) {  // empty members: weights 0, no lightest row without rows, no non-zero row
     if (p.row_weight && p.nrows > 0) HIPTRY(hipMemsetAsync(p.row_weight, 0, (size_t)(batch * p.nrows) * 4, st));
     if (p.total || p.lightest || p.first || p.end) return launch_init(st, p, p.nrows == 0 ? -1 : 0, batch);
     return 0;
   }
-  const int path = plan(p.nrows, ncols, env_bound("M4RI_AMD_REDUCE_BATCH_PATH0_MAX", RDB_W0, RDB_W0_MAX),
-                        env_bound("M4RI_AMD_REDUCE_BATCH_PATH1_MAX", RDB_T1, RDB_T1_MAX));
+  const int path = plan(p.nrows, ncols, env_bound("M4RI_AMD_REDUCE_BATCH_PATH0_MAX", RDB_W0, 0, RDB_W0_MAX),
+                        env_bound("M4RI_AMD_REDUCE_BATCH_PATH1_MAX", RDB_T1, 0, RDB_T1_MAX));
   const bool vec = aligned16(p.A, p.a_stride, p.a_bs) && (!p.B || aligned16(p.B, p.b_stride, p.b_bs));
   if (path == 0) {
-    return launch_chunked(batch, BATCH_CHUNK * RDB_WAVES, [&](int64_t b0, int64_t nb) {
+    return launch_waves(batch, [&](dim3 grid, int64_t b0, int64_t nb) {
       p.b0 = b0, p.batch = b0 + nb;
-      const dim3 grid((unsigned)((nb + RDB_WAVES - 1) / RDB_WAVES));
       if (vec) hipLaunchKernelGGL(red_wave_kernel<true>, grid, dim3(BATCH_WAVE_THREADS), 0, st, p);
       else hipLaunchKernelGGL(red_wave_kernel<false>, grid, dim3(BATCH_WAVE_THREADS), 0, st, p);
     });

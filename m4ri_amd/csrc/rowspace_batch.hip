@@ -26,7 +26,6 @@
 // Plain launches on the caller's stream: no allocation, no copy to the host, no synchronisation, no engine workspace or lock.
 #include <hip/hip_runtime.h>
 #include <limits.h>
-#include <stdlib.h>
 #include "batch_common.h"
 #include "../../include/m4ri_amd.h"
 
@@ -202,14 +201,6 @@ void launch_wt(const RswArgs &p, dim3 grid, size_t lds, hipStream_t st) {
   else hipLaunchKernelGGL((rsw_kernel<WT, false, true>), grid, dim3(BATCH_WAVE_THREADS), lds, st, p);
 }
 
-// the path-0 bound of this call: RSW_K0 unless the variable is set; clamped to [-1, RSW_K0_MAX], -1 = no path 0
-int64_t env_k0() {
-  const char *s = getenv("M4RI_AMD_ROWSPACE_PATH0_MAX");
-  if (!s || !*s) return RSW_K0;
-  const int64_t v = atoll(s);
-  return v < -1 ? -1 : v > RSW_K0_MAX ? RSW_K0_MAX : v;
-}
-
 int plan(int64_t k, int64_t n, int64_t k0) {
   if (k < 0 || n < 0) return -1;
   return n == 0 || k <= k0 ? 0 : 1;
@@ -227,20 +218,14 @@ int m4ri_amd_rowspace_weights_batch_dev(const word *G, int64_t g_stride, int64_t
   if (k < 0 || n < 0 || batch < 0 || g_stride < 0 || g_bs < 0 || v_bs < 0 || w_min < 0) return (int)hipErrorInvalidValue;
   if (k > RSW_K_MAX || n > RSW_N_MAX) return (int)hipErrorNotSupported;
   if (!hist && !lightest) return (int)hipErrorInvalidValue;
-  const int64_t width = words_of(n);
+  const int64_t width = width_of(n);
   const bool data     = k > 0 && n > 0;  // G has words
   if (n > 0 && k > 1 && g_stride < width) return (int)hipErrorInvalidValue;
   if (batch > 0) {
     if (data && !G) return (int)hipErrorInvalidValue;
-    const uintptr_t hist_bytes = (uintptr_t)(batch * (n + 1)) * 8, light_bytes = (uintptr_t)batch * 8;
-    if (hist && lightest && spans_meet(hist, hist_bytes, lightest, light_bytes)) return (int)hipErrorInvalidValue;
-    for (int o = 0; o < 2; ++o) {
-      const void *out       = o ? (const void *)lightest : (const void *)hist;
-      const uintptr_t bytes = o ? light_bytes : hist_bytes;
-      if (!out) continue;
-      if (data && spans_meet(out, bytes, G, member_span_bytes(batch, g_bs, k, g_stride, width))) return (int)hipErrorInvalidValue;
-      if (V && n > 0 && spans_meet(out, bytes, V, member_span_bytes(batch, v_bs, 1, 0, width))) return (int)hipErrorInvalidValue;
-    }
+    if (spans_meet_any({entries_span(hist, batch, n + 1, n + 1, 8), entries_span(lightest, batch, 1, 1, 8)},
+                       {rows_span(G, batch, g_bs, k, g_stride, width), rows_span(V, batch, v_bs, 1, 0, width)}))
+      return (int)hipErrorInvalidValue;
   }
   if (batch == 0) return 0;
   if (n == 0)  // every word weighs 0: all 2^k messages in the one bin, the lightest is message 0 if weight 0 qualifies
@@ -248,7 +233,7 @@ int m4ri_amd_rowspace_weights_batch_dev(const word *G, int64_t g_stride, int64_t
   RswArgs p{};
   p.G = G, p.V = V, p.g_stride = g_stride, p.g_bs = g_bs, p.v_bs = v_bs, p.k = (int)k, p.n = (int)n, p.width = (int)width;
   p.mask = tail_mask((int)(n & 63)), p.w_min = (int)(w_min > n + 1 ? n + 1 : w_min), p.hist = hist, p.lightest = lightest;
-  p.atomic = plan(k, n, env_k0());
+  p.atomic = plan(k, n, env_bound("M4RI_AMD_ROWSPACE_PATH0_MAX", RSW_K0, -1, RSW_K0_MAX));  // -1: no path 0
   if (!p.atomic || k < 2 * RSW_S1_MIN) p.s = k > 6 ? (int)k - 6 : 0;
   else p.s = k - RSW_S1_OFF < RSW_S1_MIN ? RSW_S1_MIN : k - RSW_S1_OFF > RSW_S1_MAX ? RSW_S1_MAX : (int)k - RSW_S1_OFF;
   p.wshift = k - p.s > 6 ? (int)k - p.s - 6 : 0;
@@ -262,9 +247,8 @@ int m4ri_amd_rowspace_weights_batch_dev(const word *G, int64_t g_stride, int64_t
   const size_t lds = (size_t)RSW_WAVES * ((size_t)p.row_words * 8 + (size_t)p.bin_words * 4);
   if (p.atomic) HIPTRY(launch_init(st, hist, batch * (n + 1), 0, lightest, batch, -1));
   p.units = batch << p.wshift;
-  return launch_chunked(p.units, BATCH_CHUNK * RSW_WAVES, [&](int64_t u0, int64_t nu) {
+  return launch_waves(p.units, [&](dim3 grid, int64_t u0, int64_t) {
     p.u0 = u0;
-    const dim3 grid((unsigned)((nu + RSW_WAVES - 1) / RSW_WAVES));
     switch (wt) {
       case 1: launch_wt<1>(p, grid, lds, st); break;
       case 2: launch_wt<2>(p, grid, lds, st); break;

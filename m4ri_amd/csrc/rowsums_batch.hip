@@ -33,7 +33,6 @@
 // Plain launches on the caller's stream: no allocation, no copy to the host, no synchronisation, no engine workspace or lock.
 #include <hip/hip_runtime.h>
 #include <limits.h>
-#include <stdlib.h>
 #include "batch_common.h"
 #include "subset_rank.h"  // the limits RS_*_MAX, binom_capped, binom_elem, unrank_step
 #include "../../include/m4ri_amd.h"
@@ -265,14 +264,6 @@ void launch_wt(const RsArgs &p, dim3 grid, size_t lds, hipStream_t st) {
   else hipLaunchKernelGGL((rs_kernel<WT, false, true>), grid, dim3(BATCH_WAVE_THREADS), lds, st, p);
 }
 
-// the path-0 bound of this call: RS_M0 unless the variable is set; clamped to [-1, RS_M0_MAX], -1 = no path 0
-int64_t env_m0() {
-  const char *s = getenv("M4RI_AMD_ROW_SUMS_PATH0_MAX");
-  if (!s || !*s) return RS_M0;
-  const int64_t v = atoll(s);
-  return v < -1 ? -1 : v > RS_M0_MAX ? RS_M0_MAX : v;
-}
-
 int plan(int64_t k, int64_t n, int64_t t, int64_t m0) {
   if (k < 0 || n < 0 || t < 0) return -1;
   if (n == 0 || t == 0 || k < t) return 0;  // the initialisation kernel alone
@@ -293,21 +284,14 @@ int m4ri_amd_row_sums_weights_batch_dev(const word *G, int64_t g_stride, int64_t
   const int64_t sums = binom_capped(k, t);
   if (sums > RS_SUMS_MAX) return (int)hipErrorNotSupported;
   if (!hist && !lightest) return (int)hipErrorInvalidValue;
-  const int64_t width = words_of(n);
-  const bool words    = k > 0 && n > 0;             // G has words
+  const int64_t width = width_of(n);
   const bool walked   = k >= t && t >= 1 && n > 0;  // and they are read
   if (n > 0 && k > 1 && g_stride < width) return (int)hipErrorInvalidValue;
   if (batch > 0) {
     if (walked && !G) return (int)hipErrorInvalidValue;
-    const uintptr_t hist_bytes = (uintptr_t)(batch * (n + 1)) * 8, light_bytes = (uintptr_t)batch * 8;
-    if (hist && lightest && spans_meet(hist, hist_bytes, lightest, light_bytes)) return (int)hipErrorInvalidValue;
-    for (int o = 0; o < 2; ++o) {
-      const void *out       = o ? (const void *)lightest : (const void *)hist;
-      const uintptr_t bytes = o ? light_bytes : hist_bytes;
-      if (!out) continue;
-      if (words && G && spans_meet(out, bytes, G, member_span_bytes(batch, g_bs, k, g_stride, width))) return (int)hipErrorInvalidValue;
-      if (V && n > 0 && spans_meet(out, bytes, V, member_span_bytes(batch, v_bs, 1, 0, width))) return (int)hipErrorInvalidValue;
-    }
+    if (spans_meet_any({entries_span(hist, batch, n + 1, n + 1, 8), entries_span(lightest, batch, 1, 1, 8)},
+                       {rows_span(G, batch, g_bs, k, g_stride, width), rows_span(V, batch, v_bs, 1, 0, width)}))  // G where it has words, read or not
+      return (int)hipErrorInvalidValue;
   }
   if (batch == 0) return 0;
   RsInit in{};
@@ -324,7 +308,7 @@ int m4ri_amd_row_sums_weights_batch_dev(const word *G, int64_t g_stride, int64_t
   RsArgs p{};
   p.G = G, p.V = V, p.g_stride = g_stride, p.g_bs = g_bs, p.v_bs = v_bs, p.k = (int)k, p.t = (int)t, p.n = (int)n, p.width = (int)width;
   p.mask = mask, p.w_min = (int)(w_min > n + 1 ? n + 1 : w_min), p.hist = hist, p.lightest = lightest;
-  p.atomic = plan(k, n, t, env_m0());
+  p.atomic = plan(k, n, t, env_bound("M4RI_AMD_ROW_SUMS_PATH0_MAX", RS_M0, -1, RS_M0_MAX));  // -1: no path 0
   int wt   = 1;
   while (wt < width) wt *= 2;
   p.seg_rows = (p.atomic ? RS_WAVES : 1) * RS_ROW_WORDS / wt;

@@ -42,7 +42,6 @@
 // side of the launch are join_common.h's, shared with lists_collide_batch.hip.  What is here: the row keys, the keys of the sets, the
 // word and the rank of a match, the slices, and the routing.
 #include <hip/hip_runtime.h>
-#include <stdlib.h>
 #include "join_common.h"
 #include "subset_rank.h"
 #include "../../include/m4ri_amd.h"
@@ -184,14 +183,6 @@ __global__ __launch_bounds__(JOIN_THREADS_MAX) void rc_kernel(RcArgs p) {
   join_output<HIST, LIGHT, LIST>(o, L, b, best, tid, T);
 }
 
-// the path-0 bound of this call: RC_P0 unless the variable is set; clamped to [-1, JOIN_PAIRS_WG], -1 = no path 0
-int64_t env_p0() {
-  const char *s = getenv("M4RI_AMD_ROW_SUMS_COLLIDE_PATH0_MAX");
-  if (!s || !*s) return RC_P0;
-  const int64_t v = atoll(s);
-  return v < -1 ? -1 : v > JOIN_PAIRS_WG ? JOIN_PAIRS_WG : v;
-}
-
 bool sizes_negative(int64_t k, int64_t n, int64_t k1, int64_t t1, int64_t t2, int64_t ell) {
   return k < 0 || n < 0 || k1 < 0 || k1 > k || t1 < 0 || t2 < 0 || ell < 0;
 }
@@ -228,13 +219,13 @@ int collide(const word *G, int64_t g_stride, int64_t g_bs, int64_t k, int64_t n,
   const int64_t pairs = n1 * n2;  // at most 2^13 * 2^41
   if (pairs > RS_SUMS_MAX) return (int)hipErrorNotSupported;
   if (const int e = join_check_outputs(cols, ell, n, hist, lightest, list, l_bs, cap, count, batch)) return e;
-  const int64_t width = words_of(n);
+  const int64_t width = width_of(n);
   const bool walked   = pairs > 0 && n > 0 && t1 + t2 >= 1;  // G's words are read
   if (n > 0 && k > 1 && g_stride < width) return (int)hipErrorInvalidValue;
   if (batch > 0) {
     if (walked && !G) return (int)hipErrorInvalidValue;
-    if (join_outputs_meet(hist, lightest, list, l_bs, cap, count, batch, n, cols, c_bs, ell, join_rows_span(G, batch, g_bs, k, g_stride, n),
-                          join_rows_span(V, batch, v_bs, 1, 0, n)))
+    if (join_outputs_meet(hist, lightest, list, l_bs, cap, count, batch, n, cols, c_bs, ell, rows_span(G, batch, g_bs, k, g_stride, width),
+                          rows_span(V, batch, v_bs, 1, 0, width)))
       return (int)hipErrorInvalidValue;
   }
   if (batch == 0) return 0;
@@ -247,7 +238,7 @@ int collide(const word *G, int64_t g_stride, int64_t g_bs, int64_t k, int64_t n,
   p.hist = hist, p.lightest = lightest;
   p.w_max = join_w_max(w_max, n), p.list = list, p.count = count, p.l_bs = l_bs, p.cap = cap;
   p.q         = join_bucket_bits(ell, n1);
-  p.atomic    = plan(k, n, k1, t1, t2, ell, env_p0());
+  p.atomic    = plan(k, n, k1, t1, t2, ell, env_bound("M4RI_AMD_ROW_SUMS_COLLIDE_PATH0_MAX", RC_P0, -1, JOIN_PAIRS_WG));  // -1: no path 0
   p.slice_len = p.atomic ? slice_len(n1, n2, batch) : n2;
   p.slices    = (n2 + p.slice_len - 1) / p.slice_len;
   return join_launch(rc_kernels, RC_LDS_MAX, st, in, batch, p, batch * p.slices, join_threads(n1, 1024, p.slice_len),

@@ -65,11 +65,11 @@ int m4ri_amd_row_sums_words_batch_dev(const word *G, int64_t g_stride, int64_t g
   const int64_t n1 = binom_capped(k1, t1), n2 = binom_capped(k - k1, t2);
   const __int128 pairs = (__int128)n1 * n2;
   if (pairs > RS_SUMS_MAX) return (int)hipErrorNotSupported;
-  const int64_t width = words_of(n);
+  const int64_t width = width_of(n);
   if (n > 0 && k > 1 && g_stride < width) return (int)hipErrorInvalidValue;
   const bool read = pairs > 0 && n > 0 && t1 + t2 >= 1;  // rows of G are read
-  if (const int e = join_words_check(n, batch, keys, l_bs, cap, count, W, w_stride, w_bs, skipped, read && !G, join_rows_span(G, batch, g_bs, k, g_stride, n),
-                                     join_rows_span(V, batch, v_bs, 1, 0, n)))
+  if (const int e = join_words_check(n, batch, keys, l_bs, cap, count, W, w_stride, w_bs, skipped, read && !G, rows_span(G, batch, g_bs, k, g_stride, width),
+                                     rows_span(V, batch, v_bs, 1, 0, width)))
     return e;
   RwArgs p{};
   p.G = G, p.V = n > 0 ? V : nullptr, p.g_stride = g_stride, p.g_bs = g_bs, p.v_bs = v_bs;

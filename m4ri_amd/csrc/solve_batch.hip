@@ -27,7 +27,6 @@
 // the basis, the words from the width to the stride of a row and anything between members are never written.  An inconsistent
 // member's B is not written at all.
 #include <hip/hip_runtime.h>
-#include <mutex>
 #include <vector>
 #include "batch_common.h"
 #include "../../include/m4ri_amd.h"
@@ -302,28 +301,23 @@ int64_t lds_bytes_path1(int64_t R, int64_t W, int64_t n, int64_t tab) {
 }
 
 // the kernel's path 1: m rows of words(n), the swap rule's arrangement and the index table (n entries each)
-int64_t lds_bytes_kernel(int64_t m, int64_t n) { return lds_bytes_path1(m, words_of(n), n, 2 * n); }
+int64_t lds_bytes_kernel(int64_t m, int64_t n) { return lds_bytes_path1(m, width_of(n), n, 2 * n); }
 
 template <int OP>
 int launch(const word *A, int64_t a_stride, int64_t a_bs, word *B, int64_t b_stride, int64_t b_bs, int64_t m, int64_t n, int64_t k,
            int64_t batch, int path, int32_t *status, int32_t *rank, hipStream_t st) {
-  if (path == 0) {
-    const int64_t per = BATCH_WAVE_THREADS / 64;
-    return launch_chunked(batch, BATCH_CHUNK * per, [&](int64_t b0, int64_t cnt) {
-      hipLaunchKernelGGL(sb_wave_kernel<OP>, dim3((unsigned)((cnt + per - 1) / per)), dim3(BATCH_WAVE_THREADS), 0, st, A, a_stride, a_bs, B, b_stride,
-                         b_bs, (int)m, (int)n, (int)k, b0, batch, status, rank);
+  if (path == 0)
+    return launch_waves(batch, [&](dim3 grid, int64_t b0, int64_t) {
+      hipLaunchKernelGGL(sb_wave_kernel<OP>, grid, dim3(BATCH_WAVE_THREADS), 0, st, A, a_stride, a_bs, B, b_stride, b_bs, (int)m, (int)n, (int)k, b0, batch,
+                         status, rank);
     });
-  }
-  static std::once_flag once;
-  std::call_once(once, [] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(sb_block_kernel<OP>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)BATCH_LDS_BUDGET);
-  });
+  HIPTRY(set_max_dynamic_lds<OP>(BATCH_LDS_BUDGET, sb_block_kernel<OP>));  // the three OPs' kernels have one type
   const bool ker    = OP == SB_KER;
-  const int64_t R   = (ker || m > n) ? m : n, W = words_of(n) + (ker ? 0 : words_of(k));
+  const int64_t R   = (ker || m > n) ? m : n, W = width_of(n) + (ker ? 0 : width_of(k));
   const int threads = block_threads(R, W);
   const size_t lds  = (size_t)(ker ? lds_bytes_kernel(m, n) : lds_bytes_path1(R, W, n, 0));
-  return launch_chunked(batch, BATCH_CHUNK, [&](int64_t b0, int64_t cnt) {
-    hipLaunchKernelGGL(sb_block_kernel<OP>, dim3((unsigned)cnt), dim3(threads), lds, st, A, a_stride, a_bs, B, b_stride, b_bs, (int)m, (int)n,
+  return launch_members(batch, [&](dim3 grid, int64_t b0) {
+    hipLaunchKernelGGL(sb_block_kernel<OP>, grid, dim3(threads), lds, st, A, a_stride, a_bs, B, b_stride, b_bs, (int)m, (int)n,
                        (int)k, (int)lds_row_words(W), b0, status, rank);
   });
 }
@@ -333,7 +327,7 @@ int launch(const word *A, int64_t a_stride, int64_t a_bs, word *B, int64_t b_str
 // when it exists.
 int run_path2_solve(const word *A, int64_t a_stride, int64_t a_bs, int64_t m, int64_t n, word *B, int64_t b_stride, int64_t b_bs, int64_t k,
                     int64_t batch, int32_t *status, int32_t *rank, hipStream_t st) {
-  const int64_t R = m > n ? m : n, wa = words_of(n), wb = words_of(k);
+  const int64_t R = m > n ? m : n, wa = width_of(n), wb = width_of(k);
   std::vector<int32_t> hs((size_t)batch), hr((size_t)batch), P((size_t)(m > 0 ? m : 1)), Q((size_t)(n > 0 ? n : 1));
   word *sA = nullptr, *sB = nullptr;
   Scratch scratch(st);
@@ -368,7 +362,7 @@ int run_path2_solve(const word *A, int64_t a_stride, int64_t a_bs, int64_t m, in
 // wanted) by m4ri_amd_echelonize_dev of the copy afterwards.
 int run_path2_inv(word *Binv, int64_t b_stride, int64_t b_bs, const word *A, int64_t a_stride, int64_t a_bs, int64_t n, int64_t batch, int32_t *rank,
                   hipStream_t st) {
-  const int64_t wn = words_of(n);
+  const int64_t wn = width_of(n);
   std::vector<int32_t> hr((size_t)batch);
   word *sA = nullptr, *sX = nullptr;
   Scratch scratch(st);
@@ -389,7 +383,7 @@ int run_path2_inv(word *Binv, int64_t b_stride, int64_t b_bs, const word *A, int
 // into an n x n scratch basis cleared before each member, whose first kc columns are copied under the mask.
 int run_path2_kernel(const word *A, int64_t a_stride, int64_t a_bs, int64_t m, int64_t n, word *R, int64_t r_stride, int64_t r_bs, int64_t kc,
                      int64_t batch, int32_t *rank, hipStream_t st) {
-  const int64_t wn = words_of(n), rows = m > 0 ? m : 1;
+  const int64_t wn = width_of(n), rows = m > 0 ? m : 1;
   std::vector<int32_t> hr((size_t)batch);
   word *sA = nullptr, *sR = nullptr;
   Scratch scratch(st);
@@ -418,7 +412,7 @@ int m4ri_amd_plan_solve_batch(int64_t m, int64_t n, int64_t k) {
   if (m < 0 || n < 0 || k < 0) return -1;
   const int64_t R = m > n ? m : n;
   if (R <= 64 && k <= 64) return 0;
-  const int64_t W = words_of(n) + words_of(k);
+  const int64_t W = width_of(n) + width_of(k);
   if (R > BATCH_LDS_BUDGET / 8 || W > BATCH_LDS_BUDGET / 8) return 2;
   return lds_bytes_path1(R, W, n, 0) <= BATCH_LDS_BUDGET ? 1 : 2;
 }
@@ -426,9 +420,9 @@ int m4ri_amd_plan_solve_batch(int64_t m, int64_t n, int64_t k) {
 int m4ri_amd_solve_left_batch_dev(const word *A, int64_t a_stride, int64_t a_bs, int64_t m, int64_t n, word *B, int64_t b_stride, int64_t b_bs,
                                   int64_t k, int64_t batch, int32_t *status, int32_t *rank, void *stream) {
   if (m < 0 || n < 0 || k < 0 || batch < 0 || a_stride < 0 || a_bs < 0 || b_stride < 0 || b_bs < 0) return (int)hipErrorInvalidValue;
-  const int64_t R = m > n ? m : n, wa = words_of(n), wb = words_of(k);
+  const int64_t R = m > n ? m : n, wa = width_of(n), wb = width_of(k);
   if (a_stride < wa || b_stride < wb) return (int)hipErrorInvalidValue;
-  if (batch > 1 && R > 0 && b_bs < (R - 1) * b_stride + wb) return (int)hipErrorInvalidValue;
+  if (!members_fit(batch, b_bs, R, b_stride, wb)) return (int)hipErrorInvalidValue;
   if (batch > 0 && !status) return (int)hipErrorInvalidValue;
   if (batch > 0 && ((m > 0 && n > 0 && !A) || (R > 0 && k > 0 && !B))) return (int)hipErrorInvalidValue;
   if (batch == 0) return 0;
@@ -441,14 +435,14 @@ int m4ri_amd_solve_left_batch_dev(const word *A, int64_t a_stride, int64_t a_bs,
 int m4ri_amd_inv_batch_dev(word *Binv, int64_t b_stride, int64_t b_bs, const word *A, int64_t a_stride, int64_t a_bs, int64_t n, int64_t batch,
                            int32_t *rank, void *stream) {
   if (n < 0 || batch < 0 || b_stride < 0 || b_bs < 0 || a_stride < 0 || a_bs < 0) return (int)hipErrorInvalidValue;
-  const int64_t wn = words_of(n);
+  const int64_t wn = width_of(n);
   if (b_stride < wn || a_stride < wn) return (int)hipErrorInvalidValue;
-  if (batch > 1 && n > 0 && b_bs < (n - 1) * b_stride + wn) return (int)hipErrorInvalidValue;
+  if (!members_fit(batch, b_bs, n, b_stride, wn)) return (int)hipErrorInvalidValue;
   if (batch > 0 && n > 0 && (!Binv || !A)) return (int)hipErrorInvalidValue;
   if (batch > 0 && n > 0) {  // in place with the same layout, or no overlap at all
     if (Binv == A) {
       if (a_stride != b_stride || a_bs != b_bs) return (int)hipErrorInvalidValue;
-    } else if (spans_meet(Binv, member_span_bytes(batch, b_bs, n, b_stride, wn), A, member_span_bytes(batch, a_bs, n, a_stride, wn))) {
+    } else if (spans_meet(rows_span(Binv, batch, b_bs, n, b_stride, wn), rows_span(A, batch, a_bs, n, a_stride, wn))) {
       return (int)hipErrorInvalidValue;
     }
   }
@@ -470,16 +464,14 @@ int m4ri_amd_plan_kernel_batch(int64_t m, int64_t n) {
 int m4ri_amd_kernel_left_batch_dev(const word *A, int64_t a_stride, int64_t a_bs, int64_t m, int64_t n, word *R, int64_t r_stride, int64_t r_bs,
                                    int64_t kc, int64_t batch, int32_t *rank, void *stream) {
   if (m < 0 || n < 0 || kc < 0 || batch < 0 || a_stride < 0 || a_bs < 0 || r_stride < 0 || r_bs < 0 || kc > n) return (int)hipErrorInvalidValue;
-  const int64_t wa = words_of(n), wr = words_of(kc);
+  const int64_t wa = width_of(n), wr = width_of(kc);
   if (a_stride < wa || r_stride < wr) return (int)hipErrorInvalidValue;
-  if (batch > 1 && n > 0 && r_bs < (n - 1) * r_stride + wr) return (int)hipErrorInvalidValue;
+  if (!members_fit(batch, r_bs, n, r_stride, wr)) return (int)hipErrorInvalidValue;
   if (batch > 0 && !rank) return (int)hipErrorInvalidValue;
   const bool a_data = m > 0 && n > 0, r_data = kc > 0;  // kc <= n
   if (batch > 0 && ((a_data && !A) || (r_data && !R))) return (int)hipErrorInvalidValue;
   // R's span and A's span (first member's start to last member's end) must not meet
-  if (batch > 0 && a_data && r_data &&
-      spans_meet(R, member_span_bytes(batch, r_bs, n, r_stride, wr), A, member_span_bytes(batch, a_bs, m, a_stride, wa)))
-    return (int)hipErrorInvalidValue;
+  if (spans_meet(rows_span(R, batch, r_bs, n, r_stride, wr), rows_span(A, batch, a_bs, m, a_stride, wa))) return (int)hipErrorInvalidValue;
   if (batch == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
   if (n == 0) return (int)hipMemsetAsync(rank, 0, (size_t)batch * 4, st);

@@ -412,9 +412,9 @@ int64_t scratch_of(int64_t nx, int64_t batch) {
 template <typename Kernel>
 int launch_units(Kernel kernel, SrArgs &p, int64_t batch, int64_t per, int threads, size_t lds, hipStream_t st) {
   p.per = per;
-  return launch_chunked(batch * per, BATCH_CHUNK, [&](int64_t u0, int64_t nu) {
+  return launch_members(batch * per, [&](dim3 grid, int64_t u0) {
     p.u0 = u0;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)nu), dim3((unsigned)threads), lds, st, p);
+    hipLaunchKernelGGL(kernel, grid, dim3((unsigned)threads), lds, st, p);
   });
 }
 
@@ -446,7 +446,7 @@ int m4ri_amd_sort_rows_batch_dev(const word *X, int64_t x_stride, int64_t x_bs, 
   if (n > RS_N_MAX || ell > JOIN_ELL_MAX || nx > SR_ROWS_MAX) return (int)hipErrorNotSupported;
   if (!cols && ell > n) return (int)hipErrorInvalidValue;
   if ((!order && !ucount) || (uniq && !ucount) || (mult && !uniq)) return (int)hipErrorInvalidValue;
-  const int64_t width = words_of(n);
+  const int64_t width = width_of(n);
   if (nx > 1 && x_stride < width) return (int)hipErrorInvalidValue;
   if (batch > 1 && l_bs < nx) return (int)hipErrorInvalidValue;
   const int64_t need = scratch_of(nx, batch);
@@ -454,20 +454,14 @@ int m4ri_amd_sort_rows_batch_dev(const word *X, int64_t x_stride, int64_t x_bs, 
   if (batch > 0) {
     if (n > 0 && nx > 0 && !X) return (int)hipErrorInvalidValue;
     if (need > 0 && (!scratch || scratch_bytes < need || ((uintptr_t)scratch & 7))) return (int)hipErrorInvalidValue;
-    if (join_spans_meet({join_entries_span(order, batch, l_bs, nx, 8), join_entries_span(uniq, batch, l_bs, nx, 8), join_entries_span(mult, batch, l_bs, nx, 8),
-                         join_entries_span(ucount, batch, 1, 1, 8), join_entries_span(need > 0 ? scratch : nullptr, 1, 0, need, 1)},
-                        {join_rows_span(X, batch, x_bs, nx, x_stride, n), join_entries_span(xcount, batch, 1, 1, 8), join_entries_span(cols, batch, c_bs, ell, 4)}))
+    if (spans_meet_any({entries_span(order, batch, l_bs, nx, 8), entries_span(uniq, batch, l_bs, nx, 8), entries_span(mult, batch, l_bs, nx, 8),
+                        entries_span(ucount, batch, 1, 1, 8), entries_span(need > 0 ? scratch : nullptr, 1, 0, need, 1)},
+                       {rows_span(X, batch, x_bs, nx, x_stride, width), entries_span(xcount, batch, 1, 1, 8), entries_span(cols, batch, c_bs, ell, 4)}))
       return (int)hipErrorInvalidValue;
   }
   if (batch == 0) return 0;
 
-  static std::once_flag once;
-  static hipError_t attr = hipSuccess;
-  std::call_once(once, [&] {
-    attr = hipFuncSetAttribute(reinterpret_cast<const void *>(sr_wg_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SR_LDS_MAX);
-    if (attr == hipSuccess) attr = hipFuncSetAttribute(reinterpret_cast<const void *>(sr_chunk_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SR_LDS_MAX);
-  });
-  HIPTRY(attr);
+  HIPTRY(set_max_dynamic_lds(SR_LDS_MAX, sr_wg_kernel, sr_chunk_kernel));
 
   SrArgs p{};
   p.X = X, p.xcount = xcount, p.cols = cols, p.x_stride = x_stride, p.x_bs = x_bs, p.c_bs = c_bs, p.nx = nx, p.l_bs = l_bs;

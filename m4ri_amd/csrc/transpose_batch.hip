@@ -110,16 +110,6 @@ __global__ __launch_bounds__(BATCH_WAVE_THREADS) void trb_inplace_kernel(word *M
   if (rowi < n) *pu = (lt & maskw) | (u & ~maskw);
 }
 
-// the path-1 bound of this call: TRB_T1 unless the environment overrides it (read per call; [64, 1024] in multiples of 64)
-int64_t path1_max() {
-  const char *s = getenv("M4RI_AMD_TRANSPOSE_BATCH_PATH1_MAX");
-  if (!s || !*s) return TRB_T1;
-  int64_t v = atoll(s) / 64 * 64;
-  if (v < 64) v = 64;
-  if (v > TRB_MAX) v = TRB_MAX;
-  return v;
-}
-
 // M4RI_AMD_TRANSPOSE_BATCH_TILES set and not "0": every out-of-place call takes the tile kernel, members of 64 and below included.
 // This is contender (b) of tools/bench_transpose_batch.py, which no bound can route a member of 64 and below to.
 bool tiles_forced() {
@@ -142,29 +132,26 @@ int m4ri_amd_plan_transpose_batch(int64_t nrows, int64_t ncols) { return plan(nr
 int m4ri_amd_transpose_batch_dev(word *D, int64_t d_stride, int64_t d_bs, const word *A, int64_t a_stride, int64_t a_bs, int64_t nrows, int64_t ncols,
                                  int64_t batch, void *stream) {
   if (nrows < 0 || ncols < 0 || batch < 0 || d_stride < 0 || d_bs < 0 || a_stride < 0 || a_bs < 0) return (int)hipErrorInvalidValue;
-  const int64_t wa = words_of(ncols), wd = words_of(nrows);
+  const int64_t wa = width_of(ncols), wd = width_of(nrows);
   if (a_stride < wa || d_stride < wd) return (int)hipErrorInvalidValue;
   const bool data = nrows > 0 && ncols > 0;
-  if (batch > 1 && data && d_bs < (ncols - 1) * d_stride + wd) return (int)hipErrorInvalidValue;
+  if (data && !members_fit(batch, d_bs, ncols, d_stride, wd)) return (int)hipErrorInvalidValue;
   if (batch > 0 && data && (!D || !A)) return (int)hipErrorInvalidValue;
   // in place: the same square members of at most 1024 at the same places.  D == A in any other shape is refused whatever the batch
   // (so that what an in-place call may look like is settled by its shape alone); any other meeting of D's span and A's is an overlap.
   const bool inplace = data && D && D == A && nrows == ncols && nrows <= TRB_MAX && d_stride == a_stride && d_bs == a_bs;
   if (data && D && D == A && !inplace) return (int)hipErrorInvalidValue;
-  if (batch > 0 && data && !inplace &&
-      spans_meet(D, member_span_bytes(batch, d_bs, ncols, d_stride, wd), A, member_span_bytes(batch, a_bs, nrows, a_stride, wa)))
-    return (int)hipErrorInvalidValue;
+  if (!inplace && spans_meet(rows_span(D, batch, d_bs, ncols, d_stride, wd), rows_span(A, batch, a_bs, nrows, a_stride, wa))) return (int)hipErrorInvalidValue;
   if (batch == 0 || !data) return 0;
   hipStream_t st    = (hipStream_t)stream;
   const int64_t per = BATCH_WAVE_THREADS / 64;
-  const int path    = inplace ? (nrows <= 64 ? 0 : 1) : tiles_forced() ? 2 : plan(nrows, ncols, path1_max());
+  // the path-1 bound: TRB_T1 unless the environment overrides it, [64, TRB_MAX] in multiples of 64
+  const int path = inplace ? (nrows <= 64 ? 0 : 1) : tiles_forced() ? 2 : plan(nrows, ncols, env_bound("M4RI_AMD_TRANSPOSE_BATCH_PATH1_MAX", TRB_T1, 64, TRB_MAX, 64));
   if (path == 2) return (int)gf2_launch_transpose_tiles(st, D, d_stride, d_bs, A, a_stride, a_bs, nrows, ncols, batch);
-  if (path == 0) {
-    return launch_chunked(batch, BATCH_CHUNK * per, [&](int64_t b0, int64_t nb) {
-      hipLaunchKernelGGL(trb_wave_kernel, dim3((unsigned)((nb + per - 1) / per)), dim3(BATCH_WAVE_THREADS), 0, st, D, d_stride, d_bs, A, a_stride, a_bs,
-                         (int)nrows, (int)ncols, b0, b0 + nb);
+  if (path == 0)
+    return launch_waves(batch, [&](dim3 grid, int64_t b0, int64_t nb) {
+      hipLaunchKernelGGL(trb_wave_kernel, grid, dim3(BATCH_WAVE_THREADS), 0, st, D, d_stride, d_bs, A, a_stride, a_bs, (int)nrows, (int)ncols, b0, b0 + nb);
     });
-  }
   // waves per member: blocks out of place (at most 256), block pairs in place (at most 136)
   const int64_t mb = wd, waves = inplace ? mb * (mb + 1) / 2 : mb * wa;
   return launch_chunked(batch, BATCH_CHUNK * per / waves, [&](int64_t b0, int64_t nb) {
