@@ -922,6 +922,55 @@ int m4ri_amd_pivot_exchange_batch_dev(word *D, int64_t d_stride, int64_t d_bs, i
  * alone decides between paths 1 and 2, at any step count) replace the bounds in the routing of a call, read per call; this function
  * does not read them. */
 int m4ri_amd_plan_pivot_exchange_batch(int64_t nrows, int64_t ncols, int64_t steps);
+/* A whole INFORMATION-SET DECODING SEARCH on the stored reduced echelon forms of `batch` members, one launch (isd_search_batch.hip): up
+ * to `iters` times "exchange `steps` pivots, then weigh all sums of t pivot rows against the received word", the lightest word seen
+ * kept with its key and its iteration, a member stopped as soon as that weight is <= w_stop.  t = 0 is Prange, t >= 1 Lee-Brickell;
+ * without a follower row it is a search for light codewords (w_min = 1).  The rule is a composition of two calls of this header, and
+ * the results equal theirs bit for bit.
+ * The state is that of m4ri_amd_pivot_exchange_batch_dev: D_b in place, pivots in/out, rank READ ONLY, the optional order in/out.
+ * k = pivot_rows; G_b = rows 0 .. k-1 of the current D_b; V_b = row k of the current D_b if nrows > pivot_rows, else the zero word: the
+ * first follower is the received word, further followers only follow.
+ * The rule.  Iteration it = 0, 1, ... of member b:
+ * 1. If it > 0: `steps` exchanges exactly as m4ri_amd_pivot_exchange_batch_dev(req = NULL, steps, seed = seed_it) performs them on this
+ *    member -- the same draw h = output number b * steps + s of the stream seeded seed_it, the same validity test, the same update of
+ *    D, pivots and order -- with seed_it = output number `it` of the counter-form splitmix64 stream seeded `seed`
+ *    (m4ri_amd.isd_iteration_seed in the Python layer).  Iteration 0 enumerates the form as the caller left it.
+ * 2. key_it = what m4ri_amd_row_sums_weights_batch_dev(G_b, k, n = ncols, V_b, t, w_min) writes to lightest: the minimum of
+ *    (wt << 40) | colexicographic rank over the sets with wt >= w_min, -1 if there is none.
+ * 3. The best is replaced when key_it >= 0 and either best < 0 or (key_it >> 40) < (best >> 40): only a strictly lighter word replaces
+ *    it, so the earliest iteration wins among equal weights.  Then best = key_it, best_iter = it and W_b = the word c(S) of that key on
+ *    the form of this iteration (only the ncols valid bits of W_b, at W + b * w_bs, are written).
+ * 4. If best >= 0 and (best >> 40) <= w_stop the member stops, iters_run[b] = it + 1.  A negative w_stop never stops a member.
+ * Otherwise the loop ends after `iters` iterations, iters_run[b] = iters.  D_b, pivots and order are left as the last iteration run
+ * left them, so calls chain; done[b] = all exchange steps performed.  best (DEVICE int64) is required; best_iter, iters_run, done
+ * (DEVICE int32) and W are optional.  Every wanted output is written whole -- best_iter[b] = -1 where best[b] = -1 -- except that W_b
+ * of a member with best = -1 is not written, and a member's D, pivots and order are written only if a step was performed.  iters = 0
+ * gives best = -1 and iters_run = 0 and touches nothing else.  rank is read by the exchange only: a refused member (rank -1)
+ * exchanges nothing and is still enumerated, as the composition would.
+ * hipErrorNotSupported (801), before any HIP call: pivot_rows or ncols > 1024, t > 8, C(pivot_rows, t) > 2^24 (one workgroup walks all
+ * sums of its member in every iteration; beyond that the two-call iteration, which spreads a member over the chip, is the right
+ * tool), a member beyond path 1 of m4ri_amd_plan_isd_search, or counts beyond 32 bits (iters or (iters - 1) * steps > 2^31 - 1).
+ * hipErrorInvalidValue, before any HIP call, for negative sizes, strides, batch strides, iters, steps, t or w_min, pivot_rows > nrows,
+ * olen > ncols, d_stride < words(ncols), overlapping D members, o_bs < olen with an order and batch > 1, w_bs < words(ncols) with W
+ * and batch > 1, a NULL best with batch > 0, a NULL D with non-empty members and iters > 0, a NULL pivots or rank when an exchange
+ * can happen (non-empty members, steps > 0 and iters > 1), or any two of D's span, pivots, rank, order, best, best_iter, iters_run,
+ * done and W whose bytes meet.  batch = 0 succeeds and touches nothing.  Asynchronous on `stream`: plain launches, no allocation, no
+ * copy to the host, no engine lock, no atomics; capturable.
+ * WHICH TO USE (measured at t = 2, 16 iterations): this call is ahead of the loop of the two calls at every measured
+ * shape -- 1.3x at 32 x 64, 2.0x to 2.6x at 64 x 128, where the loop's launches and stagings are the time, and 1.08x to 1.10x at
+ * 256 x 512, where the enumeration is -- and only it can stop a member.  Beyond 2^24 sums per member (refused here) and for a handful
+ * of large members, use the two calls: they spread one member's sums over the chip, here one workgroup walks them all. */
+int m4ri_amd_isd_search_dev(word *D, int64_t d_stride, int64_t d_bs, int64_t nrows, int64_t ncols, int64_t pivot_rows, int32_t *pivots,
+                            const int32_t *rank, int64_t batch, int64_t iters, int64_t steps, uint64_t seed, int64_t t, int64_t w_min, int64_t w_stop,
+                            int32_t *order, int64_t o_bs, int64_t olen, int64_t *best, int32_t *best_iter, int32_t *iters_run, int32_t *done, word *W,
+                            int64_t w_bs, void *stream);
+/* which path the call above takes (pure host arithmetic; -1 for negative sizes): 0 one wave per member, four members per workgroup,
+ * lane i holds row i (nrows, ncols <= 64); 1 one workgroup per member, the member staged in LDS once for the whole loop (the layout
+ * of path 1 of m4ri_amd_plan_pivot_exchange_batch, with 128 bytes of key slots and a word of words(ncols) words behind the slots,
+ * within 160 KiB); 2 everything else, the limits above included: the call returns 801.  There is no path in place in global memory:
+ * the call exists for members that stay resident.  The environment variable M4RI_AMD_ISD_SEARCH_PATH0_MAX (the largest side of
+ * path 0, clamped to [0, 64]) replaces the bound in the routing of a call, read per call; this function does not read it. */
+int m4ri_amd_plan_isd_search(int64_t nrows, int64_t ncols, int64_t pivot_rows, int64_t t);
 /* `batch` independent systems A_b X_b = B_b (mzd_solve_left, m4ri/solve.c:30-152; solve_batch.hip).  A_b: the m x n matrix at
  * A + b * a_bs, READ ONLY (a_bs = 0: one A shared by all members).  B_b: the max(m, n) x k matrix at B + b * b_bs.  status[b]
  * (DEVICE int32, required): 0, or -1 when A_b X = B_b has no solution, A_b padded with zero rows to max(m, n).  On status 0, B_b is

@@ -230,6 +230,9 @@ SYMBOLS = {
     "m4ri_amd_random_orders_batch_dev": (_I, [_P, _I64, _I64, _I64, ctypes.c_uint64, _P]),
     "m4ri_amd_pivot_exchange_batch_dev": (_I, [_P, _I64, _I64, _I64, _I64, _I64, _P, _P, _I64, _P, _I64, _I64, ctypes.c_uint64, _P, _I64, _I64, _P, _P]),
     "m4ri_amd_plan_pivot_exchange_batch": (_I, [_I64, _I64, _I64]),
+    "m4ri_amd_isd_search_dev": (_I, [_P, _I64, _I64, _I64, _I64, _I64, _P, _P, _I64, _I64, _I64, ctypes.c_uint64, _I64, _I64, _I64, _P, _I64, _I64, _P, _P, _P,
+                                     _P, _P, _I64, _P]),
+    "m4ri_amd_plan_isd_search": (_I, [_I64, _I64, _I64, _I64]),
     "m4ri_amd_solve_left_batch_dev": (_I, [_P, _I64, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I64, _P, _P, _P]),
     "m4ri_amd_inv_batch_dev": (_I, [_P, _I64, _I64, _P, _I64, _I64, _I64, _I64, _P, _P]),
     "m4ri_amd_plan_solve_batch": (_I, [_I64, _I64, _I64]),
@@ -960,6 +963,35 @@ def exchange_draw(seed: int, b: int, steps: int, s: int, rank: int, ncols: int):
         raise ValueError("exchange_draw: rank >= 1, ncols >= 1, 0 <= s < steps, b >= 0")
     h = int(splitmix_words(seed, b * steps + s, 1)[0])
     return (h >> 32) % rank, (h & 0xFFFFFFFF) % ncols
+
+
+def isd_search_dev(D: int, d_stride: int, d_bs: int, nrows: int, ncols: int, pivot_rows: int, pivots: int, rank: int, batch: int, iters: int,
+                   steps: int, seed: int, t: int, w_min: int, w_stop: int, best: int, order: int = 0, o_bs: int = 0, olen: int = 0, best_iter: int = 0,
+                   iters_run: int = 0, done: int = 0, W: int = 0, w_bs: int = 0, stream: int = 0) -> None:
+    """A whole information-set decoding search in one launch, on the state of pivot_exchange_batch_dev: up to `iters` times "`steps`
+    exchanges drawn from the stream seeded isd_iteration_seed(seed, it) (none before iteration 0), then the lightest sum of t of the
+    pivot_rows pivot rows against row pivot_rows (the received word; the zero word if nrows == pivot_rows) with weight >= w_min", as
+    pivot_exchange_batch_dev and row_sums_weights_batch_dev give them.  best (DEVICE int64, required): the key of the lightest word over
+    the iterations, the earliest among equal weights, -1 for none; best_iter, iters_run, done (DEVICE int32, 0 = not wanted): its
+    iteration, the iterations run (a member stops once its best weight is <= w_stop; w_stop < 0: never) and the steps performed; W
+    (0 = not wanted): the word itself, member b's at W + b * w_bs.  Asynchronous, lock-free and capturable on paths 0-1 of
+    plan_isd_search; path 2: 801."""
+    _check(lib().m4ri_amd_isd_search_dev(D or None, d_stride, d_bs, nrows, ncols, pivot_rows, pivots or None, rank or None, batch, iters, steps,
+                                         seed & 0xFFFFFFFFFFFFFFFF, t, w_min, w_stop, order or None, o_bs, olen, best or None, best_iter or None,
+                                         iters_run or None, done or None, W or None, w_bs, stream), "m4ri_amd_isd_search_dev")
+
+
+def plan_isd_search(nrows: int, ncols: int, pivot_rows: int, t: int) -> int:
+    """The path isd_search_dev takes for members of this shape at this t (0 wave, 1 LDS, 2 not supported).  Host arithmetic."""
+    return int(lib().m4ri_amd_plan_isd_search(nrows, ncols, pivot_rows, t))
+
+
+def isd_iteration_seed(seed: int, it: int) -> int:
+    """The seed of the exchanges before iteration `it` >= 1 of isd_search_dev: output number `it` of the splitmix64 stream seeded
+    `seed`.  exchange_draw(isd_iteration_seed(seed, it), b, steps, s, rank, ncols) is the draw of step s of member b there."""
+    if it < 0:
+        raise ValueError("isd_iteration_seed: it >= 0")
+    return int(splitmix_words(seed, it, 1)[0])
 
 
 def solve_left_batch_dev(A: int, a_stride: int, a_bs: int, m: int, n: int, B: int, b_stride: int, b_bs: int, k: int, batch: int, status: int,

@@ -207,6 +207,83 @@ static void pivot_exchange() {
   EXPECT(m4ri_amd_plan_pivot_exchange_batch(5, 5, -1), -1);
 }
 
+// ---- the search of information-set decoding -------------------------------------------------------------------------------------------------
+static void isd_search() {
+  // D: 2 members of 5 x 64 (80 bytes), four pivot rows and the received word; pivots 2 x 4 entries; rank 8 bytes; order 2 x 64 entries; best 16 bytes;
+  // best_iter, iters_run, done 8 bytes each; W 2 x 1 word
+  const int64_t M = INT64_MAX;
+  word *D = (word *)(1ull << 20), *W = (word *)(1ull << 36);
+  int32_t *P = (int32_t *)(1ull << 22), *R = (int32_t *)(1ull << 24), *O = (int32_t *)(1ull << 26), *I = (int32_t *)(1ull << 30), *U = (int32_t *)(1ull << 32),
+          *N = (int32_t *)(1ull << 34);
+  int64_t *B = (int64_t *)(1ull << 28);
+  auto at = [](void *p, long bytes) { return (int32_t *)((char *)p + bytes); };
+  EXPECT(m4ri_amd_isd_search_dev(D, 1, 5, 5, 64, 4, P, R, 0, 6, 3, 7, 2, 1, 3, O, 64, 64, B, I, U, N, W, 1, nullptr), 0);                  // batch = 0
+  EXPECT(m4ri_amd_isd_search_dev(nullptr, 1, 5, 5, 64, 4, nullptr, nullptr, 0, 0, 0, 7, 0, 0, -1, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr), 0);
+  EXPECT(m4ri_amd_isd_search_dev(D, 1, 5, -1, 64, 0, P, R, 2, 6, 3, 7, 2, 1, 3, O, 64, 64, B, I, U, N, W, 1, nullptr), 1);
+  EXPECT(m4ri_amd_isd_search_dev(D, 1, 5, 5, 64, 4, P, R, -1, 6, 3, 7, 2, 1, 3, O, 64, 64, B, I, U, N, W, 1, nullptr), 1);
+  EXPECT(m4ri_amd_isd_search_dev(D, 1, 5, 5, 64, 4, P, R, 2, -1, 3, 7, 2, 1, 3, O, 64, 64, B, I, U, N, W, 1, nullptr), 1);                 // iters < 0
+  EXPECT(m4ri_amd_isd_search_dev(D, 1, 5, 5, 64, 4, P, R, 2, 6, -1, 7, 2, 1, 3, O, 64, 64, B, I, U, N, W, 1, nullptr), 1);                 // steps < 0
+  EXPECT(m4ri_amd_isd_search_dev(D, 1, 5, 5, 64, 4, P, R, 2, 6, 3, 7, -1, 1, 3, O, 64, 64, B, I, U, N, W, 1, nullptr), 1);                 // t < 0
+  EXPECT(m4ri_amd_isd_search_dev(D, 1, 5, 5, 64, 4, P, R, 2, 6, 3, 7, 2, -1, 3, O, 64, 64, B, I, U, N, W, 1, nullptr), 1);                 // w_min < 0
+  EXPECT(m4ri_amd_isd_search_dev(D, 1, 5, 5, 64, 4, P, R, 2, 6, 3, 7, 2, 1, 3, O, 64, 64, B, I, U, N, W, -1, nullptr), 1);                 // w_bs < 0
+  EXPECT(m4ri_amd_isd_search_dev(D, 1, 5, 5, 64, 6, P, R, 2, 6, 3, 7, 2, 1, 3, O, 64, 64, B, I, U, N, W, 1, nullptr), 1);                  // pivot_rows > nrows
+  EXPECT(m4ri_amd_isd_search_dev(D, 1, 5, 5, 64, 4, P, R, 2, 6, 3, 7, 2, 1, 3, O, 65, 65, B, I, U, N, W, 1, nullptr), 1);                  // olen > ncols
+  EXPECT(m4ri_amd_isd_search_dev(D, 0, 5, 5, 64, 4, P, R, 2, 6, 3, 7, 2, 1, 3, O, 64, 64, B, I, U, N, W, 1, nullptr), 1);                  // d_stride < words
+  EXPECT(m4ri_amd_isd_search_dev(D, 1, 4, 5, 64, 4, P, R, 2, 6, 3, 7, 2, 1, 3, O, 64, 64, B, I, U, N, W, 1, nullptr), 1);                  // overlapping members
+  EXPECT(m4ri_amd_isd_search_dev(D, 1, 5, 5, 64, 4, P, R, 2, 6, 3, 7, 2, 1, 3, O, 63, 64, B, I, U, N, W, 1, nullptr), 1);                  // o_bs < olen
+  EXPECT(m4ri_amd_isd_search_dev(D, 1, 5, 5, 64, 4, P, R, 2, 6, 3, 7, 2, 1, 3, O, 64, 64, B, I, U, N, W, 0, nullptr), 1);                  // w_bs < words
+  EXPECT(m4ri_amd_isd_search_dev(nullptr, 1, 5, 5, 64, 4, P, R, 2, 6, 3, 7, 2, 1, 3, O, 64, 64, B, I, U, N, W, 1, nullptr), 1);
+  EXPECT(m4ri_amd_isd_search_dev(D, 1, 5, 5, 64, 4, nullptr, R, 2, 6, 3, 7, 2, 1, 3, O, 64, 64, B, I, U, N, W, 1, nullptr), 1);
+  EXPECT(m4ri_amd_isd_search_dev(D, 1, 5, 5, 64, 4, P, nullptr, 2, 6, 3, 7, 2, 1, 3, O, 64, 64, B, I, U, N, W, 1, nullptr), 1);
+  EXPECT(m4ri_amd_isd_search_dev(D, 1, 5, 5, 64, 4, P, R, 2, 6, 3, 7, 2, 1, 3, O, 64, 64, nullptr, I, U, N, W, 1, nullptr), 1);            // best is required
+  EXPECT(m4ri_amd_isd_search_dev(D, 1, 5, 5, 64, 4, P, R, 2, 0, 3, 7, 2, 1, 3, O, 64, 64, nullptr, I, U, N, W, 1, nullptr), 1);            // without iterations too
+  EXPECT(m4ri_amd_isd_search_dev(D, 1, 5, 5, 64, 4, at(D, 76), R, 2, 6, 3, 7, 2, 1, 3, O, 64, 64, B, I, U, N, W, 1, nullptr), 1);          // pivots on D's last word
+  EXPECT(m4ri_amd_isd_search_dev(D, 1, 5, 5, 64, 4, P, at(P, 28), 2, 6, 3, 7, 2, 1, 3, O, 64, 64, B, I, U, N, W, 1, nullptr), 1);          // rank on pivots
+  EXPECT(m4ri_amd_isd_search_dev(D, 1, 5, 5, 64, 4, P, R, 2, 6, 3, 7, 2, 1, 3, at(R, 4), 64, 64, B, I, U, N, W, 1, nullptr), 1);           // order on rank
+  EXPECT(m4ri_amd_isd_search_dev(D, 1, 5, 5, 64, 4, P, R, 2, 6, 3, 7, 2, 1, 3, O, 64, 64, (int64_t *)at(O, 504), I, U, N, W, 1, nullptr), 1);   // best on order
+  EXPECT(m4ri_amd_isd_search_dev(D, 1, 5, 5, 64, 4, P, R, 2, 6, 3, 7, 2, 1, 3, O, 64, 64, B, at(B, 12), U, N, W, 1, nullptr), 1);          // best_iter on best
+  EXPECT(m4ri_amd_isd_search_dev(D, 1, 5, 5, 64, 4, P, R, 2, 6, 3, 7, 2, 1, 3, O, 64, 64, B, I, at(I, 4), N, W, 1, nullptr), 1);           // iters_run on best_iter
+  EXPECT(m4ri_amd_isd_search_dev(D, 1, 5, 5, 64, 4, P, R, 2, 6, 3, 7, 2, 1, 3, O, 64, 64, B, I, U, U, W, 1, nullptr), 1);                  // done on iters_run
+  EXPECT(m4ri_amd_isd_search_dev(D, 1, 5, 5, 64, 4, P, R, 2, 6, 3, 7, 2, 1, 3, O, 64, 64, B, I, U, N, (word *)at(N, 0), 1, nullptr), 1);   // W on done
+  EXPECT(m4ri_amd_isd_search_dev(D, 1, 5, 5, 64, 4, P, R, 2, 6, 3, 7, 2, 1, 3, O, 64, 64, B, I, U, N, D + 9, 1, nullptr), 1);              // W on D's last word
+  EXPECT(m4ri_amd_isd_search_dev(D, 1, 5, 5, 64, 4, P, R, 2, 6, 3, 7, 2, 1, 3, O, 64, 64, B, I, U, N, (word *)(1ull << 19), M, nullptr), 1);   // W below all: its 2^66 bytes reach everything
+  EXPECT(m4ri_amd_isd_search_dev(D, 1, M, 5, 64, 4, P, R, 2, 6, 3, 7, 2, 1, 3, O, 64, 64, B, I, U, N, nullptr, 0, nullptr), 1);            // and D's
+  EXPECT(m4ri_amd_isd_search_dev(D, 1, 5, 5, 64, 4, P, R, 2, 6, 3, 7, 2, 1, 3, O, M, 64, B, I, U, N, W, 1, nullptr), 1);                   // and the order's
+  // the limits: 801 with and without members, after the sizes and before the pointers
+  EXPECT(m4ri_amd_isd_search_dev(D, 1, 5, 5, 64, 4, P, R, 2, 6, 3, 7, 9, 1, 3, O, 64, 64, B, I, U, N, W, 1, nullptr), 801);                // t > 8
+  EXPECT(m4ri_amd_isd_search_dev(D, 1, 5, 5, 64, 4, P, R, 0, 6, 3, 7, M, 1, 3, O, 64, 64, B, I, U, N, W, 1, nullptr), 801);
+  EXPECT(m4ri_amd_isd_search_dev(D, 1, 1 << 20, 1025, 64, 1025, P, R, 2, 6, 3, 7, 1, 1, 3, O, 64, 64, B, I, U, N, W, 1, nullptr), 801);    // pivot_rows > 1024
+  EXPECT(m4ri_amd_isd_search_dev(D, 17, 1 << 20, 5, 1025, 4, P, R, 2, 6, 3, 7, 1, 1, 3, nullptr, 0, 0, B, I, U, N, W, 17, nullptr), 801);  // ncols > 1024
+  EXPECT(m4ri_amd_isd_search_dev(D, 1, 1 << 20, 1024, 64, 1024, P, R, 2, 6, 3, 7, 2, 1, 3, O, 64, 64, B, I, U, N, W, 1, nullptr), 1);      // C(1024, 2) is in: D reaches pivots
+  EXPECT(m4ri_amd_isd_search_dev(D, 1, 1 << 20, 1024, 64, 1024, P, R, 0, 6, 3, 7, 2, 1, 3, O, 64, 64, B, I, U, N, W, 1, nullptr), 0);
+  EXPECT(m4ri_amd_isd_search_dev(D, 1, 1 << 20, 1024, 64, 1024, P, R, 0, 6, 3, 7, 3, 1, 3, O, 64, 64, B, I, U, N, W, 1, nullptr), 801);    // C(1024, 3) > 2^24
+  EXPECT(m4ri_amd_isd_search_dev(D, 16, 1 << 20, 2000, 1024, 4, P, R, 2, 6, 3, 7, 2, 1, 3, nullptr, 0, 0, B, I, U, N, W, 16, nullptr), 801);    // beyond LDS
+  EXPECT(m4ri_amd_isd_search_dev(D, M, M, M, M, M, P, R, 2, M, M, 7, M, M, M, O, M, M, B, I, U, N, W, M, nullptr), 801);
+  EXPECT(m4ri_amd_isd_search_dev(D, M, M, M, 64, 4, P, R, 0, 6, 3, 7, 2, 1, 3, O, 64, 64, B, I, U, N, W, 1, nullptr), 801);                // INT64_MAX rows
+  EXPECT(m4ri_amd_isd_search_dev(D, 1, 5, 5, 64, 4, P, R, 2, M, 3, 7, 2, 1, 3, O, 64, 64, B, I, U, N, W, 1, nullptr), 801);                // 32-bit counts
+  EXPECT(m4ri_amd_isd_search_dev(D, 1, 5, 5, 64, 4, P, R, 2, 6, M, 7, 2, 1, 3, O, 64, 64, B, I, U, N, W, 1, nullptr), 801);
+  EXPECT(m4ri_amd_isd_search_dev(D, 1, 5, 5, 64, 4, P, R, 2, M, M, 7, 2, 1, 3, O, 64, 64, B, I, U, N, W, 1, nullptr), 801);
+  EXPECT(m4ri_amd_isd_search_dev(D, 1, 5, 5, 64, 4, P, R, 0, INT32_MAX, 1, 7, 2, M, M, O, 64, 64, B, I, U, N, W, 1, nullptr), 0);
+  EXPECT(m4ri_amd_isd_search_dev(D, 1, 5, 5, 64, 4, P, R, 0, 1, M, 7, 2, 1, -M, O, 64, 64, B, I, U, N, W, 1, nullptr), 0);                 // one iteration: no step
+  EXPECT(m4ri_amd_isd_search_dev(D, 1, 5, 5, 64, 4, P, R, 0, (int64_t)INT32_MAX + 1, 0, 7, 2, 1, 3, O, 64, 64, B, I, U, N, W, 1, nullptr), 801);
+  EXPECT(m4ri_amd_isd_search_dev(D, 0, 5, 5, 64, 4, P, R, 2, 6, 3, 7, 9, 1, 3, O, 64, 64, B, I, U, N, W, 1, nullptr), 1);                  // the stride before the limits
+  setenv("M4RI_AMD_ISD_SEARCH_PATH0_MAX", "junk", 1);
+  EXPECT(m4ri_amd_isd_search_dev(D, 1, 5, 5, 64, 4, P, R, 0, 6, 3, 7, 2, 1, 3, O, 64, 64, B, I, U, N, W, 1, nullptr), 0);
+  setenv("M4RI_AMD_ISD_SEARCH_PATH0_MAX", "-99999999999999999999", 1);
+  EXPECT(m4ri_amd_isd_search_dev(D, 1, 5, 5, 64, 4, P, R, 0, 6, 3, 7, 9, 1, 3, O, 64, 64, B, I, U, N, W, 1, nullptr), 801);
+  EXPECT(m4ri_amd_plan_isd_search(64, 64, 64, 9), 2);                                                                                      // the plan does not read it
+  EXPECT(m4ri_amd_plan_isd_search(0, 0, 0, 0), 0);
+  EXPECT(m4ri_amd_plan_isd_search(64, 64, 63, 3), 0);
+  EXPECT(m4ri_amd_plan_isd_search(65, 64, 64, 3), 1);
+  EXPECT(m4ri_amd_plan_isd_search(1024, 1024, 1024, 2), 1);
+  EXPECT(m4ri_amd_plan_isd_search(1024, 1024, 1024, 3), 2);
+  EXPECT(m4ri_amd_plan_isd_search(2000, 1024, 4, 2), 2);
+  EXPECT(m4ri_amd_plan_isd_search(M, M, M, M), 2);
+  EXPECT(m4ri_amd_plan_isd_search(M, 64, 4, 0), 2);
+  EXPECT(m4ri_amd_plan_isd_search(-1, 5, 1, 1), -1);
+  EXPECT(m4ri_amd_plan_isd_search(5, 5, 1, -1), -1);
+}
+
 // ---- the calls on single operands: elimination, solves, products, transposes, reductions, assembly, weights --------------------------
 // Operands at ascending addresses 2^20 apart, A lowest: a span that is too long by the integers reaches every operand above it.
 static void sizes_beyond_int64() {
@@ -346,6 +423,7 @@ int m4ri_amd_pluq_solve_left_dev(const word *, int64_t, int64_t, int64_t, int32_
 int main() {
   join_family();
   pivot_exchange();
+  isd_search();
   sizes_beyond_int64();
   printf("%d checks, %d failed\n", n, fails);
   return fails != 0;
