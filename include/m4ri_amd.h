@@ -971,6 +971,61 @@ int m4ri_amd_isd_search_dev(word *D, int64_t d_stride, int64_t d_bs, int64_t nro
  * the call exists for members that stay resident.  The environment variable M4RI_AMD_ISD_SEARCH_PATH0_MAX (the largest side of
  * path 0, clamped to [0, 64]) replaces the bound in the routing of a call, read per call; this function does not read it. */
 int m4ri_amd_plan_isd_search(int64_t nrows, int64_t ncols, int64_t pivot_rows, int64_t t);
+/* A whole STERN COLLISION DECODING SEARCH on the stored reduced echelon forms of `batch` members, one launch
+ * (isd_collide_search_batch.hip): up to `iters` times "exchange `steps` pivots, then join the sums of t1 of the first k1 pivot rows and
+ * of t2 of the other pivot rows on a window of ell non-information columns and weigh the colliding pairs against the received word",
+ * the lightest word seen kept with its key and its iteration, a member stopped as soon as that weight is <= w_stop.  The rule is a
+ * composition of two calls of this header, and the results equal theirs bit for bit.
+ * The state is exactly that of m4ri_amd_isd_search_dev: D_b in place, pivots in/out, rank READ ONLY, order in/out.  k = pivot_rows;
+ * G_b = rows 0 .. k-1 of the current D_b; V_b = row k of the current D_b if nrows > pivot_rows, else the zero word; further followers
+ * only follow.
+ * The rule.  Iteration it = 0, 1, ... of member b:
+ * 1. If it > 0: `steps` exchanges exactly as m4ri_amd_pivot_exchange_batch_dev(req = NULL, steps, seed = seed_it) performs them on this
+ *    member -- the same draw, the same validity test, the same update of D, pivots and order -- with seed_it = output number `it` of the
+ *    counter-form splitmix64 stream seeded `seed` (m4ri_amd.isd_iteration_seed).  Iteration 0 enumerates the form as the caller left it.
+ * 2. key_it = what m4ri_amd_row_sums_collide_batch_dev(G_b, k, n = ncols, V_b, k1, t1, t2, cols = order + b * o_bs + pivot_rows, ell,
+ *    w_min) writes to lightest on the form and the order AS THEY STAND AFTER STEP 1: the minimum of (wt << 40) | (r1 * N2 + r2) over
+ *    the colliding pairs with wt >= w_min (N1 = C(k1, t1), N2 = C(k - k1, t2), m4ri_amd.row_pair_unrank splits the rank), -1 if there
+ *    is none, and -2 -- the composition's refused form -- if one of the ell window entries is outside 0 .. ncols-1.  The window is
+ *    range-checked on the device in every iteration: an exchange swaps the leaving pivot column into the place of the entering one,
+ *    which may lie in the window.  With ell = 0 every pair collides and order may be NULL (none kept).
+ * 3. The best is replaced iff key_it >= 0 and (best < 0 or (key_it >> 40) < (best >> 40)): only a strictly lighter word replaces it, so
+ *    the earliest iteration wins among equal weights.  Then best = key_it, best_iter = it and W_b = V_b ^ rows S1 ^ rows S2 of that pair
+ *    on the form of this iteration (only the ncols valid bits of W_b, at W + b * w_bs, are written).
+ * 4. If best >= 0 and (best >> 40) <= w_stop the member stops, iters_run[b] = it + 1.  A negative w_stop never stops a member.
+ * Otherwise the loop ends after `iters` iterations, iters_run[b] = iters.  D_b, pivots and order are left as the last iteration run
+ * left them, so calls chain; done[b] = all exchange steps performed.  best (DEVICE int64) is required; best_iter, iters_run, done
+ * (DEVICE int32) and W are optional.  Every wanted output is written whole -- best_iter[b] = -1 where best[b] < 0 -- except that W_b of
+ * a member with best < 0 is not written, and a member's D, pivots and order are written only if a step was performed.  iters = 0 gives
+ * best = -1 and iters_run = 0 and touches nothing else.  A member whose window is refused in every iteration ends with best = -1.
+ * hipErrorInvalidValue, before any HIP call: everything m4ri_amd_isd_search_dev refuses on the arguments the two share; k1 < 0 or
+ * k1 > pivot_rows; negative t1, t2 or ell; ell > 0 with a NULL order or with olen < pivot_rows + ell (the window is entries
+ * pivot_rows .. pivot_rows + ell - 1 of the order).  hipErrorNotSupported (801), before any HIP call: pivot_rows or ncols > 1024, t1
+ * or t2 > 8, ell > 64, N1 > 8192, N2 > 2^24 (one workgroup walks its member's whole right list in every iteration; beyond that the two
+ * calls, which slice the list over the chip, are the tool), N1 * N2 > 2^40, counts beyond 32 bits (iters or (iters - 1) * steps >
+ * 2^31 - 1), or a member m4ri_amd_plan_isd_collide_search does not place.  batch = 0 succeeds and touches nothing.  Asynchronous on
+ * `stream`: plain launches, no allocation, no copy to the host, no engine lock, no global atomics; capturable.
+ * WHICH TO USE (measured at 16 iterations, steps 1 and 4, a received word): this call is ahead of the loop of the two
+ * calls at every measured shape, each time beyond the spread -- 6.2x and 3.8x at 32 x 64 (65 536 members, t = 1 + 1, ell = 4), 5.8x and
+ * 4.6x at 64 x 128 (t = 1 + 1, ell = 5), where the loop's stagings, launches and reads of the rows from global memory are the time;
+ * 1.8x at 64 x 128 with t = 2 + 2, ell = 9 and 2.2x and 2.1x at 256 x 512 (4 096 members, t = 2 + 2, ell = 13), where the join is --
+ * and only it keeps the running minimum, writes the winning word and stops a member on the device (w_stop at the median best weight:
+ * 9.9 of 16 iterations per member in 0.67 of the time).  It lost at no measured shape.  Not measured: other t, shapes between these,
+ * and batches too small to fill the chip: there, beyond 2^24 right sums per member (refused here) and for a handful of large members
+ * use the two calls, which slice one member's right list over the chip while here one workgroup walks it all. */
+int m4ri_amd_isd_collide_search_dev(word *D, int64_t d_stride, int64_t d_bs, int64_t nrows, int64_t ncols, int64_t pivot_rows, int32_t *pivots,
+                                    const int32_t *rank, int64_t batch, int64_t iters, int64_t steps, uint64_t seed, int64_t k1, int64_t t1,
+                                    int64_t t2, int64_t ell, int64_t w_min, int64_t w_stop, int32_t *order, int64_t o_bs, int64_t olen,
+                                    int64_t *best, int32_t *best_iter, int32_t *iters_run, int32_t *done, word *W, int64_t w_bs, void *stream);
+/* whether the call above places members of this shape (pure host arithmetic; -1 for negative sizes or k1 > pivot_rows): 1 one
+ * workgroup per member, staged in LDS once for the whole loop -- path 1's staging of m4ri_amd_plan_isd_search (the word of
+ * words(ncols) words and an order of ncols entries included), rounded up to 16 bytes, then pivot_rows + 1 row keys of 8 bytes, N1
+ * sorted keys of 8 bytes, 128 bytes of wave minima, 2^q bucket ends of 4 bytes (q = ceil(log2 N1) held at ell), 4096 bytes of scan
+ * sums, a window of 256 bytes and N1 left indices of 2 bytes (rounded up to 16), plus 256 bytes the kernel keeps for itself, within
+ * 160 KiB; 2 everything else, the limits above included: the call returns 801.  There is no wave-per-member path: small members get a
+ * small workgroup instead.  The environment variable M4RI_AMD_ISD_COLLIDE_SEARCH_THREADS (a multiple of 64 in [64, 1024]) replaces
+ * the workgroup size of a call, read per call: results do not depend on it. */
+int m4ri_amd_plan_isd_collide_search(int64_t nrows, int64_t ncols, int64_t pivot_rows, int64_t k1, int64_t t1, int64_t t2, int64_t ell);
 /* `batch` independent systems A_b X_b = B_b (mzd_solve_left, m4ri/solve.c:30-152; solve_batch.hip).  A_b: the m x n matrix at
  * A + b * a_bs, READ ONLY (a_bs = 0: one A shared by all members).  B_b: the max(m, n) x k matrix at B + b * b_bs.  status[b]
  * (DEVICE int32, required): 0, or -1 when A_b X = B_b has no solution, A_b padded with zero rows to max(m, n).  On status 0, B_b is

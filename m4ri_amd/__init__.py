@@ -233,6 +233,9 @@ SYMBOLS = {
     "m4ri_amd_isd_search_dev": (_I, [_P, _I64, _I64, _I64, _I64, _I64, _P, _P, _I64, _I64, _I64, ctypes.c_uint64, _I64, _I64, _I64, _P, _I64, _I64, _P, _P, _P,
                                      _P, _P, _I64, _P]),
     "m4ri_amd_plan_isd_search": (_I, [_I64, _I64, _I64, _I64]),
+    "m4ri_amd_isd_collide_search_dev": (_I, [_P, _I64, _I64, _I64, _I64, _I64, _P, _P, _I64, _I64, _I64, ctypes.c_uint64, _I64, _I64, _I64, _I64, _I64, _I64, _P,
+                                             _I64, _I64, _P, _P, _P, _P, _P, _I64, _P]),
+    "m4ri_amd_plan_isd_collide_search": (_I, [_I64, _I64, _I64, _I64, _I64, _I64, _I64]),
     "m4ri_amd_solve_left_batch_dev": (_I, [_P, _I64, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I64, _P, _P, _P]),
     "m4ri_amd_inv_batch_dev": (_I, [_P, _I64, _I64, _P, _I64, _I64, _I64, _I64, _P, _P]),
     "m4ri_amd_plan_solve_batch": (_I, [_I64, _I64, _I64]),
@@ -984,6 +987,30 @@ def isd_search_dev(D: int, d_stride: int, d_bs: int, nrows: int, ncols: int, piv
 def plan_isd_search(nrows: int, ncols: int, pivot_rows: int, t: int) -> int:
     """The path isd_search_dev takes for members of this shape at this t (0 wave, 1 LDS, 2 not supported).  Host arithmetic."""
     return int(lib().m4ri_amd_plan_isd_search(nrows, ncols, pivot_rows, t))
+
+
+def isd_collide_search_dev(D: int, d_stride: int, d_bs: int, nrows: int, ncols: int, pivot_rows: int, pivots: int, rank: int, batch: int, iters: int,
+                           steps: int, seed: int, k1: int, t1: int, t2: int, ell: int, w_min: int, w_stop: int, best: int, order: int = 0, o_bs: int = 0,
+                           olen: int = 0, best_iter: int = 0, iters_run: int = 0, done: int = 0, W: int = 0, w_bs: int = 0, stream: int = 0) -> None:
+    """A whole Stern collision decoding search in one launch, on the state of pivot_exchange_batch_dev: up to `iters` times "`steps`
+    exchanges drawn from the stream seeded isd_iteration_seed(seed, it) (none before iteration 0), then the lightest colliding pair of a
+    sum of t1 of the first k1 pivot rows and a sum of t2 of the others against row pivot_rows (the received word; the zero word if
+    nrows == pivot_rows) on the window order[pivot_rows : pivot_rows + ell] with weight >= w_min", as pivot_exchange_batch_dev and
+    row_sums_collide_batch_dev give them.  best (DEVICE int64, required): the key (wt << 40) | pair rank (row_pair_unrank splits it) of
+    the lightest word over the iterations, the earliest among equal weights, -1 for none; best_iter, iters_run, done (DEVICE int32,
+    0 = not wanted): its iteration, the iterations run (a member stops once its best weight is <= w_stop; w_stop < 0: never) and the
+    steps performed; W (0 = not wanted): the word itself, member b's at W + b * w_bs.  ell > 0 needs the order (DEVICE int32, in/out)
+    with olen >= pivot_rows + ell.  Asynchronous, lock-free and capturable where plan_isd_collide_search gives 1; otherwise 801."""
+    _check(lib().m4ri_amd_isd_collide_search_dev(D or None, d_stride, d_bs, nrows, ncols, pivot_rows, pivots or None, rank or None, batch, iters, steps,
+                                                 seed & 0xFFFFFFFFFFFFFFFF, k1, t1, t2, ell, w_min, w_stop, order or None, o_bs, olen, best or None,
+                                                 best_iter or None, iters_run or None, done or None, W or None, w_bs, stream),
+           "m4ri_amd_isd_collide_search_dev")
+
+
+def plan_isd_collide_search(nrows: int, ncols: int, pivot_rows: int, k1: int, t1: int, t2: int, ell: int) -> int:
+    """Whether isd_collide_search_dev places members of this shape and this split (1 a workgroup per member in LDS, 2 not supported,
+    -1 negative sizes or k1 > pivot_rows).  Host arithmetic."""
+    return int(lib().m4ri_amd_plan_isd_collide_search(nrows, ncols, pivot_rows, k1, t1, t2, ell))
 
 
 def isd_iteration_seed(seed: int, it: int) -> int:

@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "csrc", "_obj")
 LIB = os.path.join(HERE, "libm4ri_amd.so")
-SOURCES = ["m4rm_leaf.hip", "a4_pack.hip", "m4rm8q_leaf.hip", "m4rm_small.hip", "aux_kernels.hip", "scheme_passes.hip", "engine.hip", "mzd_api.hip", "multi.hip", "trsm.hip", "ple.hip", "elim.hip", "echelon.hip", "echelon_batch.hip", "echelon_order_batch.hip", "pivot_exchange_batch.hip", "isd_search_batch.hip", "solve.hip", "solve_batch.hip", "ple_batch.hip", "mul_small_batch.hip", "transpose.hip", "transpose_batch.hip", "reduce_batch.hip", "rowspace_batch.hip", "rowsums_batch.hip", "rowsums_collide_batch.hip", "rowsums_words_batch.hip", "lists_collide_batch.hip", "sort_rows_batch.hip", "assemble_batch.hip", "io.cpp", "small_host.cpp", "host_pipeline_plan.cpp"]
+SOURCES = ["m4rm_leaf.hip", "a4_pack.hip", "m4rm8q_leaf.hip", "m4rm_small.hip", "aux_kernels.hip", "scheme_passes.hip", "engine.hip", "mzd_api.hip", "multi.hip", "trsm.hip", "ple.hip", "elim.hip", "echelon.hip", "echelon_batch.hip", "echelon_order_batch.hip", "pivot_exchange_batch.hip", "isd_search_batch.hip", "isd_collide_search_batch.hip", "solve.hip", "solve_batch.hip", "ple_batch.hip", "mul_small_batch.hip", "transpose.hip", "transpose_batch.hip", "reduce_batch.hip", "rowspace_batch.hip", "rowsums_batch.hip", "rowsums_collide_batch.hip", "rowsums_words_batch.hip", "lists_collide_batch.hip", "sort_rows_batch.hip", "assemble_batch.hip", "io.cpp", "small_host.cpp", "host_pipeline_plan.cpp"]
 # The test-only library of the fused passes (tests/pass_lib.py binds it; it is not API and not part of the product): the objects of the
 # pass sources linked a second time, with the internal launchers the pass tests call as its only exports.  libm4ri_amd.so keeps them local.
 PASS_LIB = os.path.join(HERE, "libm4ri_amd_passes.so")

@@ -284,6 +284,107 @@ static void isd_search() {
   EXPECT(m4ri_amd_plan_isd_search(5, 5, 1, -1), -1);
 }
 
+// ---- the collision search of information-set decoding ---------------------------------------------------------------------------------------
+static void isd_collide_search() {
+  // the operands of isd_search(); four pivot rows split 2 + 2, a sum of one row of each half, the window the order's entries 4 .. 6
+  const int64_t M = INT64_MAX;
+  word *D = (word *)(1ull << 20), *W = (word *)(1ull << 36);
+  int32_t *P = (int32_t *)(1ull << 22), *R = (int32_t *)(1ull << 24), *O = (int32_t *)(1ull << 26), *I = (int32_t *)(1ull << 30), *U = (int32_t *)(1ull << 32),
+          *N = (int32_t *)(1ull << 34);
+  int64_t *B = (int64_t *)(1ull << 28);
+  auto at = [](void *p, long bytes) { return (int32_t *)((char *)p + bytes); };
+#define ICS(D_, ds, dbs, nr, nc, pr, P_, R_, batch, iters, steps, k1, t1, t2, ell, wmin, wstop, O_, obs, olen, B_, I_, U_, N_, W_, wbs) \
+  m4ri_amd_isd_collide_search_dev(D_, ds, dbs, nr, nc, pr, P_, R_, batch, iters, steps, 7, k1, t1, t2, ell, wmin, wstop, O_, obs, olen, B_, I_, U_, N_, W_, wbs, nullptr)
+  EXPECT(ICS(D, 1, 5, 5, 64, 4, P, R, 0, 6, 3, 2, 1, 1, 3, 1, 3, O, 64, 64, B, I, U, N, W, 1), 0);                       // batch = 0
+  EXPECT(ICS(nullptr, 1, 5, 5, 64, 4, nullptr, nullptr, 0, 0, 0, 0, 0, 0, 0, 0, -1, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, 0), 0);
+  EXPECT(ICS(D, 1, 5, -1, 64, 0, P, R, 2, 6, 3, 0, 1, 1, 3, 1, 3, O, 64, 64, B, I, U, N, W, 1), 1);
+  EXPECT(ICS(D, 1, 5, 5, 64, 4, P, R, -1, 6, 3, 2, 1, 1, 3, 1, 3, O, 64, 64, B, I, U, N, W, 1), 1);
+  EXPECT(ICS(D, 1, 5, 5, 64, 4, P, R, 2, -1, 3, 2, 1, 1, 3, 1, 3, O, 64, 64, B, I, U, N, W, 1), 1);                      // iters < 0
+  EXPECT(ICS(D, 1, 5, 5, 64, 4, P, R, 2, 6, -1, 2, 1, 1, 3, 1, 3, O, 64, 64, B, I, U, N, W, 1), 1);                      // steps < 0
+  EXPECT(ICS(D, 1, 5, 5, 64, 4, P, R, 2, 6, 3, -1, 1, 1, 3, 1, 3, O, 64, 64, B, I, U, N, W, 1), 1);                      // k1 < 0
+  EXPECT(ICS(D, 1, 5, 5, 64, 4, P, R, 2, 6, 3, 5, 1, 1, 3, 1, 3, O, 64, 64, B, I, U, N, W, 1), 1);                       // k1 > pivot_rows
+  EXPECT(ICS(D, 1, 5, 5, 64, 4, P, R, 2, 6, 3, M, 1, 1, 3, 1, 3, O, 64, 64, B, I, U, N, W, 1), 1);
+  EXPECT(ICS(D, 1, 5, 5, 64, 4, P, R, 2, 6, 3, 2, -1, 1, 3, 1, 3, O, 64, 64, B, I, U, N, W, 1), 1);                      // t1 < 0
+  EXPECT(ICS(D, 1, 5, 5, 64, 4, P, R, 2, 6, 3, 2, 1, -1, 3, 1, 3, O, 64, 64, B, I, U, N, W, 1), 1);                      // t2 < 0
+  EXPECT(ICS(D, 1, 5, 5, 64, 4, P, R, 2, 6, 3, 2, 1, 1, -1, 1, 3, O, 64, 64, B, I, U, N, W, 1), 1);                      // ell < 0
+  EXPECT(ICS(D, 1, 5, 5, 64, 4, P, R, 2, 6, 3, 2, 1, 1, 3, -1, 3, O, 64, 64, B, I, U, N, W, 1), 1);                      // w_min < 0
+  EXPECT(ICS(D, 1, 5, 5, 64, 4, P, R, 2, 6, 3, 2, 1, 1, 3, 1, 3, O, 64, 64, B, I, U, N, W, -1), 1);                      // w_bs < 0
+  EXPECT(ICS(D, 1, 5, 5, 64, 6, P, R, 2, 6, 3, 2, 1, 1, 3, 1, 3, O, 64, 64, B, I, U, N, W, 1), 1);                       // pivot_rows > nrows
+  EXPECT(ICS(D, 1, 5, 5, 64, 4, P, R, 2, 6, 3, 2, 1, 1, 3, 1, 3, O, 65, 65, B, I, U, N, W, 1), 1);                       // olen > ncols
+  EXPECT(ICS(D, 1, 5, 5, 64, 4, P, R, 2, 6, 3, 2, 1, 1, 3, 1, 3, nullptr, 64, 64, B, I, U, N, W, 1), 1);                 // a window without its order
+  EXPECT(ICS(D, 1, 5, 5, 64, 4, P, R, 0, 6, 3, 2, 1, 1, 3, 1, 3, nullptr, 64, 64, B, I, U, N, W, 1), 1);                 // with no member either
+  EXPECT(ICS(D, 1, 5, 5, 64, 4, P, R, 2, 6, 3, 2, 1, 1, 3, 1, 3, O, 64, 6, B, I, U, N, W, 1), 1);                        // olen < pivot_rows + ell
+  EXPECT(ICS(D, 1, 5, 5, 64, 4, P, R, 0, 6, 3, 2, 1, 1, 3, 1, 3, O, 64, 7, B, I, U, N, W, 1), 0);                        // olen = pivot_rows + ell
+  EXPECT(ICS(D, 1, 5, 5, 64, 4, P, R, 2, 6, 3, 2, 1, 1, M, 1, 3, O, 64, 64, B, I, U, N, W, 1), 1);                       // pivot_rows + ell beyond 64 bits
+  EXPECT(ICS(D, 1, 5, 5, 64, 4, P, R, 0, 6, 3, 2, 1, 1, 0, 1, 3, nullptr, 0, 0, B, I, U, N, W, 1), 0);                   // no window: no order needed
+  EXPECT(ICS(D, 0, 5, 5, 64, 4, P, R, 2, 6, 3, 2, 1, 1, 3, 1, 3, O, 64, 64, B, I, U, N, W, 1), 1);                       // d_stride < words
+  EXPECT(ICS(D, 1, 4, 5, 64, 4, P, R, 2, 6, 3, 2, 1, 1, 3, 1, 3, O, 64, 64, B, I, U, N, W, 1), 1);                       // overlapping members
+  EXPECT(ICS(D, 1, 5, 5, 64, 4, P, R, 2, 6, 3, 2, 1, 1, 3, 1, 3, O, 63, 64, B, I, U, N, W, 1), 1);                       // o_bs < olen
+  EXPECT(ICS(D, 1, 5, 5, 64, 4, P, R, 2, 6, 3, 2, 1, 1, 3, 1, 3, O, 64, 64, B, I, U, N, W, 0), 1);                       // w_bs < words
+  EXPECT(ICS(nullptr, 1, 5, 5, 64, 4, P, R, 2, 6, 3, 2, 1, 1, 3, 1, 3, O, 64, 64, B, I, U, N, W, 1), 1);
+  EXPECT(ICS(D, 1, 5, 5, 64, 4, nullptr, R, 2, 6, 3, 2, 1, 1, 3, 1, 3, O, 64, 64, B, I, U, N, W, 1), 1);
+  EXPECT(ICS(D, 1, 5, 5, 64, 4, P, nullptr, 2, 6, 3, 2, 1, 1, 3, 1, 3, O, 64, 64, B, I, U, N, W, 1), 1);
+  EXPECT(ICS(D, 1, 5, 5, 64, 4, P, R, 2, 6, 3, 2, 1, 1, 3, 1, 3, O, 64, 64, nullptr, I, U, N, W, 1), 1);                 // best is required
+  EXPECT(ICS(D, 1, 5, 5, 64, 4, P, R, 2, 0, 3, 2, 1, 1, 3, 1, 3, O, 64, 64, nullptr, I, U, N, W, 1), 1);                 // without iterations too
+  EXPECT(ICS(D, 1, 5, 5, 64, 4, at(D, 76), R, 2, 6, 3, 2, 1, 1, 3, 1, 3, O, 64, 64, B, I, U, N, W, 1), 1);               // pivots on D's last word
+  EXPECT(ICS(D, 1, 5, 5, 64, 4, P, at(P, 28), 2, 6, 3, 2, 1, 1, 3, 1, 3, O, 64, 64, B, I, U, N, W, 1), 1);               // rank on pivots
+  EXPECT(ICS(D, 1, 5, 5, 64, 4, P, R, 2, 6, 3, 2, 1, 1, 3, 1, 3, at(R, 4), 64, 64, B, I, U, N, W, 1), 1);                // order on rank
+  EXPECT(ICS(D, 1, 5, 5, 64, 4, P, R, 2, 6, 3, 2, 1, 1, 3, 1, 3, O, 64, 64, (int64_t *)at(O, 504), I, U, N, W, 1), 1);   // best on order
+  EXPECT(ICS(D, 1, 5, 5, 64, 4, P, R, 2, 6, 3, 2, 1, 1, 3, 1, 3, O, 64, 64, B, at(B, 12), U, N, W, 1), 1);               // best_iter on best
+  EXPECT(ICS(D, 1, 5, 5, 64, 4, P, R, 2, 6, 3, 2, 1, 1, 3, 1, 3, O, 64, 64, B, I, at(I, 4), N, W, 1), 1);                // iters_run on best_iter
+  EXPECT(ICS(D, 1, 5, 5, 64, 4, P, R, 2, 6, 3, 2, 1, 1, 3, 1, 3, O, 64, 64, B, I, U, U, W, 1), 1);                       // done on iters_run
+  EXPECT(ICS(D, 1, 5, 5, 64, 4, P, R, 2, 6, 3, 2, 1, 1, 3, 1, 3, O, 64, 64, B, I, U, N, (word *)at(N, 0), 1), 1);        // W on done
+  EXPECT(ICS(D, 1, 5, 5, 64, 4, P, R, 2, 6, 3, 2, 1, 1, 3, 1, 3, O, 64, 64, B, I, U, N, D + 9, 1), 1);                   // W on D's last word
+  EXPECT(ICS(D, 1, 5, 5, 64, 4, P, R, 2, 6, 3, 2, 1, 1, 3, 1, 3, O, 64, 64, B, I, U, N, (word *)(1ull << 19), M), 1);    // W below all: its 2^66 bytes reach everything
+  EXPECT(ICS(D, 1, M, 5, 64, 4, P, R, 2, 6, 3, 2, 1, 1, 3, 1, 3, O, 64, 64, B, I, U, N, nullptr, 0), 1);                 // and D's
+  EXPECT(ICS(D, 1, 5, 5, 64, 4, P, R, 2, 6, 3, 2, 1, 1, 3, 1, 3, O, M, 64, B, I, U, N, W, 1), 1);                        // and the order's
+  // the limits, with and without members
+  EXPECT(ICS(D, 1, 5, 5, 64, 4, P, R, 2, 6, 3, 2, 9, 1, 3, 1, 3, O, 64, 64, B, I, U, N, W, 1), 801);                     // t1 > 8
+  EXPECT(ICS(D, 1, 5, 5, 64, 4, P, R, 0, 6, 3, 2, 1, M, 3, 1, 3, O, 64, 64, B, I, U, N, W, 1), 801);                     // t2 > 8
+  EXPECT(ICS(D, 2, 10, 5, 128, 4, P, R, 0, 6, 3, 2, 1, 1, 65, 1, 3, O, 128, 128, B, I, U, N, W, 2), 801);                // ell > 64
+  EXPECT(ICS(D, 2, 10, 5, 128, 4, P, R, 0, 6, 3, 2, 1, 1, 64, 1, 3, O, 128, 128, B, I, U, N, W, 2), 0);
+  EXPECT(ICS(D, 1, 1 << 20, 1025, 64, 1025, P, R, 2, 6, 3, 2, 1, 1, 0, 1, 3, O, 64, 64, B, I, U, N, W, 1), 801);         // pivot_rows > 1024
+  EXPECT(ICS(D, 17, 1 << 20, 5, 1025, 4, P, R, 2, 6, 3, 2, 1, 1, 0, 1, 3, nullptr, 0, 0, B, I, U, N, W, 17), 801);       // ncols > 1024
+  EXPECT(ICS(D, 1, 1 << 20, 137, 64, 136, P, R, 0, 6, 3, 128, 2, 1, 0, 1, 3, O, 64, 64, B, I, U, N, W, 1), 0);           // N1 = 8128
+  EXPECT(ICS(D, 1, 1 << 20, 138, 64, 137, P, R, 0, 6, 3, 129, 2, 1, 0, 1, 3, O, 64, 64, B, I, U, N, W, 1), 801);         // N1 = 8256
+  EXPECT(ICS(D, 1, 1 << 20, 1024, 64, 1024, P, R, 0, 6, 3, 8, 1, 2, 0, 1, 3, O, 64, 64, B, I, U, N, W, 1), 0);           // N2 = C(1016, 2)
+  EXPECT(ICS(D, 1, 1 << 20, 1024, 64, 1024, P, R, 0, 6, 3, 8, 1, 3, 0, 1, 3, O, 64, 64, B, I, U, N, W, 1), 801);         // N2 = C(1016, 3) > 2^24
+  EXPECT(ICS(D, 1, 1 << 20, 1024, 64, 1024, P, R, 2, 6, 3, 8, 1, 2, 0, 1, 3, O, 64, 64, B, I, U, N, W, 1), 1);           // in: D reaches pivots
+  EXPECT(ICS(D, 16, 1 << 20, 2000, 1024, 4, P, R, 2, 6, 3, 2, 1, 1, 3, 1, 3, nullptr, 0, 0, B, I, U, N, W, 16), 1);      // the window's order before the LDS
+  EXPECT(ICS(D, 16, 1 << 20, 2000, 1024, 4, P, R, 2, 6, 3, 2, 1, 1, 0, 1, 3, nullptr, 0, 0, B, I, U, N, W, 16), 801);    // beyond LDS
+  EXPECT(ICS(D, M, M, M, M, M, P, R, 2, M, M, M, M, M, 0, M, M, O, M, M, B, I, U, N, W, M), 801);
+  EXPECT(ICS(D, M, M, M, M, M, P, R, 2, M, M, M, M, M, M, M, M, O, M, M, B, I, U, N, W, M), 1);                          // 2 M > olen over the integers
+  EXPECT(ICS(D, M, M, M, 64, 4, P, R, 0, 6, 3, 2, 1, 1, 3, 1, 3, O, 64, 64, B, I, U, N, W, 1), 801);                     // INT64_MAX rows
+  EXPECT(ICS(D, 1, 5, 5, 64, 4, P, R, 2, M, 3, 2, 1, 1, 3, 1, 3, O, 64, 64, B, I, U, N, W, 1), 801);                     // 32-bit counts
+  EXPECT(ICS(D, 1, 5, 5, 64, 4, P, R, 2, 6, M, 2, 1, 1, 3, 1, 3, O, 64, 64, B, I, U, N, W, 1), 801);
+  EXPECT(ICS(D, 1, 5, 5, 64, 4, P, R, 2, M, M, 2, 1, 1, 3, 1, 3, O, 64, 64, B, I, U, N, W, 1), 801);
+  EXPECT(ICS(D, 1, 5, 5, 64, 4, P, R, 0, INT32_MAX, 1, 2, 1, 1, 3, M, M, O, 64, 64, B, I, U, N, W, 1), 0);
+  EXPECT(ICS(D, 1, 5, 5, 64, 4, P, R, 0, 1, M, 2, 1, 1, 3, 1, -M, O, 64, 64, B, I, U, N, W, 1), 0);                      // one iteration: no step
+  EXPECT(ICS(D, 1, 5, 5, 64, 4, P, R, 0, (int64_t)INT32_MAX + 1, 0, 2, 1, 1, 3, 1, 3, O, 64, 64, B, I, U, N, W, 1), 801);
+  EXPECT(ICS(D, 0, 5, 5, 64, 4, P, R, 2, 6, 3, 2, 9, 1, 3, 1, 3, O, 64, 64, B, I, U, N, W, 1), 1);                       // the stride before the limits
+  setenv("M4RI_AMD_ISD_COLLIDE_SEARCH_THREADS", "junk", 1);
+  EXPECT(ICS(D, 1, 5, 5, 64, 4, P, R, 0, 6, 3, 2, 1, 1, 3, 1, 3, O, 64, 64, B, I, U, N, W, 1), 0);
+  setenv("M4RI_AMD_ISD_COLLIDE_SEARCH_THREADS", "-99999999999999999999", 1);
+  EXPECT(ICS(D, 1, 5, 5, 64, 4, P, R, 0, 6, 3, 2, 9, 1, 3, 1, 3, O, 64, 64, B, I, U, N, W, 1), 801);
+  unsetenv("M4RI_AMD_ISD_COLLIDE_SEARCH_THREADS");
+#undef ICS
+  EXPECT(m4ri_amd_plan_isd_collide_search(0, 0, 0, 0, 0, 0, 0), 1);
+  EXPECT(m4ri_amd_plan_isd_collide_search(64, 64, 63, 31, 3, 3, 12), 1);                                                   // no wave path
+  EXPECT(m4ri_amd_plan_isd_collide_search(137, 200, 136, 128, 2, 1, 64), 1);
+  EXPECT(m4ri_amd_plan_isd_collide_search(138, 200, 137, 129, 2, 1, 64), 2);
+  EXPECT(m4ri_amd_plan_isd_collide_search(1024, 1024, 1024, 8, 1, 1, 0), 1);
+  EXPECT(m4ri_amd_plan_isd_collide_search(1024, 1024, 1024, 512, 1, 1, 0), 2);                                             // the table no longer fits beside the member
+  EXPECT(m4ri_amd_plan_isd_collide_search(1024, 64, 1024, 8, 1, 3, 0), 2);
+  EXPECT(m4ri_amd_plan_isd_collide_search(64, 64, 64, 32, 9, 1, 0), 2);
+  EXPECT(m4ri_amd_plan_isd_collide_search(64, 128, 32, 16, 1, 1, 65), 2);
+  EXPECT(m4ri_amd_plan_isd_collide_search(2000, 1024, 4, 2, 1, 1, 0), 2);
+  EXPECT(m4ri_amd_plan_isd_collide_search(M, M, M, M, M, M, M), 2);
+  EXPECT(m4ri_amd_plan_isd_collide_search(M, 64, 4, 2, 0, 0, 0), 2);
+  EXPECT(m4ri_amd_plan_isd_collide_search(-1, 5, 1, 0, 1, 1, 0), -1);
+  EXPECT(m4ri_amd_plan_isd_collide_search(5, 5, 4, 5, 1, 1, 0), -1);                                                       // k1 > pivot_rows
+  EXPECT(m4ri_amd_plan_isd_collide_search(5, 5, 4, 2, 1, 1, -1), -1);
+}
+
 // ---- the calls on single operands: elimination, solves, products, transposes, reductions, assembly, weights --------------------------
 // Operands at ascending addresses 2^20 apart, A lowest: a span that is too long by the integers reaches every operand above it.
 static void sizes_beyond_int64() {
@@ -424,6 +525,7 @@ int main() {
   join_family();
   pivot_exchange();
   isd_search();
+  isd_collide_search();
   sizes_beyond_int64();
   printf("%d checks, %d failed\n", n, fails);
   return fails != 0;
